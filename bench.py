@@ -10,6 +10,12 @@ task_mlm_itm_ifm (one training_step = mlm joint pass + ifm image/text passes + 3
 AdamW step), train mode (DropPath / dropout live), synthetic batch, random-init weights, bf16 MFMA
 GEMMs with fp32 accumulation and an fp32 residual stream.  N > 1: weak scaling, gradient all-reduce over RCCL.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the JSON line.  `--full` adds
+everything else the line can carry: the per-launch GEMM / attention roofline (HIP events around every n-th timed step),
+the attainable-peak probes, the other BASELINE configs' legs, the merge leg, the CPU baseline and the parity gates (each
+can still be dropped with its --no-* option).  `--dump-outputs DIR` writes what the last timed step computed (loss, and a
+fixed sample of the updated parameters) as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -471,9 +477,10 @@ class TrainLeg:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(self, steps, warmup, dev, per_step=None):
+    def timed(self, steps, warmup, dev, per_step=None, timeline=True):
         """`warmup` untimed steps, then EXACTLY `steps` steps between two barrier + synchronize fences; the time is the MAX
-        over the ranks.  per_step(i): hook in front of timed step i (the headline leg switches its GEMM timer there)."""
+        over the ranks.  per_step(i): hook in front of timed step i (the headline leg switches its GEMM timer there).
+        timeline: record the per-bucket timeline of the last step (grad_comm.bucket_timeline_last_step)."""
         loss = None
         for _ in range(warmup):
             loss = self.step()
@@ -492,7 +499,7 @@ class TrainLeg:
                 per_step(it)
             # per-bucket issue / complete times of the LAST timed step only (the communication stream then waits for each of its
             # collectives in turn: harmless, but kept out of the other steps)
-            self.reducer.timeline_on = self.rank == 0 and it == steps - 1
+            self.reducer.timeline_on = timeline and self.rank == 0 and it == steps - 1
             loss = self.step()
             marks[it + 1].record()
         self.reducer.timeline_on = False
@@ -727,6 +734,34 @@ def dry_run(args, rank, world):
                           "per_gpu_batchsize": args.batch, "baseline_config": cfg_index[args.arch]}))
 
 
+DUMP_SAMPLE_BASE = 4096  # per parameter: all of it up to this many elements, beyond that this many + 1/32 of the rest
+DUMP_SAMPLE_DIV = 32
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, as .npy files -- loss.npy (float64,
+    shape [1]) and params.npy (float32): the updated parameters in named_parameters() order, each a fixed sample
+    (indices drawn from a generator seeded by the parameter's name and size, sorted; the whole tensor when it is small),
+    concatenated (~22 MB at base size)."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    parts = []
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            n = flat.numel()
+            k = n if n <= DUMP_SAMPLE_BASE else DUMP_SAMPLE_BASE + (n - DUMP_SAMPLE_BASE) // DUMP_SAMPLE_DIV
+            if k < n:
+                rng = np.random.default_rng(zlib.crc32(("%s:%d" % (name, n)).encode()))
+                idx = torch.from_numpy(np.sort(rng.integers(0, n, size=k, dtype=np.int64))).to(flat.device)
+                flat = flat.index_select(0, idx)
+            parts.append(flat.float())
+        params = torch.cat(parts).cpu().numpy()
+    np.save(os.path.join(path, "loss.npy"), np.array([float(loss.detach())], dtype=np.float64))
+    np.save(os.path.join(path, "params.npy"), params.astype(np.float32, copy=False))
+
+
 def parity_gates(dev, mods, cpu, merge_check):
     """The checks that stand beside the numbers in the JSON line: (a) the merged buffer bench_merge
     has just timed against oracle/merge_oracle.py on a slice of its tensors, bit for bit; (b) the loss of one configs[0] step
@@ -794,6 +829,12 @@ def main():
     ap.add_argument("--no-calibrate", action="store_true", help="skip the attainable-peak probes")
     ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs' legs (the other two DP "
                                                                 "workloads at this N; at N = 1 also task vector, RegMean, Gram capture)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: GEMM / attention roofline, attainable peaks, "
+                         "secondary legs, merge leg, CPU baseline, parity gates (the --no-* options above apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss and a fixed sample of the updated parameters "
+                         "as DIR/*.npy (rank 0)")
     args = ap.parse_args()
     # host-side torch ops (model construction, the oracle) on every logical CPU of a 256-thread host are slower than on 16
     torch.set_num_threads(min(torch.get_num_threads(), 16))
@@ -846,10 +887,11 @@ def main():
     leg = TrainLeg(mods, args.task, args.arch, args.batch, args.image_size, rank, world, dev, force_dist)
     reducer = leg.reducer
     timer = GemmTimer(ops)
-    timer.install()
     atimer = AttnTimer(ops, timer)
-    atimer.install()
-    use_timer = rank == 0 and not args.no_gemm_timer
+    use_timer = args.full and rank == 0 and not args.no_gemm_timer
+    if use_timer:  # a plain run leaves the launch path as the product has it
+        timer.install()
+        atimer.install()
     # The steps whose GEMM launches are bracketed run with the weight-gradient side stream OFF: a launch that shares the chip
     # with another stream's kernel takes longer for reasons that are not its own, and the roofline figure is the kernel's own
     # duration.  (They stay inside the timed region: `value` pays for them.)
@@ -861,7 +903,7 @@ def main():
 
     if rank == 0:
         _phase("timed region: %d warm-up + %d steps" % (args.warmup, args.steps))
-    dt, loss = leg.timed(args.steps, args.warmup, dev, per_step)
+    dt, loss = leg.timed(args.steps, args.warmup, dev, per_step if use_timer else None, timeline=args.full)
     if rank == 0:
         _phase("timed region done: %.2f ms per step" % (dt / args.steps * 1e3))
     eng._WGRAD["enabled"] = side_default
@@ -877,6 +919,8 @@ def main():
         # a step whose activations are NaN runs FASTER (less switching power, higher clocks: docs/experiments.md round 6): a rate
         # measured on such a run is not a measurement
         raise RuntimeError("bench: the last timed step's loss is %r -- the timed steps did not compute the workload" % loss_val)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, leg.model, loss)
     total_samples = args.batch * world * args.steps
     value = total_samples / dt
     _, _, flop384, cfg_index, task_text = TASKS[args.task]
@@ -889,7 +933,7 @@ def main():
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "step_ms_rank0": [round(x, 2) for x in leg.step_ms],
             "ms_per_step_median": sorted(leg.step_ms)[len(leg.step_ms) // 2], "setup_steps": SETUP_STEPS,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "full": bool(args.full),
             "dtype": "bf16", "data": "synthetic",
             "config": {"workload": "base_vl %s %d^2 patch16 T=40 per_gpu_batchsize=%d %s fwd+bwd+AdamW, "
                                    "train mode (BASELINE configs[%d])" % (args.arch, args.image_size, args.batch, task_text,
@@ -931,14 +975,14 @@ def main():
             if ats:
                 # the kernels north_star puts a number on, timed in this run (not only in profiles/): same bracketed steps
                 out["roofline_attention"] = ats
-        if not args.no_calibrate:
+        if args.full and not args.no_calibrate:
             out["attainable"] = calibrate(dev)
     leg.close()
     del leg, reducer
 
     secondary = {}
     small = os.environ.get("VLM_BENCH_FORCE_SECONDARY", "0") != "0"  # tests: the legs at the headline's (small) geometry
-    if not args.no_secondary and (args.image_size == 384 or small):
+    if args.full and not args.no_secondary and (args.image_size == 384 or small):
         # every rank takes part: the other two data-parallel BASELINE workloads at this world size
         if rank == 0:
             _phase("secondary data-parallel legs")
@@ -948,7 +992,7 @@ def main():
         out["secondary"] = dict(secondary)
     if rank == 0:
         merge_check = None
-        if not args.no_merge:
+        if args.full and not args.no_merge:
             _phase("merge leg")
             bm = importlib.import_module("vl_merging_amd.bench_merge")
             m = bm.run(check_layers=(0, 11))
@@ -958,13 +1002,13 @@ def main():
                             "roofline": {"bound": "hbm", "achieved": m["GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                                          "frac": m["GBps"] / HBM_PEAK_GBPS,
                                          "traffic": pmc_traffic("vlm_merge_kernel"), "kernel": "vlm_merge_kernel"}}
-        if not args.no_secondary and world == 1 and not force_dist and args.image_size == 384:
+        if args.full and not args.no_secondary and world == 1 and not force_dist and args.image_size == 384:
             _phase("secondary merge legs (task vector, RegMean, Gram capture)")
             secondary.update(secondary_benches(dev))
         if secondary:
             out["secondary"] = secondary
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             _phase("CPU baseline (oracle on the host cores)")
             try:
                 cpu = cpu_baseline()

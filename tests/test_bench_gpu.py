@@ -1,5 +1,5 @@
-"""bench.py contract (the driver parses its LAST stdout line): one JSON object with the agreed fields, a roofline and a
-merge object; run at 2 timed steps so the test stays under a minute."""
+"""bench.py contract (the driver parses its LAST stdout line): one JSON object with the agreed fields; with --full also a
+roofline and a merge object; run at 2 timed steps so the test stays under a minute."""
 import json
 import os
 import subprocess
@@ -12,8 +12,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-calibrate", "--gemm-timer-every", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
+                        "--no-cpu-baseline", "--no-calibrate", "--gemm-timer-every", "1"], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = r.stdout.strip().splitlines()[-1]
     d = json.loads(line)
@@ -52,13 +53,38 @@ def test_bench_json_contract():
     assert all(0.0 < sec["gram_capture_base"][k]["frac_of_fp64_mfma_peak"] < 1.0 for k in ("D768", "D3072"))
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone (no roofline, merge, secondary legs, CPU baseline or parity runs),
+    --steps sets the number of timed steps, and --dump-outputs writes the last timed step's loss and parameter sample."""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--image-size", "224", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600,
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in d, k
+    assert d["full"] is False and d["steps"] == 3 and len(d["step_ms_rank0"]) == 3
+    assert abs(d["value"] - 2 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"] + 1e-3
+    for k in ("roofline", "roofline_attention", "attainable", "merge", "secondary", "cpu_baseline", "parity"):
+        assert k not in d, k
+    import numpy as np
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["loss.npy", "params.npy"], files
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    loss, params = np.load(out / "loss.npy"), np.load(out / "params.npy")
+    assert loss.dtype == np.float64 and loss.shape == (1,) and abs(loss[0] - d["config"]["final_loss"]) <= 1e-6 * abs(loss[0])
+    assert params.dtype == np.float32 and params.size > 1000 and np.isfinite(params).all()
+
+
 def _run_bench(argv, env=None, timeout=900):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True,
                        timeout=timeout, cwd=ROOT, env=dict(os.environ, **(env or {})))
     return r
 
 
-SMALL = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-calibrate", "--no-merge", "--batch", "2",
+SMALL = ["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-calibrate", "--no-merge", "--batch", "2",
          "--image-size", "224"]
 
 
@@ -103,7 +129,7 @@ def test_bench_irtr_task_at_two_ranks_with_secondary_legs_and_step_parity():
 @pytest.mark.gpu
 def test_bench_step_loss_gate_against_the_oracle():
     """The JSON line carries |loss_gpu - loss_oracle| of one configs[0] step (the oracle step is the CPU baseline's own)."""
-    r = _run_bench(["--steps", "2", "--warmup", "1", "--no-calibrate", "--no-merge", "--no-secondary", "--batch", "2",
+    r = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--no-calibrate", "--no-merge", "--no-secondary", "--batch", "2",
                     "--image-size", "224"], timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])

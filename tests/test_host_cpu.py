@@ -289,3 +289,19 @@ def test_round6_host_fallbacks_and_dispatch_rules(pkg, cfgmod, vm):
                  lambda: ops.sample_negatives(sim, sim, 6, torch.rand(2, 6))):
         with pytest.raises(L.VlmError):
             call()
+
+
+def test_table_transpose_keeps_broadcast_gradients(pkg):
+    """_TableT.backward drops only _BlockFn's placeholder (an expanded engine._zero_scalar); a genuine broadcast gradient
+    of the transposed table, such as the one of bias_t.sum(), reaches the table."""
+    engine = importlib.import_module("vl_merging_amd.engine")
+    table = torch.randn(7, 6, requires_grad=True)
+    rp = engine.make_relpos(table, None, None)
+    rp.bias_t.sum().backward()
+    assert table.grad is not None and torch.equal(table.grad, torch.ones(7, 6))
+    # the placeholder carries nothing: only what the attention kernels accumulated in the holder arrives
+    table.grad = None
+    rp = engine.make_relpos(table, None, None)
+    rp.holder["dbias_t"].fill_(2.0)
+    rp.bias_t.backward(engine._zero_scalar(table.device).expand_as(rp.bias_t))
+    assert torch.equal(table.grad, torch.full((7, 6), 2.0))

@@ -289,76 +289,38 @@ class _Side:
         return False
 
 
-# ----------------------------------------------------------------------------------------------------------------
-# modality experts on two streams: in an all_moe block the text rows (B*40) and the image rows (B*577) go through DIFFERENT
-# weights, so each expert's chain (LayerNorm -> GEMM ...) is an independent sequence of launches.  The text GEMMs are small
-# (M = 3 520: 168-504 tiles of 128x128 on 512 slots) and ran at a third of the image GEMMs' rate, 9.6 % of the all_moe step for
-# 6.5 % of its rows; issued on a second HIP stream they fill the CUs the image expert's last partial round of tiles leaves
-# idle.  Fork / join per phase (VLM_EXPERT_STREAMS=0 switches it off).
-_EXPERTS = {"stream": None, "enabled": os.environ.get("VLM_EXPERT_STREAMS", "1") != "0"}
-
-
-# Grouped GEMM (default): the experts' forward and dgrad GEMMs of a block are ONE launch each over both row
-# ranges (ops.gemm_grouped): the text expert's 14 row tiles ride in the image expert's rounds of 256x256 tiles instead of
-# under-filling launches of their own on the 128x128 kernel (9.6 % of the all_moe step for 6.5 % of its rows).  The two-stream
-# schedule above is then off (every GEMM is a join).  VLM_GROUPED_GEMM=0: back to one launch chain per expert.
-_GROUPED = os.environ.get("VLM_GROUPED_GEMM", "1") != "0"
-
-
-def _use_grouped(ranges):
-    return _GROUPED and len(ranges) > 1 and all(wT16(getattr(e, n)) is not None for _, _, e in ranges
-                                                for n in ("qkvw", "projw", "fc1w", "fc2w"))
-
-
-class _ExpertStreams:
-    def __init__(self, ranges):
-        self.side = None
-        self.small = -1
-        if _EXPERTS["enabled"] and len(ranges) > 1 and not _use_grouped(ranges):
-            if _EXPERTS["stream"] is None:
-                _EXPERTS["stream"] = torch.cuda.Stream()
-            self.side = _EXPERTS["stream"]
-            sizes = [r1 - r0 for r0, r1, _ in ranges]
-            self.small = sizes.index(min(sizes))  # the smallest row range (text) goes to the side stream
-
-    def __enter__(self):
-        if self.side is not None:
-            self.side.wait_stream(torch.cuda.current_stream())
-        return self
-
-    def on(self, idx):
-        if self.side is not None and idx == self.small:
-            return torch.cuda.stream(self.side)
-        return _NULL_CTX
-
-    def __exit__(self, *a):
-        if self.side is not None:
-            torch.cuda.current_stream().wait_stream(self.side)
-        return False
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-_NULL_CTX = _NullCtx()
-
-
 def wT16(p):
-    """Transposed bf16 shadow [in, out] of a weight, or None when the model keeps none for it."""
-    return getattr(p, "_vlm_bf16_t", None)
+    """Transposed bf16 shadow [in, out] of a weight (fails loudly if the model keeps none for it)."""
+    s = getattr(p, "_vlm_bf16_t", None)
+    if s is None:
+        raise L.VlmError("weight has no transposed bf16 shadow: call model.setup_engine() on a CUDA model first")
+    return s
 
 
-def _dgrad(dy, w, dx, **epi):
-    """dx = dy . W (+ epilogue): through W^T as a K-contiguous GEMM when the transposed shadow exists."""
-    wt = wT16(w)
-    if wt is not None:
-        return ops.gemm(dy, wt, dx, **epi)
-    return ops.gemm(dy, w16(w), dx, tb=True, **epi)
+# Grouped GEMM (SURVEY K9): with two row ranges (the modality experts of an all_moe block, the ufo layers before fusion) each of
+# the block's GEMMs is ONE launch over both ranges (ops.gemm_grouped): the text expert's 14 row tiles ride in the image expert's
+# rounds of 256x256 tiles instead of under-filling launches of their own (9.6 % of the all_moe step for 6.5 % of its rows).
+def _gemm_rows(a, groups, out, *, act=L.ACT_NONE, aux=None, col_scale=None, row_scale=None, residual=None, col_sum_fold=None):
+    """out[r0:r1] = epilogue(a[r0:r1] @ w^T) over a plan's row ranges, groups (r0, r1, w, bias, col_sum) as in
+    ops.gemm_grouped: one range is an ops.gemm on the row slices, more are one grouped launch."""
+    if len(groups) > 1:
+        return ops.gemm_grouped(a, groups, out, act=act, aux=aux, col_scale=col_scale, row_scale=row_scale,
+                                residual=residual, col_sum_fold=col_sum_fold)
+    (r0, r1, w, bias, col_sum), = groups
+
+    def rows(t):
+        return t[r0:r1] if t is not None else None
+
+    return ops.gemm(a[r0:r1], w, out[r0:r1], bias=bias, act=act, aux=rows(aux), col_scale=col_scale,
+                    row_scale=rows(row_scale), residual=rows(residual), col_sum=col_sum, col_sum_fold=col_sum_fold)
+
+
+def _wgrad_rows(dy, x, groups):
+    """dW (+)= dy[r0:r1]^T x[r0:r1] for every group (r0, r1, dW): ops.gemm for one range, one grouped launch for more."""
+    if len(groups) > 1:
+        return ops.gemm_wgrad_grouped(dy, x, groups)
+    (r0, r1, dw), = groups
+    return ops.gemm(dy[r0:r1], x[r0:r1], dw, ta=True, tb=True, accumulate=True)
 
 
 def w16(p):
@@ -448,7 +410,9 @@ class _TableT(torch.autograd.Function):
         acc = ctx.holder.pop("dbias_t", None)
         ctx.holder.pop("routed", None)
         table = ctx.table
-        placeholder = g.stride() == (0,) * g.dim()  # _BlockFn's expanded zero: carries nothing
+        # _BlockFn's expanded _zero_scalar carries nothing; any other gradient (a broadcast one included) is real
+        z = _ZERO.get(str(g.device))
+        placeholder = z is not None and g.data_ptr() == z.data_ptr()
         if acc is None:
             return (None if placeholder else g.t()), None
         if getattr(table, "_vlm_flat", None) is not None and table.requires_grad and table.grad is not None:
@@ -605,14 +569,7 @@ class GramCapture:
         return {k: v.cpu() for k, v in self.grams.items()}
 
 
-# A/B switch for measurements: 0 = separate colsum launches, 1/2 = q/v bias inside the attention backward and fc1 bias
-# through the GELU-backward GEMM epilogue + fold workspace
-_DEFER_FOLD = os.environ.get("VLM_DEFER_FOLD", "1") != "0"
 _DENSE_BIAS = True  # the attention kernels always read the dense table (round 2: bias enters through the matrix pipe)
-_SAVE_DERIV = os.environ.get("VLM_GELU_SAVE_DERIV", "1") != "0"  # fc1 saves gelu'(h) instead of h for the backward pass
-_FUSE_MODE = int(os.environ.get("VLM_FUSE_BIAS_GRADS", "2"))
-_FUSE_BIAS_GRADS = _FUSE_MODE != 0
-_FUSE_FC1_BIAS = _FUSE_MODE in (1, 2)  # through the fold workspace (mode 0: separate colsum launch)
 
 
 def _segment_bias_grads(ranges, seq):
@@ -652,12 +609,6 @@ def _qkv_bias(e):
     return torch.cat((e.qb.detach(), torch.zeros_like(e.vb), e.vb.detach()))
 
 
-# norm2's backward and the attention branch's LayerScale backward as ONE pass over the rows (K3-style fusion of two row kernels:
-# the second one's 4-B-per-element read of the residual-stream gradient and its launch go; bit-identical).  VLM_FUSE_LN_SCALE=0:
-# two launches.
-_FUSE_LN_SCALE = os.environ.get("VLM_FUSE_LN_SCALE", "1") != "0"
-
-
 # LayerScale folded into attn.proj / mlp.fc2 (csrc/layerscale.hip, FlatParams.enable_layerscale_fold): the residual epilogues of
 # the two forward GEMMs lose their column scale and their bf16 copy of the branch output, the LayerScale backward shrinks to a
 # cast (+ column sums), and dgamma comes from the weight gradient.  VLM_FOLD_LAYERSCALE=0: the round-1..4 form (A/B).
@@ -693,20 +644,17 @@ def _arm_layerscale_finish(flat):
 
 
 def _ln2_bwd_scale1(dln, x1, st2, e, dx1, dx2, y1, g1, rs1, dy1, fold):
-    if y1 is None:  # folded LayerScale: dy1 = bf16(rs1 * dx1) and its column sums (the raw proj-bias gradient)
-        if _FUSE_LN_SCALE and x1.shape[1] <= 768:
-            ops.layernorm_bwd_scale(dln, x1, st2, e.n2w, dx1, dx2, e.n2w.grad, e.n2b.grad, y=None, sgamma=None, row_scale=rs1,
-                                    sdy=dy1, dsgamma=None, dsbias=_rb(e.projb), fold=fold)
-        else:
-            ops.layernorm_bwd(dln, x1, st2, e.n2w, dx1, dres=dx2, dgamma=e.n2w.grad, dbeta=e.n2b.grad, fold=fold)
-            ops.layerscale_bwd(dx1, None, None, rs1, dy1, None, _rb(e.projb), fold=fold)
-        return
-    if _FUSE_LN_SCALE and x1.shape[1] <= 768:  # (wider rows: the fused kernel's four accumulator sets spill)
-        ops.layernorm_bwd_scale(dln, x1, st2, e.n2w, dx1, dx2, e.n2w.grad, e.n2b.grad, y=y1, sgamma=g1, row_scale=rs1, sdy=dy1,
-                                dsgamma=g1.grad, dsbias=e.projb.grad, fold=fold)
+    # norm2's backward and the attention branch's LayerScale backward as ONE pass over the rows (K3-style fusion of two row
+    # kernels: the second one's 4-B-per-element read of the residual-stream gradient and its launch go; bit-identical).
+    # Wider rows run the two kernels: the fused kernel's four accumulator sets spill.
+    # Folded LayerScale (y1 is None): dy1 = bf16(rs1 * dx1) and its column sums (the raw proj-bias gradient).
+    sgamma, dsgamma, dsbias = (None, None, _rb(e.projb)) if y1 is None else (g1, g1.grad, e.projb.grad)
+    if x1.shape[1] <= 768:
+        ops.layernorm_bwd_scale(dln, x1, st2, e.n2w, dx1, dx2, e.n2w.grad, e.n2b.grad, y=y1, sgamma=sgamma, row_scale=rs1,
+                                sdy=dy1, dsgamma=dsgamma, dsbias=dsbias, fold=fold)
     else:
         ops.layernorm_bwd(dln, x1, st2, e.n2w, dx1, dres=dx2, dgamma=e.n2w.grad, dbeta=e.n2b.grad, fold=fold)
-        ops.layerscale_bwd(dx1, y1, g1, rs1, dy1, g1.grad, e.projb.grad, fold=fold)
+        ops.layerscale_bwd(dx1, y1, sgamma, rs1, dy1, dsgamma, dsbias, fold=fold)
 
 
 class _BlockFn(torch.autograd.Function):
@@ -726,17 +674,10 @@ class _BlockFn(torch.autograd.Function):
         qkv = torch.empty(M, 3 * D, device=dev, dtype=BF16)
         rs1 = pc.drop_path_rows(plan.drop_prob, training, dev)
         rs2 = pc.drop_path_rows(plan.drop_prob, training, dev)
-        grouped = _use_grouped(plan.ranges)
-        if grouped:
-            for r0, r1, e in plan.ranges:
-                ops.layernorm_fwd(x[r0:r1], e.n1w, e.n1b, plan.eps, ln1[r0:r1], st1[r0:r1])
-            ops.gemm_grouped(ln1, [(r0, r1, w16(e.qkvw), _qkv_bias(e), None) for r0, r1, e in plan.ranges], qkv)
-        else:
-            with _ExpertStreams(plan.ranges) as es:
-                for idx, (r0, r1, e) in enumerate(plan.ranges):
-                    with es.on(idx):
-                        ops.layernorm_fwd(x[r0:r1], e.n1w, e.n1b, plan.eps, ln1[r0:r1], st1[r0:r1])
-                        ops.gemm(ln1[r0:r1], w16(e.qkvw), qkv[r0:r1], bias=_qkv_bias(e))
+        rg = plan.ranges
+        for r0, r1, e in rg:
+            ops.layernorm_fwd(x[r0:r1], e.n1w, e.n1b, plan.eps, ln1[r0:r1], st1[r0:r1])
+        _gemm_rows(ln1, [(r0, r1, w16(e.qkvw), _qkv_bias(e), None) for r0, r1, e in rg], qkv)
         o = torch.empty(M, D, device=dev, dtype=BF16)
         lse = torch.empty(H, M, device=dev, dtype=F32)
         rp = pc.relpos
@@ -757,31 +698,15 @@ class _BlockFn(torch.autograd.Function):
         cs1, cs2 = (None, None) if folded else (plan.gamma1, plan.gamma2)
         pb = (lambda e: _fb(e.projb)) if folded else (lambda e: e.projb)
         fb2 = (lambda e: _fb(e.fc2b)) if folded else (lambda e: e.fc2b)
-        if grouped:
-            rg = plan.ranges
-            ops.gemm_grouped(o, [(r0, r1, w16(e.projw), pb(e), None) for r0, r1, e in rg], x1, col_scale=cs1,
-                             row_scale=rs1, residual=x, aux=y1)
-            for r0, r1, e in rg:
-                ops.layernorm_fwd(x1[r0:r1], e.n2w, e.n2b, plan.eps, ln2[r0:r1], st2[r0:r1])
-            ops.gemm_grouped(ln2, [(r0, r1, w16(e.fc1w), e.fc1b, None) for r0, r1, e in rg], a,
-                             act=L.ACT_GELU_DERIV if _SAVE_DERIV else L.ACT_GELU, aux=h)
-            ops.gemm_grouped(a, [(r0, r1, w16(e.fc2w), fb2(e), None) for r0, r1, e in rg], x2, col_scale=cs2,
-                             row_scale=rs2, residual=x1, aux=y2)
-        else:
-            with _ExpertStreams(plan.ranges) as es:  # each expert's proj -> LayerNorm -> fc1 -> fc2 chain is independent
-                for idx, (r0, r1, e) in enumerate(plan.ranges):
-                    with es.on(idx):
-                        ops.gemm(o[r0:r1], w16(e.projw), x1[r0:r1], bias=pb(e), col_scale=cs1,
-                                 row_scale=rs1[r0:r1] if rs1 is not None else None, residual=x[r0:r1],
-                                 aux=y1[r0:r1] if y1 is not None else None)
-                        ops.layernorm_fwd(x1[r0:r1], e.n2w, e.n2b, plan.eps, ln2[r0:r1], st2[r0:r1])
-                        # h = gelu'(pre-activation) (VLM_GELU_SAVE_DERIV, default): the forward epilogue has erf and exp in
-                        # hand anyway, and the fc2-dgrad epilogue of the backward pass becomes a multiplication
-                        ops.gemm(ln2[r0:r1], w16(e.fc1w), a[r0:r1], bias=e.fc1b,
-                                 act=L.ACT_GELU_DERIV if _SAVE_DERIV else L.ACT_GELU, aux=h[r0:r1])
-                        ops.gemm(a[r0:r1], w16(e.fc2w), x2[r0:r1], bias=fb2(e), col_scale=cs2,
-                                 row_scale=rs2[r0:r1] if rs2 is not None else None, residual=x1[r0:r1],
-                                 aux=y2[r0:r1] if y2 is not None else None)
+        _gemm_rows(o, [(r0, r1, w16(e.projw), pb(e), None) for r0, r1, e in rg], x1, col_scale=cs1, row_scale=rs1,
+                   residual=x, aux=y1)
+        for r0, r1, e in rg:
+            ops.layernorm_fwd(x1[r0:r1], e.n2w, e.n2b, plan.eps, ln2[r0:r1], st2[r0:r1])
+        # h = gelu'(pre-activation): the forward epilogue has erf and exp in hand anyway, and the fc2-dgrad epilogue of the
+        # backward pass becomes a multiplication
+        _gemm_rows(ln2, [(r0, r1, w16(e.fc1w), e.fc1b, None) for r0, r1, e in rg], a, act=L.ACT_GELU_DERIV, aux=h)
+        _gemm_rows(a, [(r0, r1, w16(e.fc2w), fb2(e), None) for r0, r1, e in rg], x2, col_scale=cs2, row_scale=rs2,
+                   residual=x1, aux=y2)
         if pc.gram is not None:
             # Gram cache: the LayerNorm outputs enter in fp32 (re-computed here, capture runs are not timed), like the
             # fp32 activations the reference's hooks see; the attention output and the GELU output exist only as the bf16
@@ -838,72 +763,39 @@ class _BlockFn(torch.autograd.Function):
         dln = torch.empty(M, D, device=dev, dtype=BF16)
         dx1 = torch.empty(M, D, device=dev, dtype=F32)
         # column partials (dgamma / dbeta / dbias) of the block's four row kernels are folded by ONE launch at the end
-        fold = ops.FoldBatch(dev, D) if _DEFER_FOLD else None
-        grouped = _use_grouped(plan.ranges)
-        if fold is not None and _EXPERTS["enabled"] and len(plan.ranges) > 1 and not grouped:
-            fold.multi_stream = True  # the experts' row kernels run on two streams: fold only after the join
-        # ---- FFN branch, then the attention branch up to the attention core: one independent chain per expert ----
+        fold = ops.FoldBatch(dev, D)
+        # ---- FFN branch, then the attention branch up to the attention core.  Row kernels run per expert row range (their
+        # parameters and gradient targets differ), every GEMM covers all ranges (_gemm_rows / _wgrad_rows) ----
+        rg = plan.ranges
         do = torch.empty(M, D, device=dev, dtype=BF16)
-        fuse_b1 = _FUSE_FC1_BIAS and fold is not None
-        if grouped:
-            # the same chain with every dgrad as ONE grouped launch over the experts' row ranges; row kernels and wgrads
-            # stay per expert (their parameters and gradient targets differ)
-            rg = plan.ranges
-            act_bwd = L.ACT_MUL_AUX if _SAVE_DERIV else L.ACT_GELU_BWD
-            for r0, r1, e in rg:
-                rr = slice(r0, r1)
-                if folded:
-                    ops.layerscale_bwd(dx2[rr], None, None, rs2[rr] if rs2 is not None else None, dy2[rr], None, _rb(e.fc2b), fold=fold)
-                else:
-                    ops.layerscale_bwd(dx2[rr], y2[rr], g2, rs2[rr] if rs2 is not None else None, dy2[rr], g2.grad, e.fc2b.grad,
-                                       fold=fold)
-            ops.gemm_grouped(dy2, [(r0, r1, wT16(e.fc2w), None, e.fc1b.grad if fuse_b1 else None) for r0, r1, e in rg], dh,
-                             act=act_bwd, aux=h, col_sum_fold=fold if fuse_b1 else None)
-            if not fuse_b1:
-                for r0, r1, e in rg:
-                    ops.colsum(dh[r0:r1], e.fc1b.grad)
-            with _Side(dy2, a, dh, ln2):
-                ops.gemm_wgrad_grouped(dy2, a, [(r0, r1, wg(e.fc2w)) for r0, r1, e in rg])
-                ops.gemm_wgrad_grouped(dh, ln2, [(r0, r1, e.fc1w.grad) for r0, r1, e in rg])
-            ops.gemm_grouped(dh, [(r0, r1, wT16(e.fc1w), None, None) for r0, r1, e in rg], dln)
-            for r0, r1, e in rg:
-                rr = slice(r0, r1)
-                _ln2_bwd_scale1(dln[rr], x1[rr], st2[rr], e, dx1[rr], dx2[rr], y1[rr] if y1 is not None else None, g1,
-                                rs1[rr] if rs1 is not None else None, dy1[rr], fold)
-            ops.gemm_grouped(dy1, [(r0, r1, wT16(e.projw), None, None) for r0, r1, e in rg], do)
-            with _Side(dy1, o):
-                ops.gemm_wgrad_grouped(dy1, o, [(r0, r1, wg(e.projw)) for r0, r1, e in rg])
-        with _ExpertStreams(plan.ranges) as es:  # (grouped: nothing left for the per-expert chains -- no side stream either)
-            for idx, (r0, r1, e) in enumerate(plan.ranges if not grouped else ()):
-                rr = slice(r0, r1)
-                with es.on(idx):
-                    if folded:
-                        ops.layerscale_bwd(dx2[rr], None, None, rs2[rr] if rs2 is not None else None, dy2[rr], None, _rb(e.fc2b),
-                                           fold=fold)
-                    else:
-                        ops.layerscale_bwd(dx2[rr], y2[rr], g2, rs2[rr] if rs2 is not None else None, dy2[rr], g2.grad,
-                                           e.fc2b.grad, fold=fold)
-                    # fc1 bias gradient = column sums of dh: per-tile sums from the epilogue that produces dh, folded with
-                    # the block's other column partials (no atomics, no second pass over dh); without a fold batch: colsum
-                    _dgrad(dy2[rr], e.fc2w, dh[rr], act=L.ACT_MUL_AUX if _SAVE_DERIV else L.ACT_GELU_BWD, aux=h[rr],
-                           col_sum=e.fc1b.grad if fuse_b1 else None, col_sum_fold=fold if fuse_b1 else None)
-                    if not fuse_b1:
-                        ops.colsum(dh[rr], e.fc1b.grad)
-                    with _Side(dy2, a, dh, ln2):
-                        ops.gemm(dy2[rr], a[rr], wg(e.fc2w), ta=True, tb=True, accumulate=True)
-                        ops.gemm(dh[rr], ln2[rr], e.fc1w.grad, ta=True, tb=True, accumulate=True)
-                    _dgrad(dh[rr], e.fc1w, dln[rr])
-                    _ln2_bwd_scale1(dln[rr], x1[rr], st2[rr], e, dx1[rr], dx2[rr], y1[rr] if y1 is not None else None, g1,
-                                    rs1[rr] if rs1 is not None else None, dy1[rr], fold)
-                    _dgrad(dy1[rr], e.projw, do[rr])
-                    with _Side(dy1, o):
-                        ops.gemm(dy1[rr], o[rr], wg(e.projw), ta=True, tb=True, accumulate=True)
+        for r0, r1, e in rg:
+            rr = slice(r0, r1)
+            if folded:
+                ops.layerscale_bwd(dx2[rr], None, None, rs2[rr] if rs2 is not None else None, dy2[rr], None, _rb(e.fc2b), fold=fold)
+            else:
+                ops.layerscale_bwd(dx2[rr], y2[rr], g2, rs2[rr] if rs2 is not None else None, dy2[rr], g2.grad, e.fc2b.grad,
+                                   fold=fold)
+        # fc1 bias gradient = column sums of dh: per-tile sums from the epilogue that produces dh, folded with the block's
+        # other column partials (no atomics, no second pass over dh)
+        _gemm_rows(dy2, [(r0, r1, wT16(e.fc2w), None, e.fc1b.grad) for r0, r1, e in rg], dh, act=L.ACT_MUL_AUX, aux=h,
+                   col_sum_fold=fold)
+        with _Side(dy2, a, dh, ln2):
+            _wgrad_rows(dy2, a, [(r0, r1, wg(e.fc2w)) for r0, r1, e in rg])
+            _wgrad_rows(dh, ln2, [(r0, r1, e.fc1w.grad) for r0, r1, e in rg])
+        _gemm_rows(dh, [(r0, r1, wT16(e.fc1w), None, None) for r0, r1, e in rg], dln)
+        for r0, r1, e in rg:
+            rr = slice(r0, r1)
+            _ln2_bwd_scale1(dln[rr], x1[rr], st2[rr], e, dx1[rr], dx2[rr], y1[rr] if y1 is not None else None, g1,
+                            rs1[rr] if rs1 is not None else None, dy1[rr], fold)
+        _gemm_rows(dy1, [(r0, r1, wT16(e.projw), None, None) for r0, r1, e in rg], do)
+        with _Side(dy1, o):
+            _wgrad_rows(dy1, o, [(r0, r1, wg(e.projw)) for r0, r1, e in rg])
         dqkv = torch.empty(M, 3 * D, device=dev, dtype=BF16)
         dln1 = torch.empty(M, D, device=dev, dtype=BF16)
         rp = pc.relpos
         # q_bias / v_bias gradients: column sums of dQ / dV per segment, taken inside the attention backward when every
         # segment lies inside ONE expert's row range (always true for the layouts Block.plan() builds)
-        qb_grads, vb_grads, fused_qv = _segment_bias_grads(plan.ranges, pc.seq) if _FUSE_BIAS_GRADS else (None, None, False)
+        qb_grads, vb_grads, fused_qv = _segment_bias_grads(rg, pc.seq)
         ops.attention_bwd(qkv, o, do, lse, dqkv, pc.seq, H, bias_t=bias_t, head_row0=plan.layer * H,
                           rel_index=rp.index if rp is not None else None,
                           rel_index_t=rp.index_t if rp is not None else None, keep0=pc.keep0, keep1=pc.keep1,
@@ -911,33 +803,18 @@ class _BlockFn(torch.autograd.Function):
                           dq_colsum=qb_grads, dv_colsum=vb_grads,
                           bias_dense=rp.dense_for(pc.seq, plan.mode) if rp is not None else None)
         dx = torch.empty(M, D, device=dev, dtype=F32)
-        if grouped:
-            for r0, r1, e in plan.ranges:
-                rr = slice(r0, r1)
-                if e.qb is not None and not fused_qv:
-                    ops.colsum(dqkv[rr, :D], e.qb.grad)
-                    ops.colsum(dqkv[rr, 2 * D:], e.vb.grad)
-            with _Side(dqkv, ln1):
-                ops.gemm_wgrad_grouped(dqkv, ln1, [(r0, r1, e.qkvw.grad) for r0, r1, e in plan.ranges])
-            ops.gemm_grouped(dqkv, [(r0, r1, wT16(e.qkvw), None, None) for r0, r1, e in plan.ranges], dln1)
-            for r0, r1, e in plan.ranges:
-                rr = slice(r0, r1)
-                ops.layernorm_bwd(dln1[rr], x[rr], st1[rr], e.n1w, dx[rr], dres=dx1[rr], dgamma=e.n1w.grad,
-                                  dbeta=e.n1b.grad, fold=fold)
-        with _ExpertStreams(plan.ranges) as es:
-            for idx, (r0, r1, e) in enumerate(plan.ranges if not grouped else ()):
-                rr = slice(r0, r1)
-                with es.on(idx):
-                    if e.qb is not None and not fused_qv:
-                        ops.colsum(dqkv[rr, :D], e.qb.grad)
-                        ops.colsum(dqkv[rr, 2 * D:], e.vb.grad)
-                    with _Side(dqkv, ln1):
-                        ops.gemm(dqkv[rr], ln1[rr], e.qkvw.grad, ta=True, tb=True, accumulate=True)
-                    _dgrad(dqkv[rr], e.qkvw, dln1[rr])
-                    ops.layernorm_bwd(dln1[rr], x[rr], st1[rr], e.n1w, dx[rr], dres=dx1[rr], dgamma=e.n1w.grad,
-                                      dbeta=e.n1b.grad, fold=fold)
-        if fold is not None:
-            fold.flush()
+        for r0, r1, e in rg:
+            if e.qb is not None and not fused_qv:
+                ops.colsum(dqkv[r0:r1, :D], e.qb.grad)
+                ops.colsum(dqkv[r0:r1, 2 * D:], e.vb.grad)
+        with _Side(dqkv, ln1):
+            _wgrad_rows(dqkv, ln1, [(r0, r1, e.qkvw.grad) for r0, r1, e in rg])
+        _gemm_rows(dqkv, [(r0, r1, wT16(e.qkvw), None, None) for r0, r1, e in rg], dln1)
+        for r0, r1, e in rg:
+            rr = slice(r0, r1)
+            ops.layernorm_bwd(dln1[rr], x[rr], st1[rr], e.n1w, dx[rr], dres=dx1[rr], dgamma=e.n1w.grad, dbeta=e.n1b.grad,
+                              fold=fold)
+        fold.flush()
         if folded:
             flat.ls_pending.add(plan.layer)
         if ctx.hook is not None:

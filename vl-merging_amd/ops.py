@@ -211,7 +211,6 @@ class FoldBatch:
         self.ws = ws
         self.jobs = []
         self.taken = 0  # regions handed out since the last flush (a region whose job turned out empty stays taken)
-        self.multi_stream = False  # set by a caller whose row kernels run on more than one stream between two flushes
 
     def next_region(self):
         return self.next_regions(1)[0]
@@ -220,9 +219,6 @@ class FoldBatch:
         """n consecutive free regions (a fused row kernel parks one job per column-sum pair): all reserved BEFORE the launch,
         because making room (flush) after the first was taken would fold a region the launch has not written yet."""
         if self.taken + n > self.MAX:
-            if self.multi_stream:
-                raise L.VlmError("FoldBatch overflow while its producers run on several streams (a mid-way fold would "
-                                 "read partials of launches the folding stream is not ordered behind)")
             self.flush()
         i = self.taken
         self.taken += n

@@ -231,8 +231,7 @@ class ViLTransformerSS(nn.Module):
             raise L.VlmError("ViLTransformerSS runs on the GPU only: call .cuda() before setup_engine()")
         L.get_lib()
         self._flat = engine.FlatParams(self, order_key=vilt_utils.flat_order_key)
-        if os.environ.get("VLM_TRANSPOSED_SHADOWS", "1") != "0":  # A/B switch for measurements
-            self._flat.enable_transposed(lambda n: n.startswith("transformer.blocks.") and n.endswith(".weight"))
+        self._flat.enable_transposed(lambda n: n.startswith("transformer.blocks.") and n.endswith(".weight"))
         if os.environ.get("VLM_FOLD_LAYERSCALE", "1") != "0":  # A/B switch for measurements
             # gamma_1 / gamma_2 folded into attn.proj / mlp.fc2 of every expert (vision_transformer.py:489-491, :586, :603)
             entries = []

@@ -7,9 +7,8 @@
  *   - every call is stream-ordered on `stream` (a hipStream_t passed as void*), re-entrant, allocates
  *     nothing: the caller owns outputs and workspaces;
  *   - return 0 on success, a negative VLM_ERR_* otherwise; nothing throws across the boundary;
- *   - process-wide state is limited to (1) diagnostic switches read ONCE from the environment at first use (VLM_GEMM_BIG,
- *     VLM_GEMM_BIGT, VLM_GEMM_STAGE, VLM_GEMM_SPLITK, VLM_GEMM_SPLITK_SLOTS, VLM_GEMM_GROUP_M, VLM_GEMM_BIG_GROUP_M,
- *     VLM_GEMM_TAIL_SPLIT, VLM_GEMM_CUS, VLM_ATT_DB_GROUPS, VLM_MERGE_VARIANT: thread-safe function-local statics,
+ *   - process-wide state is limited to (1) diagnostic switches read ONCE from the environment at first use
+ *     (VLM_GEMM_CUS, VLM_ATT_DB_GROUPS, VLM_MERGE_VARIANT: thread-safe function-local statics,
  *     immutable afterwards) and (2) the hooks vlm_gemm_set_big_tile_mode and vlm_set_cu_budget (one atomic int each).  None changes results
  *     beyond the fp32 summation order of a GEMM or of the bias-table gradient.
  *
@@ -169,9 +168,9 @@ typedef struct {
 } vlm_wgrad_group_t;
 int vlm_gemm_wgrad_grouped(int n_groups, const vlm_wgrad_group_t* groups, int M, int N, const void* A, int lda,
                            const void* B, int ldb, int ldc, float* splitk_ws, uint64_t splitk_ws_bytes, void* stream);
-/* Which kernel serves ta = tb = 0 calls: 0 the 128x128 tile always, 1 by shape (default; VLM_GEMM_BIG in the environment),
- * 2 the 256x256 tile whenever the call is legal for it, 3 by shape with the last partial round of tiles handed to the
- * 128x128 kernel as a second launch over the remaining rows, -1 back to the environment.  Tests and benchmarks only. */
+/* Which kernel serves ta = tb = 0 calls: 0 the 128x128 tile always, 1 by shape (default), 2 the 256x256 tile whenever the
+ * call is legal for it, -1 back to the default; mode 0 also keeps wgrad (ta = tb = 1) off the 256x256 kernel.  Tests and
+ * benchmarks only. */
 int vlm_gemm_set_big_tile_mode(int mode);
 
 /* ------------------------------------------------------------------------------------------------

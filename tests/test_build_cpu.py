@@ -50,6 +50,11 @@ def test_big_gemm_accumulators_stay_in_agprs(resources):
         assert r["VGPRs"] <= (248 if residual else 232), (name, r)
 
 
+def test_gemm_kernel_variants(resources):
+    small = [k for k in resources if "vlm_gemm_kernel" in k]
+    assert len(small) == 10, sorted(small)  # 8 (TA, TB, OUT_F32) keys + the two split-K launches; staging follows from them
+
+
 def test_wgrad_kernel_resources(resources):
     both = [(k, v) for k, v in resources.items() if "vlm_gemm_bigT_kernel" in k]
     assert len(both) == 2, sorted(k for k, _ in both)  # plain + GROUPED

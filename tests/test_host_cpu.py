@@ -305,3 +305,20 @@ def test_table_transpose_keeps_broadcast_gradients(pkg):
     rp.holder["dbias_t"].fill_(2.0)
     rp.bias_t.backward(engine._zero_scalar(table.device).expand_as(rp.bias_t))
     assert torch.equal(table.grad, torch.full((7, 6), 2.0))
+
+
+def test_big_tile_mode_range(pkg):
+    """vlm_gemm_set_big_tile_mode takes 0..2 and -1 (back to the default, by shape); the removed tail-split mode 3 is an
+    argument error.  Host state only: no GPU needed."""
+    L = importlib.import_module("vl_merging_amd._lib")
+    if not os.path.exists(L.LIB_PATH):
+        import __graft_entry__ as ge
+        ge.build()
+    lib = L.get_lib()
+    try:
+        for mode in (0, 2, 1, -1):
+            assert lib.vlm_gemm_set_big_tile_mode(mode) == 0, mode
+        for mode in (3, -2):
+            assert lib.vlm_gemm_set_big_tile_mode(mode) == -1, mode  # VLM_ERR_ARG
+    finally:
+        lib.vlm_gemm_set_big_tile_mode(-1)

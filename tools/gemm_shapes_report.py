@@ -12,6 +12,6 @@ for r in rows:
     agg[k][0] += 1
     agg[k][1] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
 tot = sum(v[1] for v in agg.values())
-print("flags = TA,TB,OUT_F32,DMA_A,DMA_B,SPLITK ; total %.2f ms/step" % (tot / steps / 1e3))
+print("flags = TA,TB,OUT_F32,SPLITK ; total %.2f ms/step" % (tot / steps / 1e3))
 for k, v in sorted(agg.items(), key=lambda kv: -kv[1][1])[:24]:
     print("%-14s wgs %6d  n/step %5.1f  avg %7.1f us  %6.2f ms/step" % (k[0], k[1], v[0] / steps, v[1] / v[0], v[1] / steps / 1e3))

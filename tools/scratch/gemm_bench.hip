@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
   if (variant == 5) { e.act = VLM_ACT_MUL_AUX; e.aux = aux; e.ld_aux = N; e.col_sum = vec + N; e.col_sum_ws = ws; }  // fc2 dgrad with the saved GELU' factor
   if (variant == 3) { e.bias = vec; e.col_scale = vec + 2 * N; e.row_scale = vec + 4 * N; e.residual = (float*)nullptr; e.aux = aux; e.ld_aux = N; }
   if (variant == 3) { e.residual = (const float*)C; e.ld_res = N; }
-  setenv("VLM_GEMM_BIG", "2", 1);
+  vlm_gemm_set_big_tile_mode(2);
   auto run = [&]() {
     int rc = vlm_gemm_bf16(0, 0, M, N, K, A, K, B, K, C, N, f32, &e, 0);
     if (rc) { printf("launch failed rc=%d\n", rc); exit(1); }

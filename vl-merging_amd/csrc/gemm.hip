@@ -11,8 +11,9 @@
 //   wgrad     dW = dy^T x       : ta=1 tb=1   (reduction over tokens; fp32 out, accumulate)
 //
 // Tiling (gfx950): 128x128x64 block tile, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 MFMA tiles.
-// Operands are staged global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds; the descriptor's bounds check zero-fills
-// ragged M/N/K tails), double-buffered in LDS (2 x 32 KiB), next tile's DMA in flight during the current tile's MFMAs.  K-contiguous operands live in LDS as [128][64] with a 16-B-chunk XOR swizzle
+// K-contiguous operands are staged global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds), K-strided ones and those of
+// split-K launches through registers; the descriptor's bounds check zero-fills ragged M/N/K tails.  Double-buffered in
+// LDS (2 x 32 KiB), next tile's loads in flight during the current tile's MFMAs.  K-contiguous operands live in LDS as [128][64] with a 16-B-chunk XOR swizzle
 // (chunk ^= row & 7) and are read with ds_read_b128; K-strided operands live as [64][128] with a 32-B-chunk XOR
 // swizzle and are read transposed with ds_read_b64_tr_b16, so no operand is ever transposed in memory.
 // The MFMA is issued "swapped" (A-operand = weight rows, B-operand = activation rows) so that each lane ends
@@ -20,7 +21,6 @@
 #include "vlm_common.h"
 #include "vlm_diag.h"
 #include <atomic>
-#include <stdlib.h>
 
 #define GEMM_BM 128
 #define GEMM_BN 128
@@ -69,7 +69,7 @@ __device__ __forceinline__ float act_bwd_factor(int act, float saved) {
   return act == VLM_ACT_MUL_AUX ? saved : gelu_erf_grad(saved);
 }
 
-// ---- global -> register -> LDS staging (kept for K-strided operands, where it measured faster than LDS-DMA) ------
+// ---- global -> register -> LDS staging (K-strided operands, where it measured faster than LDS-DMA; split-K) -------
 template <bool KSTRIDED>
 __device__ __forceinline__ void stage_load(u32x4 (&r)[4], __amdgpu_buffer_rsrc_t rsrc, uint32_t row0, uint32_t k0,
                                            uint32_t ld, int tid) {
@@ -109,28 +109,17 @@ __device__ __forceinline__ void stage_store(const u32x4 (&r)[4], unsigned char* 
 // ---- global -> LDS staging by LDS-DMA (buffer_load_dwordx4 ... lds) ------------------------------------------------
 // ds_write_b128 moves only ~79 B/clk/CU (MI355X_MICROARCH.md, LDS table): register staging made the LDS pipe, not the
 // MFMAs, the bound (measured 311 TFLOP/s).  One wave instruction writes 1 KiB of LDS linearly (wave-uniform base +
-// lane*16 B) from a PER-LANE source address, so the XOR swizzles live on the source side (guide rule 21):
-//   K-contiguous tile [128 rows][64 k]: instruction j covers rows 8j..8j+7; lane -> row 8j + (lane>>3), LDS slot
-//     (lane&7) holds global chunk (lane&7) ^ (row&7)
-//   K-strided tile [64 k][128 x]: instruction j covers k-rows 4j..4j+3; lane -> krow 4j + (lane>>4), LDS 16-B slot
-//     (lane&15) holds global 32-B chunk ((lane&15)>>1) ^ (krow&3) ^ (((krow>>3)&1)<<2), same half
-// The buffer descriptor's bounds check zero-fills ragged M/N/K tails in flight.
+// lane*16 B) from a PER-LANE source address, so the XOR swizzles live on the source side (guide rule 21).  K-contiguous
+// tile [128 rows][64 k]: instruction j covers rows 8j..8j+7; lane -> row 8j + (lane>>3), LDS slot (lane&7) holds global
+// chunk (lane&7) ^ (row&7).  The buffer descriptor's bounds check zero-fills ragged M/N/K tails in flight.
 typedef __attribute__((address_space(3))) void lds_void;
-template <bool KSTRIDED>
 __device__ __forceinline__ void stage_dma(__amdgpu_buffer_rsrc_t rsrc, unsigned char* tile, uint32_t row0, uint32_t k0,
                                           uint32_t ld, int wave, int lane) {
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int j = wave + 4 * u;  // wave-uniform
-    uint32_t off;
-    if (!KSTRIDED) {
-      const uint32_t row = j * 8 + (lane >> 3), chunk = (lane & 7) ^ (row & 7);
-      off = ((row0 + row) * ld + k0 + chunk * 8) * 2;
-    } else {
-      const uint32_t krow = j * 4 + (lane >> 4), s16 = lane & 15;
-      const uint32_t c32 = (s16 >> 1) ^ (krow & 3) ^ (((krow >> 3) & 1) << 2);
-      off = ((k0 + krow) * ld + row0 + (c32 * 2 + (s16 & 1)) * 8) * 2;
-    }
+    const uint32_t row = j * 8 + (lane >> 3), chunk = (lane & 7) ^ (row & 7);
+    const uint32_t off = ((row0 + row) * ld + k0 + chunk * 8) * 2;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(tile + j * 1024), 16, off, 0, 0, 0);
   }
 }
@@ -470,12 +459,14 @@ __device__ __forceinline__ int gemm_epilogue(const gemm_params_t& p, const f32x4
   return -1;
 }
 
-// DMA_A / DMA_B: stage that operand by LDS-DMA (else through registers).  SPLITK: K is cut over gridDim.x / tiles
-// slices, the MFMA is issued un-swapped so that 16 consecutive lanes hold 16 consecutive output columns, and the
-// epilogue is a plain fp32 atomicAdd (C += alpha*acc): wgrad reduces over ~13.5k tokens into only 36-144 output
-// tiles, a single-pass grid leaves most of the 256 CUs idle and every resident workgroup latency-bound.
-template <bool TA, bool TB, bool OUT_F32, bool DMA_A, bool DMA_B, bool SPLITK>
+// SPLITK: K is cut over gridDim.x / tiles slices, the MFMA is issued un-swapped so that 16 consecutive lanes hold 16
+// consecutive output columns, and the epilogue is a plain fp32 atomicAdd (C += alpha*acc): wgrad reduces over ~13.5k
+// tokens into only 36-144 output tiles, a single-pass grid leaves most of the 256 CUs idle and every resident workgroup
+// latency-bound.
+template <bool TA, bool TB, bool OUT_F32, bool SPLITK>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void vlm_gemm_kernel(const gemm_params_t p) {
+  // staging: LDS-DMA for a K-contiguous operand outside split-K, registers otherwise
+  constexpr bool DMA_A = !TA && !SPLITK, DMA_B = !TB && !SPLITK;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -531,9 +522,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void vlm_gemm_kernel(const gemm_pa
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   u32x4 sa[4], sb[4];
   if (kt0 < kt1) {
-    if (DMA_A) stage_dma<TA>(ra, LDS_A(0), m0, kt0 * GEMM_BK, p.lda, wave_u, lane);
+    if (DMA_A) stage_dma(ra, LDS_A(0), m0, kt0 * GEMM_BK, p.lda, wave_u, lane);
     else { stage_load<TA>(sa, ra, m0, kt0 * GEMM_BK, p.lda, tid); stage_store<TA>(sa, LDS_A(0), tid); }
-    if (DMA_B) stage_dma<TB>(rb, LDS_B(0), n0, kt0 * GEMM_BK, p.ldb, wave_u, lane);
+    if (DMA_B) stage_dma(rb, LDS_B(0), n0, kt0 * GEMM_BK, p.ldb, wave_u, lane);
     else { stage_load<TB>(sb, rb, n0, kt0 * GEMM_BK, p.ldb, tid); stage_store<TB>(sb, LDS_B(0), tid); }
   }
   __syncthreads();  // hipcc drains a pending LDS-DMA (vmcnt(0)) in front of the barrier
@@ -542,9 +533,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void vlm_gemm_kernel(const gemm_pa
   for (int kt = kt0; kt < kt1; ++kt) {
     const int cur = (kt - kt0) & 1;
     if (kt + 1 < kt1) {  // next tile's loads fly during this tile's MFMAs
-      if (DMA_A) stage_dma<TA>(ra, LDS_A(cur ^ 1), m0, (kt + 1) * GEMM_BK, p.lda, wave_u, lane);
+      if (DMA_A) stage_dma(ra, LDS_A(cur ^ 1), m0, (kt + 1) * GEMM_BK, p.lda, wave_u, lane);
       else stage_load<TA>(sa, ra, m0, (kt + 1) * GEMM_BK, p.lda, tid);
-      if (DMA_B) stage_dma<TB>(rb, LDS_B(cur ^ 1), n0, (kt + 1) * GEMM_BK, p.ldb, wave_u, lane);
+      if (DMA_B) stage_dma(rb, LDS_B(cur ^ 1), n0, (kt + 1) * GEMM_BK, p.ldb, wave_u, lane);
       else stage_load<TB>(sb, rb, n0, (kt + 1) * GEMM_BK, p.ldb, tid);
     }
     const unsigned char* la = LDS_A(cur);
@@ -616,18 +607,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void vlm_gemm_kernel(const gemm_pa
   GEMM_STAMP_END()
 }
 
-template <bool TA, bool TB, bool OUT_F32, bool DMA_A, bool DMA_B, bool SPLITK>
+template <bool TA, bool TB, bool OUT_F32, bool SPLITK>
 static int launch_gemm(const gemm_params_t& p, hipStream_t stream) {
   const size_t smem = 4 * GEMM_TILE_BYTES;
   static bool attr_set = false;  // per instantiation
   if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&vlm_gemm_kernel<TA, TB, OUT_F32, DMA_A, DMA_B, SPLITK>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&vlm_gemm_kernel<TA, TB, OUT_F32, SPLITK>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
       return VLM_ERR_LAUNCH;
     attr_set = true;
   }
   dim3 grid(p.tiles_m * p.tiles_n * (SPLITK ? p.splits : 1)), block(GEMM_THREADS);
-  hipLaunchKernelGGL((vlm_gemm_kernel<TA, TB, OUT_F32, DMA_A, DMA_B, SPLITK>), grid, block, smem, stream, p);
+  hipLaunchKernelGGL((vlm_gemm_kernel<TA, TB, OUT_F32, SPLITK>), grid, block, smem, stream, p);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }
@@ -1297,6 +1288,26 @@ __global__ __launch_bounds__(256) void splitk_reduce_grouped_kernel(const float*
   *reinterpret_cast<f32x4*>(C + m * ldc + n) = t;
 }
 
+// CUs the grids plan for (vlm_device_cus), 256 when unknown
+static int plan_cus() {
+  const int cus = vlm_device_cus();
+  return cus > 0 ? cus : 256;
+}
+
+// Host-side, workgroup-uniform copy of the epilogue's 8-column fast-path test (gemm_epilogue: vec8_ok): 16-B epilogue vectors
+static bool epi_vec8(const vlm_epilogue_t* e, int ldc, int c_is_f32) {
+  const bool v4 = ((ldc & 3) == 0) && (!e->aux || (e->ld_aux & 3) == 0) && (!e->residual || (e->ld_res & 3) == 0);
+  return v4 && (c_is_f32 || (ldc & 7) == 0) && (!e->aux || ((e->ld_aux & 7) == 0 && ((uintptr_t)e->aux & 15) == 0)) &&
+         (!e->residual || ((uintptr_t)e->residual & 15) == 0) && (!e->bias || ((uintptr_t)e->bias & 15) == 0) &&
+         (!e->col_scale || ((uintptr_t)e->col_scale & 15) == 0);
+}
+
+// The 256x256 kernel's buffer descriptors take 32-bit byte offsets into M rows of A, C and the epilogue's row inputs
+static bool epi_off32(const vlm_epilogue_t* e, int M, int lda, int ldc) {
+  return (uint64_t)M * ldc * 4 < (1ull << 31) && (!e->residual || (uint64_t)M * e->ld_res * 4 < (1ull << 31)) &&
+         (!e->aux || (uint64_t)M * e->ld_aux * 2 < (1ull << 31)) && (uint64_t)M * lda * 2 < (1ull << 31);
+}
+
 // wgrad through the 256x256 kernel: 1 = not offered (no / too small workspace, shape), else the launch's return code
 static int launch_gemm_bigT(gemm_params_t p, const vlm_epilogue_t* epi, hipStream_t stream) {
   // whole 256-column tiles only: the looped epilogue has no column bound (a 128-column tail's second wave would store into
@@ -1306,9 +1317,7 @@ static int launch_gemm_bigT(gemm_params_t p, const vlm_epilogue_t* epi, hipStrea
   p.tiles_m = (p.M + BIG_BM - 1) / BIG_BM;
   p.tiles_n = (p.N + BIG_BN - 1) / BIG_BN;
   const int ntile = p.tiles_m * p.tiles_n, nk = (p.K + BIG_BK - 1) / BIG_BK;
-  int cus = vlm_device_cus();
-  if (cus <= 0) cus = 256;
-  int splits = cus / ntile;  // one round of workgroups, never a little more
+  int splits = plan_cus() / ntile;  // one round of workgroups, never a little more
   if (splits < 1) splits = 1;
   if (splits > nk / 16) splits = nk / 16;  // >= 16 steps per slice
   if (splits < 1) return 1;
@@ -1335,13 +1344,7 @@ template <bool OUT_F32, bool RES, int AUX, bool GROUPED = false>
 static int launch_gemm_big(gemm_params_t p, hipStream_t stream) {
   if (!GROUPED) p.tiles_m = (p.M + BIG_BM - 1) / BIG_BM;  // GROUPED: the caller counted every group's own tiles
   p.tiles_n = (p.N + BIG_BN - 1) / BIG_BN;
-  static const int group_m = [] {
-    const char* e = getenv("VLM_GEMM_BIG_GROUP_M");
-    int v = e ? atoi(e) : 0;
-    if (v < 0) v = 0;
-    return v;
-  }();
-  p.group_m = group_m ? group_m : (p.tiles_n >= 6 ? 4 : 1);
+  p.group_m = p.tiles_n >= 6 ? 4 : 1;
   GEMM_STAMP_ARM(p)
   hipLaunchKernelGGL((vlm_gemm_big_kernel<OUT_F32, RES, AUX, GROUPED>), dim3(p.tiles_m * p.tiles_n), dim3(GEMM_THREADS), 0, stream, p);
   VLM_CHECK_LAUNCH();
@@ -1377,22 +1380,13 @@ static int launch_gemm_big_variant(const gemm_params_t& p, bool c_is_f32, hipStr
   return 1;
 }
 
-// VLM_GEMM_BIG: 0 = never, 1 = by shape (default), 2 = whenever the kernel is legal (tests), 3 = by shape with the tail split; vlm_gemm_set_big_tile_mode
-// overrides the environment (tests compare the two kernels in one process), -1 returns to it
-static std::atomic<int> g_big_mode{-1};  // -1: follow the environment
-static int gemm_big_mode() {
-  const int m = g_big_mode.load(std::memory_order_relaxed);
-  if (m >= 0) return m;
-  static const int env_mode = [] {
-    const char* e = getenv("VLM_GEMM_BIG");
-    int v = e ? atoi(e) : 1;
-    return v;
-  }();
-  return env_mode;
-}
+// 256x256 kernels: 0 = never, 1 = by shape (default), 2 = whenever the kernel is legal; vlm_gemm_set_big_tile_mode sets it
+// (tests compare the two kernels in one process), -1 returns to the default
+static std::atomic<int> g_big_mode{1};
+static int gemm_big_mode() { return g_big_mode.load(std::memory_order_relaxed); }
 extern "C" int vlm_gemm_set_big_tile_mode(int mode) {
-  if (mode < -1 || mode > 3) return VLM_ERR_ARG;
-  g_big_mode.store(mode, std::memory_order_relaxed);
+  if (mode < -1 || mode > 2) return VLM_ERR_ARG;
+  g_big_mode.store(mode < 0 ? 1 : mode, std::memory_order_relaxed);
   return VLM_OK;
 }
 
@@ -1413,45 +1407,9 @@ extern "C" int vlm_gemm_set_big_tile_mode(int mode) {
 // With staging switched off (tools/stamp_gemm.py, variant _noload) this kernel's loop runs at the MFMA bound (993 of
 // 1024 cycles per K step); with staging and no MFMAs it takes as long as the full loop: what remains is the vector-memory
 // issue path (8 LDS-DMA instructions per wave and K step) overlapped only by the partner workgroup's MFMAs.
-// staging policy: K-contiguous operands by LDS-DMA, K-strided operands through registers (VLM_GEMM_STAGE: 0 = all
-// registers, 1 = all DMA, 2 = hybrid [default]); VLM_GEMM_SPLITK=0 disables split-K
-static int gemm_stage_mode() {
-  static const int mode = [] {
-    const char* e = getenv("VLM_GEMM_STAGE");
-    int v = e ? atoi(e) : 2;
-    return v;
-  }();
-  return mode;
-}
-static int gemm_splitk_enabled() {
-  static const int on = [] {
-    const char* e = getenv("VLM_GEMM_SPLITK");
-    int v = e ? atoi(e) : 1;
-    return v;
-  }();
-  return on;
-}
-
-template <bool TA, bool TB, bool OUT_F32>
-static int dispatch_stage(const gemm_params_t& p, hipStream_t s) {
-  const int mode = gemm_stage_mode();
-  const bool da = mode == 1 || (mode == 2 && !TA), db = mode == 1 || (mode == 2 && !TB);
-  if (da && db) return launch_gemm<TA, TB, OUT_F32, true, true, false>(p, s);
-  if (da) return launch_gemm<TA, TB, OUT_F32, true, false, false>(p, s);
-  if (db) return launch_gemm<TA, TB, OUT_F32, false, true, false>(p, s);
-  return launch_gemm<TA, TB, OUT_F32, false, false, false>(p, s);
-}
-
-static int gemm_dispatch(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                         int c_is_f32, const vlm_epilogue_t* epi, void* stream, bool allow_big);
 
 extern "C" int vlm_gemm_bf16(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
                              void* C, int ldc, int c_is_f32, const vlm_epilogue_t* epi, void* stream) {
-  return gemm_dispatch(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, c_is_f32, epi, stream, true);
-}
-
-static int gemm_dispatch(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                         int c_is_f32, const vlm_epilogue_t* epi, void* stream, bool allow_big) {
   if (M < 0 || N < 0 || K < 0 || !C) return VLM_ERR_ARG;
   if (M == 0 || N == 0) return VLM_OK;
   if (!A || !B || !epi) return VLM_ERR_ARG;
@@ -1471,114 +1429,53 @@ static int gemm_dispatch(int ta, int tb, int M, int N, int K, const void* A, int
   p.M = M; p.N = N; p.K = K;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.epi = *epi;
-  {  // workgroup-uniform copy of the epilogue's 8-column fast-path test (gemm_epilogue: vec8_ok), for the LDS column sums
-    const bool v4 = ((ldc & 3) == 0) && (!epi->aux || (epi->ld_aux & 3) == 0) && (!epi->residual || (epi->ld_res & 3) == 0);
-    const bool v8 = v4 && (c_is_f32 || (ldc & 7) == 0) && (!epi->aux || ((epi->ld_aux & 7) == 0 && ((uintptr_t)epi->aux & 15) == 0)) &&
-                    (!epi->residual || ((uintptr_t)epi->residual & 15) == 0) && (!epi->bias || ((uintptr_t)epi->bias & 15) == 0) &&
-                    (!epi->col_scale || ((uintptr_t)epi->col_scale & 15) == 0);
-    p.epi.reserved = v8 ? 1 : 0;
-    if (epi->col_sum_ws && !v8) return VLM_ERR_ARG;  // workspace mode exists only on the 16-B epilogue path
-  }
+  p.epi.reserved = epi_vec8(epi, ldc, c_is_f32) ? 1 : 0;  // for the LDS column sums
+  if (epi->col_sum_ws && !p.epi.reserved) return VLM_ERR_ARG;  // workspace mode exists only on the 16-B epilogue path
   p.tiles_m = (M + GEMM_BM - 1) / GEMM_BM;
   p.tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
   p.splits = 1;
   p.ksteps_per_split = 0;
   p.n_groups = 0;
-  // 0 = by shape.  Fabric-side fetch per launch at M = 54 296 (rocprofv3 FETCH_SIZE x 2, tools/pmc_gemm.py), group height
+  // Raster group height.  Fabric-side fetch per launch at M = 54 296 (rocprofv3 FETCH_SIZE x 2, tools/pmc_gemm.py), group height
   // 1 / 4 / 8 / 16 / 32:  qkv fwd (operands 87 MB) 523 / 485 / 346 / 526 / 906 MB;  fc1 fwd 879 / 623 / 431 / 663 / 1277;
   // fc2 dgrad 1462 / 626 / 460 / 676 / 1143;  fc2 fwd (N = 768, K = 3072, operands 338 MB) 534 / 620 / 851 / 1023 / 1323.
   // Times differ by < 3 %, so the choice follows the traffic: 8 for wide outputs, row-major for N = 768.
-  static const int group_m = [] {
-    const char* e = getenv("VLM_GEMM_GROUP_M");
-    int v = e ? atoi(e) : 0;
-    if (v < 0) v = 0;
-    return v;
-  }();
-  p.group_m = group_m ? group_m : (p.tiles_n >= 12 ? 8 : 1);
+  p.group_m = p.tiles_n >= 12 ? 8 : 1;
   GEMM_STAMP_ARM(p)
   hipStream_t s = (hipStream_t)stream;
   // split-K: pure accumulation into fp32 (wgrad), few output tiles, long reduction
   const int ntile = p.tiles_m * p.tiles_n, nk = (K + GEMM_BK - 1) / GEMM_BK;
   const bool plain_acc = epi->accumulate && c_is_f32 && !epi->bias && !epi->col_scale && !epi->row_scale &&
                          !epi->residual && !epi->aux && !epi->col_sum && epi->act == VLM_ACT_NONE;
-  // VLM_GEMM_BIGT=0: wgrad stays on the 128x128 atomic split-K kernel (A/B runs)
-  static const int bigt = [] {
-    const char* e = getenv("VLM_GEMM_BIGT");
-    int v = e ? atoi(e) : 1;
-    return v;
-  }();
-  if (bigt && gemm_big_mode() > 0 && ta && tb && c_is_f32 && !epi->bias && !epi->col_scale && !epi->row_scale && !epi->residual &&
+  if (gemm_big_mode() > 0 && ta && tb && c_is_f32 && !epi->bias && !epi->col_scale && !epi->row_scale && !epi->residual &&
       !epi->aux && !epi->col_sum && epi->act == VLM_ACT_NONE && K >= 2048) {
     const int rc = launch_gemm_bigT(p, epi, s);
     if (rc <= 0) return rc;
   }
   // (ta = 0: a dgrad whose reduction is long and whose output is small -- the MLM decoder's, [880 x 30 522] . [30 522 x 768]: 42
   // tiles on 256 CUs took 475 us)
-  if (gemm_splitk_enabled() && tb && plain_acc && ntile < 512 && nk >= 32) {
-    int cus = vlm_device_cus();
-    if (cus <= 0) cus = 256;
+  if (tb && plain_acc && ntile < 512 && nk >= 32) {
     // Slices so that the launch is ONE round of the 2 x CUs resident workgroups, never a little more: measured at
     // K = 13 574 / 54 296 (tools/bench_gemm.py): 432 workgroups 97 / 332 us, 576 (1.125 rounds) 118 / 402 us, 864 113 / 337 us
     // -- fewer slices also mean fewer fp32 atomics (25 us of a 113-us launch at K = 13 574).
-    static const int slots_override = [] {
-    const char* e = getenv("VLM_GEMM_SPLITK_SLOTS");
-    int v = e ? atoi(e) : 0;
-    return v;
-  }();
-    const int slots = slots_override > 0 ? slots_override : 2 * cus;
-    int splits = slots / ntile;
+    int splits = 2 * plan_cus() / ntile;
     if (splits < 1) splits = 1;
     if (splits > nk / 8) splits = nk / 8;                // keep >= 8 K-steps per slice
     if (splits > 1) {
       p.ksteps_per_split = (nk + splits - 1) / splits;
       p.splits = (nk + p.ksteps_per_split - 1) / p.ksteps_per_split;
-      if (!group_m) p.group_m = p.tiles_n >= 12 ? 1 : 4;  // split-K (timed): co-resident blocks already share tiles across K slices
-      if (ta) return launch_gemm<true, true, true, false, false, true>(p, s);
-      return launch_gemm<false, true, true, false, false, true>(p, s);
+      p.group_m = p.tiles_n >= 12 ? 1 : 4;  // split-K (timed): co-resident blocks already share tiles across K slices
+      if (ta) return launch_gemm<true, true, true, true>(p, s);
+      return launch_gemm<false, true, true, true>(p, s);
     }
   }
-  if (allow_big && !ta && !tb && (K % (4 * BIG_BK)) == 0 && gemm_big_mode() > 0) {
+  if (!ta && !tb && (K % (4 * BIG_BK)) == 0 && gemm_big_mode() > 0) {
     const long big_tiles = (long)((M + BIG_BM - 1) / BIG_BM) * ((N + BIG_BN - 1) / BIG_BN);
-    int cus = vlm_device_cus();
-    if (cus <= 0) cus = 256;
-    // the kernel has only the looped epilogue without a column bound: whole 256-column tiles in N, 16-B epilogue vectors
-    const bool off32 = (uint64_t)M * ldc * 4 < (1ull << 31) && (!epi->residual || (uint64_t)M * epi->ld_res * 4 < (1ull << 31)) &&
-                       (!epi->aux || (uint64_t)M * epi->ld_aux * 2 < (1ull << 31));  // the epilogue's buffer descriptors
-    const bool ws_ok = (N % BIG_BN) == 0 && p.epi.reserved == 1 && off32 && !epi->accumulate;  // no column bound in the epilogue
+    // the kernel has only the looped epilogue without a column bound: whole 256-column tiles in N, 16-B epilogue vectors,
+    // 32-bit descriptor offsets
+    const bool ws_ok = (N % BIG_BN) == 0 && p.epi.reserved == 1 && epi_off32(epi, M, lda, ldc) && !epi->accumulate;
     // measured (tools/bench_gemm.py, M = 13 574 and 54 296): ahead of the 128x128 kernel from half a round of tiles up
-    if (ws_ok && (gemm_big_mode() >= 2 || 2 * big_tiles >= cus)) {
-      // Tail split (OFF by default; VLM_GEMM_TAIL_SPLIT=1 or big-tile mode 3): one workgroup per CU means whole ROUNDS of
-      // `cus` tiles; 639 tiles (M = 54 296, N = 768) are 2.5 rounds and the last half round idles half the chip for a full
-      // tile time.  With the split the whole rounds run on this kernel and the remaining ROWS go to the 128x128 kernel (two
-      // workgroups per CU, shorter tiles: 10 776 rows x 768 = 510 tiles = one round of it).  Standalone, plain bf16 outputs:
-      // proj forward 82.7 -> 76.3 us, fc2 forward 269.5 -> 245.6 us (-8 / -9 %).  In the training step, where these calls
-      // carry the fp32 residual-stream epilogue, the 128x128 part costs 41 us per call: kernel time -0.4 %, step rate
-      // -0.4 % (522 more launches per 6 steps) in two A/B pairs on one box -- not adopted.
-      static const int tail_split_env = [] {
-        const char* e = getenv("VLM_GEMM_TAIL_SPLIT");
-        return e ? atoi(e) : 0;
-      }();
-      const bool plain_out = !epi->residual && !c_is_f32;  // VLM_GEMM_TAIL_SPLIT=2: only calls without the fp32 residual epilogue
-      const bool tail_split = ((tail_split_env == 1 || (tail_split_env == 2 && plain_out)) && gemm_big_mode() == 1) || gemm_big_mode() == 3;
-      const long full = big_tiles / cus, rem = big_tiles - full * cus, tn = (N + BIG_BN - 1) / BIG_BN;
-      const long rows_big = (full * cus / tn) * BIG_BM;
-      if (tail_split && full >= 1 && rem > 0 && rem * 10 <= (long)cus * 6 && !epi->col_sum &&
-          rows_big > 0 && rows_big < M) {
-        gemm_params_t p1 = p;
-        p1.M = (int)rows_big;
-        const int rc = launch_gemm_big_variant<>(p1, c_is_f32 != 0, s);
-        if (rc <= 0) {
-          if (rc < 0) return rc;
-          vlm_epilogue_t e2 = *epi;
-          const size_t r0 = (size_t)rows_big;
-          if (e2.residual) e2.residual += r0 * e2.ld_res;
-          if (e2.aux) e2.aux = reinterpret_cast<unsigned char*>(e2.aux) + r0 * e2.ld_aux * 2;
-          if (e2.row_scale) e2.row_scale += r0;
-          return gemm_dispatch(0, 0, M - (int)rows_big, N, K, reinterpret_cast<const unsigned char*>(A) + r0 * lda * 2, lda, B, ldb,
-                               reinterpret_cast<unsigned char*>(C) + r0 * ldc * (c_is_f32 ? 4 : 2), ldc, c_is_f32, &e2, stream,
-                               /*allow_big=*/false);
-        }
-      }
+    if (ws_ok && (gemm_big_mode() >= 2 || 2 * big_tiles >= plan_cus())) {
       const int rc = launch_gemm_big_variant<>(p, c_is_f32 != 0, s);
       if (rc <= 0) return rc;
     }
@@ -1588,14 +1485,14 @@ static int gemm_dispatch(int ta, int tb, int M, int N, int K, const void* A, int
 #endif
   const int key = (ta ? 4 : 0) | (tb ? 2 : 0) | (c_is_f32 ? 1 : 0);
   switch (key) {
-    case 0: return dispatch_stage<false, false, false>(p, s);
-    case 1: return dispatch_stage<false, false, true>(p, s);
-    case 2: return dispatch_stage<false, true, false>(p, s);
-    case 3: return dispatch_stage<false, true, true>(p, s);
-    case 4: return dispatch_stage<true, false, false>(p, s);
-    case 5: return dispatch_stage<true, false, true>(p, s);
-    case 6: return dispatch_stage<true, true, false>(p, s);
-    default: return dispatch_stage<true, true, true>(p, s);
+    case 0: return launch_gemm<false, false, false, false>(p, s);
+    case 1: return launch_gemm<false, false, true, false>(p, s);
+    case 2: return launch_gemm<false, true, false, false>(p, s);
+    case 3: return launch_gemm<false, true, true, false>(p, s);
+    case 4: return launch_gemm<true, false, false, false>(p, s);
+    case 5: return launch_gemm<true, false, true, false>(p, s);
+    case 6: return launch_gemm<true, true, false, false>(p, s);
+    default: return launch_gemm<true, true, true, false>(p, s);
   }
 }
 
@@ -1616,16 +1513,9 @@ extern "C" int vlm_gemm_bf16_grouped(int n_groups, const vlm_gemm_group_t* group
   if (M_total == 0 || N == 0) return VLM_OK;
   if (!A) return VLM_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
+  // the looped epilogue's 16-B vectors and 32-bit descriptor offsets, as in vlm_gemm_bf16
   bool big = gemm_big_mode() > 0 && (K % (4 * BIG_BK)) == 0 && (N % BIG_BN) == 0 && !epi->accumulate && (lda & 7) == 0 &&
-             ((uintptr_t)A & 15) == 0 && ((uintptr_t)C & 15) == 0;
-  {  // the looped epilogue's 16-B vectors and 32-bit descriptor offsets (gemm_dispatch: v8, off32)
-    const bool v4 = ((ldc & 3) == 0) && (!epi->aux || (epi->ld_aux & 3) == 0) && (!epi->residual || (epi->ld_res & 3) == 0);
-    const bool v8 = v4 && (c_is_f32 || (ldc & 7) == 0) && (!epi->aux || ((epi->ld_aux & 7) == 0 && ((uintptr_t)epi->aux & 15) == 0)) &&
-                    (!epi->residual || ((uintptr_t)epi->residual & 15) == 0) && (!epi->col_scale || ((uintptr_t)epi->col_scale & 15) == 0);
-    const bool off32 = (uint64_t)M_total * ldc * 4 < (1ull << 31) && (!epi->residual || (uint64_t)M_total * epi->ld_res * 4 < (1ull << 31)) &&
-                       (!epi->aux || (uint64_t)M_total * epi->ld_aux * 2 < (1ull << 31)) && (uint64_t)M_total * lda * 2 < (1ull << 31);
-    big = big && v8 && off32;
-  }
+             ((uintptr_t)A & 15) == 0 && ((uintptr_t)C & 15) == 0 && epi_vec8(epi, ldc, c_is_f32) && epi_off32(epi, M_total, lda, ldc);
   gemm_params_t p;
   p.A = A; p.B = nullptr; p.C = C;
   p.M = M_total; p.N = N; p.K = K;
@@ -1646,10 +1536,8 @@ extern "C" int vlm_gemm_bf16_grouped(int n_groups, const vlm_gemm_group_t* group
     tiles += (G.rows + BIG_BM - 1) / BIG_BM;
   }
   if (big && p.n_groups >= 1) {
-    int cus = vlm_device_cus();
-    if (cus <= 0) cus = 256;
     p.tiles_m = tiles;
-    if (gemm_big_mode() >= 2 || 2l * tiles * (N / BIG_BN) >= cus) {
+    if (gemm_big_mode() >= 2 || 2l * tiles * (N / BIG_BN) >= plan_cus()) {
       const int rc = launch_gemm_big_variant<true>(p, c_is_f32 != 0, s);
       if (rc <= 0) return rc;
     }
@@ -1663,8 +1551,8 @@ extern "C" int vlm_gemm_bf16_grouped(int n_groups, const vlm_gemm_group_t* group
     if (e.residual) e.residual += r0 * e.ld_res;
     if (e.aux) e.aux = reinterpret_cast<unsigned char*>(e.aux) + r0 * e.ld_aux * 2;
     if (e.row_scale) e.row_scale += r0;
-    const int rc = gemm_dispatch(0, 0, G.rows, N, K, reinterpret_cast<const unsigned char*>(A) + r0 * lda * 2, lda, G.B, G.ldb,
-                                 reinterpret_cast<unsigned char*>(C) + r0 * ldc * (c_is_f32 ? 4 : 2), ldc, c_is_f32, &e, stream, true);
+    const int rc = vlm_gemm_bf16(0, 0, G.rows, N, K, reinterpret_cast<const unsigned char*>(A) + r0 * lda * 2, lda, G.B, G.ldb,
+                                 reinterpret_cast<unsigned char*>(C) + r0 * ldc * (c_is_f32 ? 4 : 2), ldc, c_is_f32, &e, stream);
     if (rc) return rc;
   }
   return VLM_OK;
@@ -1707,8 +1595,7 @@ extern "C" int vlm_gemm_wgrad_grouped(int n_groups, const vlm_wgrad_group_t* gro
   splitk_groups_t rg{};
   if (big) {
     const int ntile = p.tiles_m * p.tiles_n;
-    int cus = vlm_device_cus();
-    if (cus <= 0) cus = 256;
+    const int cus = plan_cus();
     long total_steps = 0;
     int live = 0;
     for (int g = 0; g < n_groups; ++g)
@@ -1761,8 +1648,8 @@ extern "C" int vlm_gemm_wgrad_grouped(int n_groups, const vlm_wgrad_group_t* gro
     e.splitk_ws = splitk_ws;
     e.splitk_ws_bytes = splitk_ws_bytes;
     const size_t r0 = (size_t)G.row0;
-    const int rc = gemm_dispatch(1, 1, M, N, G.rows, reinterpret_cast<const unsigned char*>(A) + r0 * lda * 2, lda,
-                                 reinterpret_cast<const unsigned char*>(B) + r0 * ldb * 2, ldb, G.C, ldc, 1, &e, stream, true);
+    const int rc = vlm_gemm_bf16(1, 1, M, N, G.rows, reinterpret_cast<const unsigned char*>(A) + r0 * lda * 2, lda,
+                                 reinterpret_cast<const unsigned char*>(B) + r0 * ldb * 2, ldb, G.C, ldc, 1, &e, stream);
     if (rc) return rc;
   }
   return VLM_OK;

@@ -8,7 +8,7 @@
  *     nothing: the caller owns outputs and workspaces;
  *   - return 0 on success, a negative VLM_ERR_* otherwise; nothing throws across the boundary;
  *   - process-wide state is limited to (1) diagnostic switches read ONCE from the environment at first use
- *     (VLM_GEMM_CUS, VLM_ATT_DB_GROUPS, VLM_MERGE_VARIANT: thread-safe function-local statics,
+ *     (VLM_GEMM_CUS, VLM_MERGE_VARIANT: thread-safe function-local statics,
  *     immutable afterwards) and (2) the hooks vlm_gemm_set_big_tile_mode and vlm_set_cu_budget (one atomic int each).  None changes results
  *     beyond the fp32 summation order of a GEMM or of the bias-table gradient.
  *
@@ -493,11 +493,12 @@ typedef struct {
   float* dv[2];
 } vlm_attn_colsum_t;
 
-/* delta_ws: f32 scratch of ws_floats elements: at least H * total_rows (rowsum(dO*O)).  With a bias table,
- * vlm_attention_bwd_ws_floats(d, 0) = 3 * H * total_rows also holds the C operands (-lse / (scale log2 e), -delta) of the
- * 16-wave bias-table-gradient kernel (a smaller scratch selects the 8-wave kernel it replaced), and with
- * vlm_attention_bwd_ws_floats(d, 1) elements the per-workgroup histograms are summed by a second small launch instead of
- * global atomics (order-independent result).  dbias_t (f32 [n_cols, R], may be NULL) is ACCUMULATED.  colsum may be NULL. */
+/* delta_ws: f32 scratch of ws_floats >= vlm_attention_bwd_ws_floats(d, .) elements: H * total_rows (rowsum(dO*O)), or
+ * 3 * H * total_rows for a bias table whose gradient cannot come from the fused dK / dV / bias-gradient kernel (more than 1 024
+ * positions in a part): the 16-wave bias-table-gradient kernel's C operands (-lse / (scale log2 e), -delta) live behind delta.
+ * `with_dbias` no longer changes the answer (kept for the signature); a larger scratch is accepted and changes nothing: which
+ * kernels run depends on the descriptor and on dbias_t alone.  dbias_t (f32 [n_cols, R], may be NULL) is ACCUMULATED by float
+ * atomics.  colsum may be NULL. */
 size_t vlm_attention_bwd_ws_floats(const vlm_attn_desc_t* d, int with_dbias);
 int vlm_attention_bwd(const vlm_attn_desc_t* d, const void* out_bf16, int ld_out, const void* dout_bf16, int ld_dout,
                       const float* lse, float* delta_ws, size_t ws_floats, void* dqkv_bf16, int ld_dqkv, float* dbias_t,

@@ -322,3 +322,46 @@ def test_big_tile_mode_range(pkg):
             assert lib.vlm_gemm_set_big_tile_mode(mode) == -1, mode  # VLM_ERR_ARG
     finally:
         lib.vlm_gemm_set_big_tile_mode(-1)
+
+
+def test_attention_bwd_workspace_size(pkg):
+    """vlm_attention_bwd_ws_floats launches nothing and states one size per geometry, whatever `with_dbias` says: H * rows
+    (delta) when there is no bias or the fused dK / dV / bias-gradient kernel's panel fits LDS (at most 1 024 positions in a
+    part), 3 * H * rows (delta | nstat for the 16-wave bias-gradient kernel) when it does not.  Dummy non-null pointers, filled
+    the way ops._attn_desc fills the descriptor.  Host arithmetic only: no GPU needed."""
+    import ctypes
+    L = importlib.import_module("vl_merging_amd._lib")
+    ops = importlib.import_module("vl_merging_amd.ops")
+    if not os.path.exists(L.LIB_PATH):
+        import __graft_entry__ as ge
+        ge.build()
+    lib = L.get_lib()
+
+    def size(B, n0, n1, H, mode, bias=True, with_dbias=0):
+        seq = ops.Seq(B, n0, n1)
+        NP = seq.pos1 + n1
+        d = L.AttnDesc()
+        d.qkv, d.ld_qkv, d.H, d.total_rows = 0x10000, 3 * H * 64, H, seq.rows
+        if bias:
+            d.R, d.bias_t = 300, 0x20000
+            d.rel_index, d.ld_index, d.index_rows = 0x30000, (NP + 3) // 4 * 4, NP
+            d.rel_index_t, d.ld_index_t, d.index_t_rows = 0x40000, (NP + 3) // 4 * 4, NP
+            d.bias_dense, d.bias_dense_t = 0x50000, 0x60000
+            d.dense_tiles = lib.vlm_bias_dense_bytes(n0, n1, seq.pos1, mode) // 4096
+        d.mode = mode
+        d.B, d.n0, d.n1, d.base0, d.base1, d.pos1 = seq.B, seq.n0, seq.n1, seq.base0, seq.base1, seq.pos1
+        d.scale = 0.125
+        return lib.vlm_attention_bwd_ws_floats(ctypes.byref(d), with_dbias), H * seq.rows
+
+    for mode in (L.ATTN_JOINT, L.ATTN_SEPARATE):
+        for B, n0, n1, H, bias, factor in ((22, 40, 577, 12, True, 1),     # 617 joint positions: the panel fits
+                                           (2, 40, 901, 2, True, 1),       # 941 (480^2): fits with four waves
+                                           (2, 40, 984, 2, True, 1),       # exactly 1 024 positions
+                                           (1, 8, 1040, 1, True, 3),       # 1 048 joint / 1 040 image positions in one part: it does not
+                                           (1, 8, 1040, 1, False, 1)):
+            got0, hr = size(B, n0, n1, H, mode, bias, 0)
+            got1, _ = size(B, n0, n1, H, mode, bias, 1)
+            assert got0 == got1 == factor * hr, (mode, B, n0, n1, H, bias, got0, got1, hr)
+    # SEPARATE looks at each part alone: 40 text + 1 000 image positions fit, the same 1 040 joint positions do not
+    assert size(1, 40, 1000, 1, L.ATTN_SEPARATE)[0] == 1040
+    assert size(1, 40, 1000, 1, L.ATTN_JOINT)[0] == 3 * 1040

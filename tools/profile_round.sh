@@ -58,7 +58,7 @@ try:
         nm = re.sub(r"[<(].*", "", r["Name"]).replace("void ", "")
         t[nm] = t.get(nm, 0.0) + float(r["TotalDurationNs"]) / 6e6  # ms per step
     fwd = sum(v for k, v in t.items() if k.startswith("attn_fwd"))
-    bwd = sum(v for k, v in t.items() if k.startswith("attn_bwd_") or k == "attn_dbias_fold_kernel")
+    bwd = sum(v for k, v in t.items() if k.startswith("attn_bwd_"))
     alg = {"fwd_tflop_per_step": 1.427, "fwd_ms_per_step": fwd, "fwd_tflops": 1.427 / fwd * 1e3 if fwd else None,
            "fwd_frac_of_2500": 1.427 / fwd * 1e3 / 2500 if fwd else None,
            "bwd_tflop_per_step": 2.854, "bwd_ms_per_step": bwd, "bwd_tflops": 2.854 / bwd * 1e3 if bwd else None,
@@ -71,17 +71,17 @@ print(json.dumps(res, indent=1))
 PY
 grep -E '^\{"metric' $OUT/trace.log | tail -1 | cut -c1-600 > $OUT/${TAG}_bench_line_under_trace.txt
 head -25 $OUT/${TAG}_train_ufo384_b22_kernel_stats.csv
-# launches of one step by origin (this library / torch-native / copies), and the attention kernels standalone: the hand-placed
-# streams against the round-3 kernels, with the in-kernel clock (s_memtime / s_memrealtime stamps of the -DVLM_DIAG harness)
+# launches of one step by origin (this library / torch-native / copies), and the attention kernels standalone,
+# with the in-kernel clock (s_memtime / s_memrealtime stamps of the -DVLM_DIAG harness)
 python3 tools/count_launches.py > $OUT/${TAG}_launches_per_step.txt 2>&1
 {
-  for args in "88 0 1 0" "22 0 1 0"; do for v in 0 1; do
-    echo -n "forward  hand-placed=$v  B mode bias = $args: "; VLM_ATT_FWD2=$v bash tools/scratch/trace_attn.sh attn_bench $args 2>&1 | grep -E "attn_fwd" | awk '{print $1, $(NF-1), $NF}'
-  done; done
-  for args in "88 0 1 1 1" "22 0 1 1 1"; do for v in 0 1; do
-    echo -n "backward hand-placed dQ=$v  $args: "; VLM_ATT_DQ2=$v bash tools/scratch/trace_attn.sh attn_bench $args 2>&1 | grep -E "attn_bwd" | awk '{printf "%s %s us; ", $1, $(NF-1)} END {print ""}'
-  done; done
-  for v in 0 1; do echo "stamps forward hand-placed=$v:"; VLM_ATT_FWD2=$v tools/scratch/attn_bench_diag 88 0 1 0 2>&1 | grep -E "wave 0 clock"; done
-  for v in 0 1; do echo "stamps backward (dQ kernel) hand-placed=$v:"; VLM_ATT_DQ2=$v tools/scratch/attn_bench_diag 88 0 1 1 1 2>&1 | grep -E "wave 0 clock"; done
+  for args in "88 0 1 0" "22 0 1 0"; do
+    echo -n "forward  B mode bias = $args: "; bash tools/scratch/trace_attn.sh attn_bench $args 2>&1 | grep -E "attn_fwd" | awk '{print $1, $(NF-1), $NF}'
+  done
+  for args in "88 0 1 1 1" "22 0 1 1 1"; do
+    echo -n "backward $args: "; bash tools/scratch/trace_attn.sh attn_bench $args 2>&1 | grep -E "attn_bwd" | awk '{printf "%s %s us; ", $1, $(NF-1)} END {print ""}'
+  done
+  echo "stamps forward:"; tools/scratch/attn_bench_diag 88 0 1 0 2>&1 | grep -E "wave 0 clock"
+  echo "stamps backward (dQ kernel):"; tools/scratch/attn_bench_diag 88 0 1 1 1 2>&1 | grep -E "wave 0 clock"
 } > $OUT/${TAG}_attention_harness.txt 2>&1
 cat $OUT/${TAG}_attention_harness.txt

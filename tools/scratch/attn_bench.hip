@@ -48,7 +48,7 @@ int main(int argc, char** argv) {
   d.bias_dense = dense; d.bias_dense_t = dense_t; d.dense_tiles = (int)(cb / 4096);
   auto run = [&]() {
     int rc = what == 0 ? vlm_attention_fwd(&d, out, D, lse, 0)
-                       : vlm_attention_bwd(&d, out, D, dout, D, lse, delta, vlm_attention_bwd_ws_floats(&d, 1), dqkv, 3 * D, with_bias && with_dbias ? dbias : nullptr, nullptr, 0);
+                       : vlm_attention_bwd(&d, out, D, dout, D, lse, delta, vlm_attention_bwd_ws_floats(&d, 0), dqkv, 3 * D, with_bias && with_dbias ? dbias : nullptr, nullptr, 0);
     if (rc) { printf("launch failed rc=%d\n", rc); exit(1); }
   };
   if (what == 1) { int rc = vlm_attention_fwd(&d, out, D, lse, 0); if (rc) { printf("fwd rc=%d\n", rc); return 1; } }

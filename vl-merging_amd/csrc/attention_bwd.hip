@@ -13,7 +13,6 @@
 #include "vlm_common.h"
 #include "attention_common.h"
 #include "vlm_diag.h"
-#include <stdlib.h>
 
 struct attn_bwd_params_t {
   attn_params_t f;        // forward description (qkv, bias, index, ranges)
@@ -27,7 +26,6 @@ struct attn_bwd_params_t {
   bf16_t* dqkv;           // [rows, 3*H*64]
   int ld_dqkv;
   float* dbias_t;         // [n_cols, R] accumulate
-  float* dbias_part;      // [items][R] per-workgroup histograms (two-stage reduction) or NULL (global atomics)
   float* nstat;           // [2][H][rows]: -lse / c1 and -delta for the 16-wave bias-gradient kernel (written by the dQ kernel) or NULL
   float* dq_colsum[2];    // per segment (0 text rows, 1 image rows): [H*64] += column sums of dQ (q_bias grad) or NULL
   float* dv_colsum[2];    // same for dV (v_bias gradient)
@@ -563,10 +561,8 @@ __global__ __launch_bounds__(ATT_DB16_THREADS) void attn_bwd_dbias16_kernel(cons
   const int logical = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= per || logical >= total) return;
   int item = logical % pairs;
-  const int pair_id = item;
   const int grp = (logical / pairs) % n_groups;
   const int h = logical / (pairs * n_groups);
-  const int part_slot = (pair_id * p.H + h) * n_groups + grp;
   int kt = 0;
   att_span_t sp = att_span(ps, p.mode, 0);
   for (;; ++kt) {
@@ -760,113 +756,94 @@ __global__ __launch_bounds__(ATT_DB16_THREADS) void attn_bwd_dbias16_kernel(cons
     }
   }
   __syncthreads();
-  if (bp.dbias_part) {
-    float* g = bp.dbias_part + (size_t)part_slot * p.R;
-    for (int i = tid; i < p.R; i += ATT_DB16_THREADS) g[i] = (float)(long long)hist64[i] * UNFIX;
-  } else {
-    float* g = bp.dbias_t + (size_t)(p.head_row0 + h) * p.R;
-    for (int i = tid; i < p.R; i += ATT_DB16_THREADS) {
-      const long long v = (long long)hist64[i];
-      if (v != 0) atomicAdd(g + i, (float)v * UNFIX);
-    }
+  float* g = bp.dbias_t + (size_t)(p.head_row0 + h) * p.R;
+  for (int i = tid; i < p.R; i += ATT_DB16_THREADS) {
+    const long long v = (long long)hist64[i];
+    if (v != 0) atomicAdd(g + i, (float)v * UNFIX);
   }
 }
 
-// dbias_t[head_row0 + h][i] += sum over the work items of head h (item = (pair * H + h) * groups + grp) of part[item][i]
-__global__ __launch_bounds__(256) void attn_dbias_fold_kernel(const float* __restrict__ part, int R, int H, int groups, int pairs,
-                                                              float* __restrict__ dbias_t, int head_row0) {
-  const int i = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
-  if (i >= R) return;
-  float sum = 0.f;
-  for (int pr = 0; pr < pairs; ++pr)
-    for (int g = 0; g < groups; ++g) sum += part[((size_t)(pr * H + h) * groups + g) * R + i];
-  dbias_t[(size_t)(head_row0 + h) * R + i] += sum;
-}
-
-// work items of the bias-gradient kernel for this geometry: (key tile, query tile) pairs and sample groups
-static void att_dbias_items(const attn_params_t& p, int& pairs, int& groups) {
-  const int NP = p.seq.pos1 + p.seq.n1;
+// attn_bwd_dbias16_kernel's (key tile, query tile) pairs for this geometry ...
+static int att_dbias_pairs(const attn_params_t& p) {
   if (p.mode == VLM_ATTN_SEPARATE) {
     const int a = (p.seq.n0 + ATT_BQ - 1) / ATT_BQ, c = (p.seq.n1 + ATT_BQ - 1) / ATT_BQ;
-    pairs = a * a + c * c;
-  } else {
-    const int a = (NP + ATT_BQ - 1) / ATT_BQ;
-    pairs = a * a;
+    return a * a + c * c;
   }
-  int cus = vlm_device_cus();
-  if (cus <= 0) cus = 256;
-  if (pairs <= 0) {
-    groups = 1;
-    return;
-  }
-  // an item costs its samples (2.2 us each) plus the histogram tail (10 us); the CUs finish within half an
-  // item of each other.  (Harness sweep, 300 (pair, head) items per group: 88 samples 330 / 294 / 282 / 297 / 298 us for 1..5
-  // groups, 66: 253 / 226 / 218 / 229 / 243, 22: 108 / 104 / 113 / 127 / 131 -- the model picks 3, 3, 2.)
-  static const int forced = []() {  // VLM_ATT_DB_GROUPS=n overrides the model (experiments); parsed once
-    const char* e = getenv("VLM_ATT_DB_GROUPS");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced > 0) {
-    groups = forced < p.seq.B ? forced : p.seq.B;
-    return;
-  }
-  groups = 1;
+  const int a = (p.seq.pos1 + p.seq.n1 + ATT_BQ - 1) / ATT_BQ;
+  return a * a;
+}
+// ... and its sample groups: an item costs its samples (2.2 us each) plus the histogram tail (10 us); the CUs finish within half an
+// item of each other.  (Harness sweep, 300 (pair, head) items per group: 88 samples 330 / 294 / 282 / 297 / 298 us for 1..5
+// groups, 66: 253 / 226 / 218 / 229 / 243, 22: 108 / 104 / 113 / 127 / 131 -- the model picks 3, 3, 2.)
+static int att_dbias_groups(const attn_params_t& p, int pairs, int cus) {
+  int groups = 1;
   float best = 1e30f;
-  for (int g = 1; g <= 8 && g <= p.seq.B; ++g) {
+  for (int g = 1; g <= 8 && g <= p.seq.B && pairs > 0; ++g) {
     const float item = 2.2f * (float)p.seq.B / (float)g + 10.0f;
     const float t = ((float)pairs * p.H * g / (float)cus + 0.5f) * item;
     if (t < best) { best = t; groups = g; }
   }
+  return groups;
 }
 
-// ---- the fused dK / dV / bias-gradient launch (attention_bwd_dkvb.h): which form, how many sample groups -----------------------
-struct dkvb_plan_t {
-  int W;             // waves per workgroup (8: two per SIMD; 4 when the panel leaves room for four slots only); 0: does not apply
-  int panel_blocks, groups, items;
-  size_t lds;
+// ---- the backward's plan: which kernels run for a call and how its workspace is laid out ---------------------------------------
+// Stated ONCE: vlm_attention_bwd_ws_floats returns its total, vlm_attention_bwd launches from it.
+struct att_bwd_plan_t {
+  bool dq2;          // dQ by the hand-placed stream (attention_bwd_dq2.h) instead of attn_bwd_dq_kernel<true>
+  int W;             // fused dK / dV / bias-gradient kernel (attention_bwd_dkvb.h): waves per workgroup (8: two per SIMD; 4 when the
+                     // panel leaves room for four slots only); 0: attn_bwd_dkv_kernel (+ attn_bwd_dbias16_kernel for the table)
+  int panel_blocks;  // fused: the panel's height in 4-KB blocks
+  size_t lds;        // fused: dynamic LDS bytes
+  int groups, items; // sample groups and work items of the kernel that takes the bias-table gradient
+  size_t nstat_off;  // workspace = delta [H][rows] | nstat [2][H][rows]; nstat is carved for attn_bwd_dbias16_kernel only (else 0)
+  size_t ws_floats;
 };
-static dkvb_plan_t dkvb_plan(const attn_params_t& p) {
-  dkvb_plan_t pl = {0, 0, 1, 0, 0};
-  static const int enabled = []() {  // VLM_ATT_BWD_FUSED=0: the round-2..4 pair attn_bwd_dkv_kernel + attn_bwd_dbias16_kernel (A/B)
-    const char* e = getenv("VLM_ATT_BWD_FUSED");
-    return e ? atoi(e) : 1;
-  }();
-  if (!enabled || !p.bias_t || !p.dense_t || !p.idx) return pl;
-  for (int W = 8; W >= 4; W -= 4) {
-    int pb;
-    const size_t lds = dkvb_lds_bytes(p, W, pb);
-    if (lds) { pl.W = W; pl.panel_blocks = pb; pl.lds = lds; break; }
-  }
-  if (!pl.W) return pl;
-  const dkvb_geom_t gm = dkvb_geom(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode);
-  const int nkb = gm.nkb[0] + gm.nkb[1];
+static att_bwd_plan_t att_bwd_plan(const attn_params_t& p, bool want_dbias) {
+  const size_t hr = (size_t)p.H * p.total_rows;
+  att_bwd_plan_t pl = {p.bias_t && att_handplaced_covers(p), 0, 0, 0, 1, 0, 0, hr};
+  if (!want_dbias) return pl;
   int cus = vlm_device_cus();
   if (cus <= 0) cus = 256;
-  // one workgroup per CU (the panel): sample groups only where heads x key blocks leave CUs idle (small models)
-  int g = cus / (nkb * p.H > 0 ? nkb * p.H : 1);
-  if (g < 1) g = 1;
-  const int per_round = pl.W;  // a group should hold at least one full round of samples
-  if (g > (p.seq.B + per_round - 1) / per_round) g = (p.seq.B + per_round - 1) / per_round;
-  if (g < 1) g = 1;
-  pl.groups = g;
-  pl.items = nkb * p.H * g;
+  for (int W = 8; W >= 4 && !pl.W && p.dense_t && p.idx; W -= 4) {
+    pl.lds = dkvb_lds_bytes(p, W, pl.panel_blocks);
+    if (pl.lds) pl.W = W;
+  }
+  if (pl.W) {
+    const dkvb_geom_t gm = dkvb_geom(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode);
+    const int nkb = gm.nkb[0] + gm.nkb[1];
+    // one workgroup per CU (the panel): sample groups only where heads x key blocks leave CUs idle (small models), and a group
+    // holds at least one full round of W samples
+    const int rounds = (p.seq.B + pl.W - 1) / pl.W;
+    int g = cus / (nkb * p.H > 0 ? nkb * p.H : 1);
+    if (g > rounds) g = rounds;
+    pl.groups = g < 1 ? 1 : g;
+    pl.items = nkb * p.H * pl.groups;
+    return pl;
+  }
+  // work items: every (128-key tile, 128-query tile of its span) pair x heads x sample groups; the samples are cut into groups
+  // until the grid has ~3 items per CU (the per-item histogram is the price of every extra group)
+  const int pairs = att_dbias_pairs(p);
+  pl.groups = att_dbias_groups(p, pairs, cus);
+  pl.items = pairs * p.H * pl.groups;
+  pl.nstat_off = hr;
+  pl.ws_floats = 3 * hr;
   return pl;
 }
 
+// (with_dbias no longer changes the answer: the caller may not know yet, so a biased geometry gets the larger of its two sizes)
 extern "C" size_t vlm_attention_bwd_ws_floats(const vlm_attn_desc_t* d, int with_dbias) {
+  (void)with_dbias;
   attn_params_t p;
   if (att_fill_params(d, p) != VLM_OK) return 0;
-  size_t n = (size_t)p.H * p.total_rows;  // delta
-  if (p.bias_t) n *= 3;                    // + (-lse / c1 | -delta) for the 16-wave bias-gradient kernel
-  if (with_dbias && p.bias_t) {
-    int pairs, groups;
-    att_dbias_items(p, pairs, groups);
-    size_t items = (size_t)pairs * p.H * groups;
-    const dkvb_plan_t pl = dkvb_plan(p);
-    if (pl.W && (size_t)pl.items > items) items = (size_t)pl.items;  // either form's per-item histograms fit
-    n += items * p.R;
-  }
-  return n;
+  return att_bwd_plan(p, p.bias_t != nullptr).ws_floats;
+}
+
+template <int W>
+static void dkvb_launch(const attn_bwd_params_t& bp, const att_bwd_plan_t& pl, hipStream_t s) {
+  // dynamic LDS beyond 64 KB has to be asked for once per kernel
+  static const hipError_t asked = hipFuncSetAttribute((const void*)attn_bwd_dkvb_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)asked;
+  hipLaunchKernelGGL((attn_bwd_dkvb_kernel<W>), dim3((unsigned)((pl.items + 7) / 8 * 8)), dim3(W * 64), pl.lds, s, bp, pl.groups, pl.panel_blocks);
 }
 
 extern "C" int vlm_attention_bwd(const vlm_attn_desc_t* d, const void* out, int ld_out, const void* d_out,
@@ -876,8 +853,6 @@ extern "C" int vlm_attention_bwd(const vlm_attn_desc_t* d, const void* out, int 
   int rc = att_fill_params(d, bp.f);
   if (rc != VLM_OK) return rc;
   if (!out || !d_out || !lse || !delta_ws || !dqkv) return VLM_ERR_ARG;
-  bp.dbias_part = nullptr;
-  bp.nstat = nullptr;
   if ((ld_out & 7) || (ld_dout & 7) || (ld_dqkv & 3) || ((uintptr_t)out & 15) || ((uintptr_t)d_out & 15))
     return VLM_ERR_ARG;
   if (bp.f.bias_t && (!bp.f.idx || (bp.f.ld_idx & 3))) return VLM_ERR_ARG;
@@ -901,67 +876,28 @@ extern "C" int vlm_attention_bwd(const vlm_attn_desc_t* d, const void* out, int 
   if ((size_t)p.total_rows * p.ld_qkv * 2 >= (1ull << 32) || (size_t)p.total_rows * ld_dout * 2 >= (1ull << 32)) return VLM_ERR_UNSUPPORTED;
   if (p.bias_t && (!p.dense || !p.dense_t)) return VLM_ERR_ARG;  // biased attention runs on the dense tables (vlm_bias_dense)
   if (p.dense && p.dense_tiles != att_dense_layout(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode).tiles) return VLM_ERR_ARG;
-  if (ws_floats < (size_t)p.H * p.total_rows) return VLM_ERR_WORKSPACE;  // delta[h][row]
   // the bias-gradient kernel's 64-bit histogram (R bins + the item's maximum) lives in its two operand stages' LDS
   if (p.bias_t && dbias_t && ((size_t)p.R * 8 + 8 > 2 * (size_t)(8 * ATT_TILE_BYTES + 1024) || !p.idx_t)) return VLM_ERR_UNSUPPORTED;
-  // ... and takes its C operands from the dQ launch: workspace = delta | nstat (-lse / c1, -delta) | per-item histograms
-  const size_t hr = (size_t)p.H * p.total_rows;
-  const bool want_dbias = p.bias_t && dbias_t;
-  if (want_dbias && ws_floats < 3 * hr) return VLM_ERR_WORKSPACE;  // vlm_attention_bwd_ws_floats says so
-  bp.nstat = want_dbias ? delta_ws + hr : nullptr;
+  // ... and takes its C operands (nstat) from the dQ launch
+  const att_bwd_plan_t pl = att_bwd_plan(p, p.bias_t && dbias_t);
+  if (ws_floats < pl.ws_floats) return VLM_ERR_WORKSPACE;  // vlm_attention_bwd_ws_floats says so
+  bp.nstat = pl.nstat_off ? delta_ws + pl.nstat_off : nullptr;
   bp.o = reinterpret_cast<const bf16_t*>(out);
   bp.ld_o = ld_out;
   bp.inv_c1 = 1.0f / (p.scale * ATT_LOG2E);
 
   const int nt = att_num_tiles(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode);
   dim3 grid(att_grid_size(nt, p.seq.B, p.H)), block(ATT_THREADS);
-  const dkvb_plan_t pl = want_dbias ? dkvb_plan(p) : dkvb_plan_t{0, 0, 1, 0, 0};
-  if (pl.W) {
-    // dQ (+ delta), then dK / dV and the bias-table gradient in ONE launch: 7 MFMA products per score instead of 9
-    bp.nstat = nullptr;  // (the 16-wave kernel's C operands are not needed)
-    if (!att_dq2_launch(bp, grid, s)) {  // the hand-placed stream (attention_bwd_dq2.h) takes the calls it covers
-#ifdef VLM_DIAG  // harness only: VLM_DIAG_DQ_PAD_LDS=bytes of unused dynamic LDS (40960: one workgroup per CU instead of two)
-      static const size_t dq_pad = [] { const char* e = getenv("VLM_DIAG_DQ_PAD_LDS"); return e ? (size_t)atoi(e) : (size_t)0; }();
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<true>), grid, block, dq_pad, s, bp);
-#else
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<true>), grid, block, 0, s, bp);
-#endif
-    }
+  if (p.bias_t) {
+    if (pl.dq2) hipLaunchKernelGGL(attn_bwd_dq2_kernel, grid, block, 0, s, bp);
+    else hipLaunchKernelGGL((attn_bwd_dq_kernel<true>), grid, block, 0, s, bp);
     VLM_CHECK_LAUNCH();
-    const size_t need = hr + (size_t)pl.items * p.R;
-    bp.dbias_part = ws_floats >= need ? delta_ws + hr : nullptr;
-    static bool attr_set[2] = {false, false};  // dynamic LDS beyond 64 KB has to be asked for once per kernel
-    if (pl.W == 8) {
-      if (!attr_set[0]) { (void)hipFuncSetAttribute((const void*)attn_bwd_dkvb_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set[0] = true; }
-      hipLaunchKernelGGL((attn_bwd_dkvb_kernel<8>), dim3((unsigned)((pl.items + 7) / 8 * 8)), dim3(512), pl.lds, s, bp, pl.groups, pl.panel_blocks);
-    } else {
-      if (!attr_set[1]) { (void)hipFuncSetAttribute((const void*)attn_bwd_dkvb_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set[1] = true; }
-      hipLaunchKernelGGL((attn_bwd_dkvb_kernel<4>), dim3((unsigned)((pl.items + 7) / 8 * 8)), dim3(256), pl.lds, s, bp, pl.groups, pl.panel_blocks);
-    }
-    if (bp.dbias_part) {
+    if (pl.W == 8) dkvb_launch<8>(bp, pl, s);  // dK / dV and the bias-table gradient in ONE launch: 7 MFMA products per score instead of 9
+    else if (pl.W == 4) dkvb_launch<4>(bp, pl, s);
+    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<true>), grid, block, 0, s, bp);
+    if (!pl.W && dbias_t) {
       VLM_CHECK_LAUNCH();
-      const dkvb_geom_t gm = dkvb_geom(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode);
-      hipLaunchKernelGGL(attn_dbias_fold_kernel, dim3((p.R + 255) / 256, p.H), dim3(256), 0, s, bp.dbias_part, p.R, p.H, pl.groups,
-                         gm.nkb[0] + gm.nkb[1], dbias_t, p.head_row0);
-    }
-  } else if (p.bias_t) {
-    if (!att_dq2_launch(bp, grid, s)) hipLaunchKernelGGL((attn_bwd_dq_kernel<true>), grid, block, 0, s, bp);
-    VLM_CHECK_LAUNCH();
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<true>), grid, block, 0, s, bp);
-    if (dbias_t) {
-      VLM_CHECK_LAUNCH();
-      // work items: every (128-key tile, 128-query tile of its span) pair x heads x sample groups; the samples are cut
-      // into groups until the grid has ~3 items per CU (the per-item histogram is the price of every extra group)
-      int pairs, groups;
-      att_dbias_items(p, pairs, groups);
-      const size_t items = (size_t)pairs * p.H * groups, need = 3 * hr + items * p.R;
-      bp.dbias_part = ws_floats >= need ? delta_ws + 3 * hr : nullptr;
-      hipLaunchKernelGGL(attn_bwd_dbias16_kernel, dim3((unsigned)((items + 7) / 8 * 8)), dim3(ATT_DB16_THREADS), 0, s, bp, groups);
-      if (bp.dbias_part) {
-        VLM_CHECK_LAUNCH();
-        hipLaunchKernelGGL(attn_dbias_fold_kernel, dim3((p.R + 255) / 256, p.H), dim3(256), 0, s, bp.dbias_part, p.R, p.H, groups,
-                           pairs, dbias_t, p.head_row0);
-      }
+      hipLaunchKernelGGL(attn_bwd_dbias16_kernel, dim3((unsigned)((pl.items + 7) / 8 * 8)), dim3(ATT_DB16_THREADS), 0, s, bp, pl.groups);
     }
   } else {
     hipLaunchKernelGGL((attn_bwd_dq_kernel<false>), grid, block, 0, s, bp);

@@ -375,15 +375,10 @@ __global__ __launch_bounds__(W * 64, 1) void attn_bwd_dkvb_kernel(const attn_bwd
     }
   }
   __syncthreads();
-  if (bp.dbias_part) {
-    float* g = bp.dbias_part + (size_t)((kbi * p.H + h) * n_groups + grp) * p.R;
-    for (int i = tid; i < p.R; i += W * 64) g[i] = (float)(long long)hist64[i] * UNFIX;
-  } else {
-    float* g = bp.dbias_t + (size_t)(p.head_row0 + h) * p.R;
-    for (int i = tid; i < p.R; i += W * 64) {
-      const long long v = (long long)hist64[i];
-      if (v != 0) atomicAdd(g + i, (float)v * UNFIX);
-    }
+  float* g = bp.dbias_t + (size_t)(p.head_row0 + h) * p.R;
+  for (int i = tid; i < p.R; i += W * 64) {
+    const long long v = (long long)hist64[i];
+    if (v != 0) atomicAdd(g + i, (float)v * UNFIX);
   }
 }
 

@@ -1,7 +1,7 @@
 // dQ of the fused attention backward as a hand-placed instruction stream (round 6; included by attention_bwd.hip after
 // attn_bwd_params_t).  Same operator and outputs as attn_bwd_dq_kernel (reference: autograd of vision_transformer.py:346-358): dQ,
 // delta = rowsum(dO * O) and the C operands of the bias-gradient kernel from its prologue, the q_bias column sums from its
-// epilogue.  It takes the calls that have a dense bias table and a geometry the stream covers (att_dq2_eligible).
+// epilogue.  It takes the calls that have a dense bias table and a geometry the stream covers (att_handplaced_covers, attention_common.h).
 //
 // Structure (gen/attn_dq2_gen.py holds the register map and the stream): a wave = 32 query positions of one (sample, head), a
 // workgroup = 128 positions, TWO workgroups per CU (252 registers per wave).  Keys stream in 32-key blocks through a ring of four
@@ -279,20 +279,3 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq2_kernel(const attn
   ATT_STAMP(51);
 }
 
-// a dense bias table, no image keep mask (mask words exist for tiles 0 and 1; the stream's own loads start at position 96 with
-// image rows: the text segment and the gap must end inside tile 0), 32-bit buffer offsets
-static bool att_dq2_eligible(const attn_params_t& p) {
-  if (!p.dense || p.keep1) return false;
-  if (p.seq.pos1 > ATT_BK) return false;
-  return true;
-}
-
-// 1 = launched, 0 = not a call for this kernel
-static int att_dq2_launch(const attn_bwd_params_t& bp, dim3 grid, hipStream_t s) {
-  static const int enabled = [] { const char* e = getenv("VLM_ATT_DQ2"); return e ? atoi(e) : 1; }();
-  if (!enabled || !att_dq2_eligible(bp.f)) return 0;
-  // diagnostic: VLM_ATT_DQ2_LDS_PAD bytes of unused dynamic LDS leave room for fewer workgroups per CU (docs/experiments.md, round 6)
-  static const int lds_pad = [] { const char* e = getenv("VLM_ATT_DQ2_LDS_PAD"); return e ? atoi(e) : 0; }();
-  hipLaunchKernelGGL(attn_bwd_dq2_kernel, grid, dim3(ATT_THREADS), (size_t)lds_pad, s, bp);
-  return 1;
-}

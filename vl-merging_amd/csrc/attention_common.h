@@ -125,6 +125,13 @@ static inline int att_fill_params(const vlm_attn_desc_t* d, attn_params_t& p) {
   return VLM_OK;
 }
 
+// What the hand-placed streams (attn_fwd2_kernel, attn_bwd_dq2_kernel) cover: a dense bias table, no image keep mask (their mask
+// words exist for tiles 0 and 1 only, and their own loads start with image rows: the text segment and the gap must end inside
+// tile 0), 32-bit buffer descriptors over qkv.  Every other call runs attn_fwd_kernel / attn_bwd_dq_kernel.
+static inline bool att_handplaced_covers(const attn_params_t& p) {
+  return p.dense && !p.keep1 && p.seq.pos1 <= ATT_BK && (size_t)p.total_rows * p.ld_qkv * 2 < (1ull << 32);
+}
+
 // attention_fwd2.hip: 1 = launched, 0 = not a call for the hand-placed kernel, < 0 = error
 int att_fwd2_launch(const attn_params_t& p, hipStream_t s);
 

@@ -1,6 +1,6 @@
 // Fused attention forward, hand-placed instruction stream (round 6).  Same operator as attention_fwd.hip (reference
 // vision_transformer.py:346-358 + get_rel_pos_bias vilt_module.py:1061-1064), same inputs and outputs; this is the kernel
-// vlm_attention_fwd launches whenever the call has a dense bias table and a geometry it covers (att_fwd2_eligible), the
+// vlm_attention_fwd launches whenever the call has a dense bias table and a geometry it covers (att_handplaced_covers, attention_common.h), the
 // round-2 kernel stays for everything else.
 //
 // Why another kernel.  The round-2/3 kernel (three 32-row waves per SIMD, compiler-scheduled) spends ~1 200 SIMD cycles per
@@ -22,7 +22,6 @@
 #include "vlm_common.h"
 #include "attention_common.h"
 #include "vlm_diag.h"
-#include <stdlib.h>
 
 #define F2_STAGE 16384
 #define F2_NSTAGE 4
@@ -243,24 +242,12 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd2_kernel(const attn_pa
   ATT_STAMP(51);
 }
 
-// The geometries the stream covers: a dense bias table, no image keep mask (its mask words exist for tiles 0 and 1 only, and its
-// own loads start at position 64 with image rows: the text segment and the gap must end inside tile 0), 32-bit buffer offsets.
-static bool att_fwd2_eligible(const attn_params_t& p) {
-  if (!p.dense || p.keep1) return false;
-  if (p.seq.pos1 > ATT_BK) return false;
-  if ((size_t)p.total_rows * p.ld_qkv * 2 >= (1ull << 32)) return false;
-  return true;
-}
-
 // returns 1 when it has launched the call, 0 when the call is not for this kernel, < 0 on error
 int att_fwd2_launch(const attn_params_t& p, hipStream_t s) {
-  static const int enabled = [] { const char* e = getenv("VLM_ATT_FWD2"); return e ? atoi(e) : 1; }();
-  if (!enabled || !att_fwd2_eligible(p)) return 0;
+  if (!att_handplaced_covers(p)) return 0;
   const int nt = att_num_tiles(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode);
   dim3 grid(att_grid_size(nt, (p.seq.B + 1) / 2, p.H)), block(ATT_THREADS);
-  // diagnostic (docs/experiments.md, round 6): VLM_ATT_FWD2_LDS_PAD bytes of unused dynamic LDS leave room for ONE workgroup per CU
-  static const int lds_pad = [] { const char* e = getenv("VLM_ATT_FWD2_LDS_PAD"); return e ? atoi(e) : 0; }();
-  hipLaunchKernelGGL(attn_fwd2_kernel, grid, block, (size_t)lds_pad, s, p);
+  hipLaunchKernelGGL(attn_fwd2_kernel, grid, block, 0, s, p);
   if (hipGetLastError() != hipSuccess) return VLM_ERR_LAUNCH;
   return 1;
 }

@@ -57,7 +57,6 @@ S_BOFF = 60      # bias scalar offset of the pass's first 64-key tile (tile * 40
 S_TMP = 61
 S_LO = 62        # s[62:63] = lower half-wave
 
-PRIO = os.environ.get("VLM_GEN_PRIO", "slot")
 MF_BF = "v_mfma_f32_32x32x16_bf16"
 MF_F16 = "v_mfma_f32_32x32x16_f16"
 
@@ -270,14 +269,13 @@ def build():
     # turns MFMA by MFMA (both stretch their matrix phases, both then sit in their vector phases together).  The wave in the ODD
     # hardware slot of its SIMD runs at priority 1 for the whole stream -- one static s_setprio, no flips
     # (MI355X_MICROARCH.md, "Two waves per SIMD", items 4 and 9) -- so that one wave's matrix chain runs through while its
-    # partner does its vector work.  PRIO_EXPERIMENT (env-less switch of the generator): "none" leaves it out.
-    if PRIO == "slot":
-        pre += [Op("s_getreg_b32 s%d, hwreg(HW_REG_HW_ID, 0, 4)" % S_TMP, "salu", [], ["s%d" % S_TMP]),
-                Op("s_and_b32 s%d, s%d, 1" % (S_TMP, S_TMP), "salu", ["s%d" % S_TMP], ["s%d" % S_TMP]),
-                Op("s_cmp_eq_u32 s%d, 1" % S_TMP, "salu", ["s%d" % S_TMP], ["scc"]),
-                Op("s_cbranch_scc0 L_noprio_%=", "salu"),
-                Op("s_setprio 1", "salu"),
-                Op("L_noprio_%=:", "raw")]
+    # partner does its vector work.
+    pre += [Op("s_getreg_b32 s%d, hwreg(HW_REG_HW_ID, 0, 4)" % S_TMP, "salu", [], ["s%d" % S_TMP]),
+            Op("s_and_b32 s%d, s%d, 1" % (S_TMP, S_TMP), "salu", ["s%d" % S_TMP], ["s%d" % S_TMP]),
+            Op("s_cmp_eq_u32 s%d, 1" % S_TMP, "salu", ["s%d" % S_TMP], ["scc"]),
+            Op("s_cbranch_scc0 L_noprio_%=", "salu"),
+            Op("s_setprio 1", "salu"),
+            Op("L_noprio_%=:", "raw")]
     pre += dma_offsets()
     pre.append(valu("v_mov_b32_e32 v%d, v%d" % (V_KMC, V_ADDR + 8), [], ["v%d" % V_KMC]))
     # M(0) alone: the chains of block 0 (no dQ yet) on the bias operands the prologue loaded; block 1's operands came with the

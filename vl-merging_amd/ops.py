@@ -956,7 +956,7 @@ def attention_bwd(qkv, out, dout, lse, dqkv, seq, H, *, bias_t=None, head_row0=0
                     if t.dtype != F32 or t.numel() < H * 64 or not t.is_contiguous():
                         raise L.VlmError("attention_bwd: column-sum outputs must be contiguous f32 [H*64]")
                     getattr(cs, name)[sgm] = t.data_ptr()
-    need = L.get_lib().vlm_attention_bwd_ws_floats(ctypes.byref(d), 0)  # (1: two-stage bias-gradient fold; measured no faster)
+    need = L.get_lib().vlm_attention_bwd_ws_floats(ctypes.byref(d), 0)
     if delta_ws is None or delta_ws.numel() < need:
         key = (qkv.device.index, torch.cuda.current_stream().cuda_stream)
         delta_ws = _ATTN_WS.get(key)

@@ -80,6 +80,66 @@ int vlm_merge_plan_upload(const vlm_merge_job_t* jobs_host, int n_jobs, void* wo
 int vlm_merge_run(const void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * TIES merge (trim, elect sign, disjoint mean; Yadav et al. 2023), csrc/ties.hip.  NO REFERENCE SITE: the reference has
+ * no TIES; the arithmetic below is the specification and is pinned to a numpy restatement of it (tests/ties_restatement.py),
+ * not to the reference.  One job = one output tensor with central tensor c (base), sources W_0 .. W_{S-1}, scale lam;
+ * fp32, one rounding per operation, no FMA, source order:
+ *   1. t_m = W_m - c
+ *   2. key(x) = bits(x) & 0x7fffffff;  thr_m = the k[m]-th largest key(t_m[i]) of the tensor;
+ *      tt_m[i] = t_m[i] if key(t_m[i]) >= thr_m (all ties at the threshold are kept), else +0.0
+ *   3. s = ((0 + tt_0) + tt_1) + ...;  the sign is taken by comparison (s > 0, s < 0): -0.0 counts as zero
+ *   4. source m agrees at i iff (s > 0 and tt_m > 0) or (s < 0 and tt_m < 0);  num = sum of the agreeing tt_m from +0.0 in
+ *      source order, cnt = how many agree;  d = num / float(cnt) if cnt > 0 else +0.0
+ *   5. dst = c + lam * d
+ * Non-finite inputs are outside the contract.  dst must not overlap base or a source of its own job (the selection passes re-read
+ * them; vlm_ties_plan_upload rejects a job whose dst byte range meets one of its inputs' -- overlap ACROSS jobs is the caller's to avoid).
+ * k[m] is computed by the caller (1 <= k[m] <= n_elem).
+ */
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each */
+  uint64_t k[VLM_MERGE_MAX_SRC];        /* entries to keep per source (step 2) */
+  uint64_t n_elem;
+  int32_t n_src;
+  float lam;
+} vlm_ties_job_t;
+
+/* What a plan's workspace holds, for callers that read results back: the workspace BEGINS with this header (byte offsets from
+ * its start).  Jobs keep their upload order; the (job, source) pairs ("units") are numbered job-major, source-minor. */
+typedef struct {
+  uint64_t n_jobs, n_units, n_chunks;
+  uint64_t jobs_off;      /* vlm_ties_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table */
+  uint64_t unit0_off;     /* uint32 [n_jobs]: first unit of each job */
+  uint64_t units_off;     /* {uint32 job, uint32 source} [n_units] */
+  uint64_t state_off;     /* vlm_ties_state_t [n_units] */
+  uint64_t counters_off;  /* uint64 [n_jobs][VLM_TIES_COUNTERS] */
+  uint64_t hist_off;      /* uint64 [n_units][2048]: selection histograms, zero between runs */
+} vlm_ties_header_t;
+typedef struct {
+  uint32_t key;       /* after a run: thr_m as a key (= the bits of the threshold magnitude) */
+  uint32_t reserved;
+  uint64_t rank;      /* after a run: 1 + how many of the keys equal to thr_m rank above the k-th place */
+} vlm_ties_state_t;
+/* per job after a run: kept[0 .. MAX_SRC) = entries kept per source (step 2), then `conflict` = elements where the kept sources
+ * hold both a positive and a negative entry, then `empty` = elements with cnt == 0 (step 4) */
+#define VLM_TIES_COUNTERS (VLM_MERGE_MAX_SRC + 2)
+
+/* Bytes of device workspace a TIES plan for n_jobs jobs over total_elems elements needs (jobs, chunk table, selection state,
+ * histograms, counters).  No reference site. */
+size_t vlm_ties_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Build the chunk table on the host, copy header + jobs + tables into `workspace` (16-byte aligned) and zero the histograms.
+ * Like vlm_merge_plan_upload the call SYNCHRONISES `stream` before it returns (pageable temporary source); it is the last
+ * host synchronisation of a plan.  Implements no step of the rule; no reference site. */
+int vlm_ties_plan_upload(const vlm_ties_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: steps 1-2 (three histogram launches over all jobs, 11 + 10 + 10 key bits, each followed by a tiny launch
+ * that picks the bin of the k-th largest key on the device) and steps 1-5 plus the counters (one launch); seven launches, no
+ * host synchronisation.  May be called again on the same workspace and gives the same bytes: the run zeroes its own
+ * histograms and counters on the stream.  One run at a time per workspace.  No reference site. */
+int vlm_ties_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

@@ -28,6 +28,33 @@ class MergeJob(ctypes.Structure):
     ]
 
 
+TIES_COUNTERS = MERGE_MAX_SRC + 2  # VLM_TIES_COUNTERS: kept per source, conflict, empty
+
+
+class TiesJob(ctypes.Structure):
+    """vlm_ties_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("k", c_u64 * MERGE_MAX_SRC),
+        ("n_elem", c_u64),
+        ("n_src", ctypes.c_int32),
+        ("lam", c_float),
+    ]
+
+
+class TiesHeader(ctypes.Structure):
+    """vlm_ties_header_t: the first bytes of a TIES plan's workspace (byte offsets of what a run leaves there)."""
+    _fields_ = [(n, c_u64) for n in ("n_jobs", "n_units", "n_chunks", "jobs_off", "chunks_off", "unit0_off", "units_off",
+                                     "state_off", "counters_off", "hist_off")]
+
+
+class TiesState(ctypes.Structure):
+    """vlm_ties_state_t."""
+    _fields_ = [("key", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("rank", c_u64)]
+
+
 class ScatterSrc(ctypes.Structure):
     """vlm_scatter_src_t of include/vlm_hip.h."""
     _fields_ = [("g", c_void_p), ("g_is_f32", ctypes.c_int32), ("ld", ctypes.c_int32), ("first_row", ctypes.c_int32),
@@ -114,6 +141,9 @@ SIGNATURES = {
     "vlm_merge_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_merge_plan_upload": (c_int, [ctypes.POINTER(MergeJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_merge_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_ties_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_ties_plan_upload": (c_int, [ctypes.POINTER(TiesJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_ties_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_bf16_grouped": (c_int, [c_int, ctypes.POINTER(GemmGroup), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

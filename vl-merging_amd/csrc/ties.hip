@@ -1,0 +1,483 @@
+// TIES merge (trim, elect sign, disjoint mean; Yadav et al. 2023) over every output tensor of an all_moe -> ufo merge.
+// No reference site: the reference repository has no TIES.  The rule is written down in include/vlm_hip.h and restated in
+// numpy by tests/ties_restatement.py; the kernels are held to that restatement bit for bit.
+//
+// Trim needs, per (tensor, source), the K-th largest magnitude of the task vector t_m = W_m - c.  It is found exactly, on
+// the device, by a radix select over key(x) = bits(x) & 0x7fffffff in three passes of 11 + 10 + 10 bits:
+//   vlm_ties_hist_kernel<PASS>  one launch over the plan's 16-KiB chunk table (the chunk idea of merge.hip).  A workgroup owns a
+//                               CONTIGUOUS run of chunks, recomputes t_m from W_m and c (16-B non-temporal loads; the task vectors
+//                               are never stored), counts the digit of every key that still matches the prefix found so far in
+//                               LDS histograms (integer LDS atomics) and adds the non-empty bins to the (job, source) histogram in
+//                               global memory (64-bit integer atomics) when its run leaves a job.
+//   vlm_ties_scan_kernel<PASS>  a tiny launch: per (job, source) walks the histogram from the top bin down, picks the bin that holds
+//                               the K-th largest key, extends the prefix, keeps the rank left inside that bin, and ZEROES the
+//                               histogram for the next pass / the next run.
+//   vlm_ties_apply_kernel       steps 1-5 of the rule with the thresholds read from the workspace, and the per-job counters.
+// Integer counters only, so nothing depends on the order workgroups run in.  HBM-bound: every pass streams 4 (S + 1) B per
+// element; the apply pass also writes 4 B.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
+#include "vlm_common.h"
+#include <string.h>
+#include <vector>
+
+#define TIES_CHUNK 4096u  // floats per chunk: 256 threads x 4 float4
+#define TIES_THREADS 256
+#define TIES_BINS 2048u           // bins per source in LDS and in global memory (pass 0 uses all, passes 1 and 2 use 1024)
+#define TIES_FLUSH_CHUNKS (1u << 19)  // 2^19 chunks x 4096 keys < 2^32: the 32-bit LDS bins cannot wrap between flushes
+#define TIES_HIST_BLOCKS_PER_CU 4  // 110 VGPRs: four workgroups (one wave per SIMD each) are resident per CU; 32 KiB LDS each
+#define TIES_APPLY_BLOCKS_PER_CU 12  // three resident per CU (145 VGPRs): four even rounds
+#define TIES_SCAN_BLOCKS 1024
+// The three grid sizes above follow from the kernels' resident-workgroup counts (register and LDS use recorded by the build); none of
+// them has been A/B-measured against other values (docs/experiments.md, "TIES merge").
+
+typedef unsigned long long u64_t;
+
+struct ties_chunk_t {
+  uint32_t job;
+  uint32_t start4;  // chunk start / 4 (float4 units)
+};
+struct ties_unit_t {  // one (job, source) pair
+  uint32_t job;
+  uint32_t m;
+};
+
+template <int PASS>
+__device__ __forceinline__ constexpr uint32_t ties_bins() { return PASS == 0 ? 2048u : 1024u; }
+template <int PASS>
+__device__ __forceinline__ constexpr int ties_shift() { return PASS == 0 ? 20 : (PASS == 1 ? 10 : 0); }
+
+__device__ __forceinline__ uint32_t ties_key(float w, float c) { return __float_as_uint(__fsub_rn(w, c)) & 0x7fffffffu; }
+
+template <int PASS>
+__device__ __forceinline__ void ties_bin(uint32_t key, uint32_t prefix, uint32_t* h) {
+  if (PASS == 0) atomicAdd(&h[key >> 20], 1u);
+  else if (PASS == 1) { if ((key >> 20) == (prefix >> 20)) atomicAdd(&h[(key >> 10) & 1023u], 1u); }
+  else { if ((key >> 10) == (prefix >> 10)) atomicAdd(&h[key & 1023u], 1u); }
+}
+
+template <int PASS, int NSRC>
+__device__ __forceinline__ void ties_hist_vec(const vlm_ties_job_t& j, const uint32_t* prefix, uint64_t start4, uint64_t n4,
+                                              uint32_t* lds) {
+  const f32x4* __restrict__ base = reinterpret_cast<const f32x4*>(j.base);
+  const f32x4* __restrict__ s[NSRC];
+#pragma unroll
+  for (int m = 0; m < NSRC; ++m) s[m] = reinterpret_cast<const f32x4*>(j.src[m]);
+  f32x4 v[4][NSRC];
+  f32x4 b[4];
+  uint64_t idx[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    idx[u] = start4 + threadIdx.x + u * TIES_THREADS;
+    if (idx[u] < n4) {
+#pragma unroll
+      for (int m = 0; m < NSRC; ++m) v[u][m] = __builtin_nontemporal_load(&s[m][idx[u]]);
+      b[u] = __builtin_nontemporal_load(&base[idx[u]]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    if (idx[u] < n4) {
+#pragma unroll
+      for (int m = 0; m < NSRC; ++m)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ties_bin<PASS>(ties_key(v[u][m][c], b[u][c]), prefix[m], lds + m * TIES_BINS);
+    }
+  }
+}
+
+struct ties_view_t {
+  const vlm_ties_header_t* hdr;
+  const vlm_ties_job_t* jobs;
+  const ties_chunk_t* chunks;
+  const uint32_t* unit0;
+  const ties_unit_t* units;
+  vlm_ties_state_t* state;
+  u64_t* hist;
+  u64_t* counters;
+};
+
+__device__ __forceinline__ ties_view_t ties_view(unsigned char* ws) {
+  ties_view_t v;
+  v.hdr = reinterpret_cast<const vlm_ties_header_t*>(ws);
+  v.jobs = reinterpret_cast<const vlm_ties_job_t*>(ws + v.hdr->jobs_off);
+  v.chunks = reinterpret_cast<const ties_chunk_t*>(ws + v.hdr->chunks_off);
+  v.unit0 = reinterpret_cast<const uint32_t*>(ws + v.hdr->unit0_off);
+  v.units = reinterpret_cast<const ties_unit_t*>(ws + v.hdr->units_off);
+  v.state = reinterpret_cast<vlm_ties_state_t*>(ws + v.hdr->state_off);
+  v.hist = reinterpret_cast<u64_t*>(ws + v.hdr->hist_off);
+  v.counters = reinterpret_cast<u64_t*>(ws + v.hdr->counters_off);
+  return v;
+}
+
+// the contiguous run of chunks this workgroup owns
+__device__ __forceinline__ void ties_my_chunks(uint64_t n_chunks, uint64_t* c0, uint64_t* c1) {
+  const uint64_t per = (n_chunks + gridDim.x - 1) / gridDim.x;
+  *c0 = (uint64_t)blockIdx.x * per;
+  uint64_t e = *c0 + per;
+  *c1 = e < n_chunks ? e : n_chunks;
+}
+
+template <int PASS>
+__device__ __forceinline__ void ties_flush(uint32_t* lds, u64_t* hist, int n_src) {
+  __syncthreads();  // every LDS atomic of the run has landed
+  for (int m = 0; m < n_src; ++m)
+    for (uint32_t i = threadIdx.x; i < ties_bins<PASS>(); i += TIES_THREADS) {
+      const uint32_t cnt = lds[m * TIES_BINS + i];
+      if (cnt) {
+        __hip_atomic_fetch_add(&hist[(uint64_t)m * TIES_BINS + i], (u64_t)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        lds[m * TIES_BINS + i] = 0;
+      }
+    }
+  __syncthreads();
+}
+
+template <int PASS>
+__global__ __launch_bounds__(TIES_THREADS) void vlm_ties_hist_kernel(unsigned char* __restrict__ ws) {
+  __shared__ uint32_t lds[VLM_MERGE_MAX_SRC * TIES_BINS];
+  const ties_view_t w = ties_view(ws);
+  uint64_t c0, c1;
+  ties_my_chunks(w.hdr->n_chunks, &c0, &c1);
+  if (c0 >= c1) return;
+  for (uint32_t i = threadIdx.x; i < VLM_MERGE_MAX_SRC * TIES_BINS; i += TIES_THREADS) lds[i] = 0;
+  __syncthreads();
+  uint32_t cur = 0xffffffffu, since = 0;
+  uint32_t prefix[VLM_MERGE_MAX_SRC] = {0, 0, 0, 0};
+  for (uint64_t c = c0; c < c1; ++c) {
+    const ties_chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
+    if (ck.job != cur || since >= TIES_FLUSH_CHUNKS) {
+      if (cur != 0xffffffffu) ties_flush<PASS>(lds, w.hist + (uint64_t)w.unit0[cur] * TIES_BINS, w.jobs[cur].n_src);
+      cur = ck.job;
+      since = 0;
+      if (PASS > 0) {
+#pragma unroll
+        for (int m = 0; m < VLM_MERGE_MAX_SRC; ++m)
+          if (m < w.jobs[cur].n_src) prefix[m] = w.state[w.unit0[cur] + m].key;
+      }
+    }
+    ++since;
+    const vlm_ties_job_t& j = w.jobs[cur];
+    const uint64_t n4 = j.n_elem >> 2;
+    const uint64_t start4 = ck.start4;
+    switch (j.n_src) {
+      case 1: ties_hist_vec<PASS, 1>(j, prefix, start4, n4, lds); break;
+      case 2: ties_hist_vec<PASS, 2>(j, prefix, start4, n4, lds); break;
+      case 3: ties_hist_vec<PASS, 3>(j, prefix, start4, n4, lds); break;
+      default: ties_hist_vec<PASS, 4>(j, prefix, start4, n4, lds); break;
+    }
+    // ragged tail (n_elem % 4) belongs to the chunk that holds the last float4 (or chunk 0 of a tiny job), as in merge.hip
+    const uint64_t tail0 = n4 << 2;
+    const bool last = (start4 + (TIES_CHUNK / 4) >= n4);
+    if (last && threadIdx.x < (j.n_elem - tail0)) {
+      const uint64_t i = tail0 + threadIdx.x;
+      const float b = reinterpret_cast<const float*>(j.base)[i];
+      for (int m = 0; m < j.n_src; ++m)
+        ties_bin<PASS>(ties_key(reinterpret_cast<const float*>(j.src[m])[i], b), prefix[m], lds + m * TIES_BINS);
+    }
+  }
+  ties_flush<PASS>(lds, w.hist + (uint64_t)w.unit0[cur] * TIES_BINS, w.jobs[cur].n_src);
+}
+
+// One workgroup per (job, source): find the bin that holds the rank-th largest key, walking down from the top bin.
+template <int PASS>
+__global__ __launch_bounds__(TIES_THREADS) void vlm_ties_scan_kernel(unsigned char* __restrict__ ws) {
+  constexpr int PER = ties_bins<PASS>() / TIES_THREADS;  // bins per thread: 8 or 4
+  __shared__ u64_t part[TIES_THREADS];
+  __shared__ u64_t sel_before;
+  __shared__ int sel;
+  const ties_view_t w = ties_view(ws);
+  const uint32_t n_units = w.hdr->n_units;
+  for (uint32_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+    const ties_unit_t uj = w.units[unit];
+    u64_t* h = w.hist + (uint64_t)unit * TIES_BINS;
+    const u64_t rank = PASS == 0 ? w.jobs[uj.job].k[uj.m] : w.state[unit].rank;
+    const uint32_t prefix = PASS == 0 ? 0u : w.state[unit].key;
+    if (PASS == 0 && uj.m == 0 && threadIdx.x < VLM_TIES_COUNTERS)  // the counters of the job start every run at zero
+      w.counters[(uint64_t)uj.job * VLM_TIES_COUNTERS + threadIdx.x] = 0;
+    // thread t owns bins hi, hi-1, ..., hi-PER+1 with hi = BINS-1 - t*PER: thread order is descending key order
+    const int hi = (int)ties_bins<PASS>() - 1 - (int)threadIdx.x * PER;
+    u64_t local[PER];
+    u64_t sum = 0;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      local[q] = h[hi - q];
+      h[hi - q] = 0;  // ready for the next pass and the next run
+      sum += local[q];
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      u64_t cum = 0;
+      int t = 0;
+      for (; t < TIES_THREADS - 1; ++t) {
+        if (cum + part[t] >= rank) break;
+        cum += part[t];
+      }
+      sel = t;
+      sel_before = cum;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x == sel) {
+      u64_t cum = sel_before;
+      int q = 0;
+      for (; q < PER - 1; ++q) {
+        if (cum + local[q] >= rank) break;
+        cum += local[q];
+      }
+      vlm_ties_state_t st;
+      st.key = prefix | ((uint32_t)(hi - q) << ties_shift<PASS>());
+      st.reserved = 0;
+      st.rank = rank - cum;
+      w.state[unit] = st;
+    }
+    __syncthreads();
+  }
+}
+
+struct ties_counts_t {
+  uint32_t c[VLM_TIES_COUNTERS];  // kept[0..3], conflict, empty
+};
+
+template <int NSRC>
+__device__ __forceinline__ float ties_elem(float c, const float* wv, const uint32_t* thr, float lam, ties_counts_t& n) {
+  float tt[NSRC];
+  float s = 0.0f;
+  bool has_pos = false, has_neg = false;
+#pragma unroll
+  for (int m = 0; m < NSRC; ++m) {
+    const float t = __fsub_rn(wv[m], c);                                 // step 1
+    const bool kept = (__float_as_uint(t) & 0x7fffffffu) >= thr[m];      // step 2
+    tt[m] = kept ? t : 0.0f;
+    n.c[m] += kept ? 1u : 0u;
+    s = __fadd_rn(s, tt[m]);                                             // step 3
+    has_pos |= tt[m] > 0.0f;
+    has_neg |= tt[m] < 0.0f;
+  }
+  float num = 0.0f;
+  int cnt = 0;
+#pragma unroll
+  for (int m = 0; m < NSRC; ++m) {                                       // step 4
+    const bool agree = (s > 0.0f && tt[m] > 0.0f) || (s < 0.0f && tt[m] < 0.0f);
+    if (agree) {
+      num = __fadd_rn(num, tt[m]);
+      ++cnt;
+    }
+  }
+  const float d = cnt > 0 ? __fdiv_rn(num, (float)cnt) : 0.0f;
+  n.c[VLM_MERGE_MAX_SRC] += (has_pos && has_neg) ? 1u : 0u;
+  n.c[VLM_MERGE_MAX_SRC + 1] += cnt == 0 ? 1u : 0u;
+  return __fadd_rn(c, __fmul_rn(lam, d));                                // step 5
+}
+
+template <int NSRC>
+__device__ __forceinline__ void ties_apply_vec(const vlm_ties_job_t& j, const uint32_t* thr, uint64_t start4, uint64_t n4,
+                                               ties_counts_t& n) {
+  f32x4* __restrict__ dst = reinterpret_cast<f32x4*>(j.dst);
+  const f32x4* __restrict__ base = reinterpret_cast<const f32x4*>(j.base);
+  const f32x4* __restrict__ s[NSRC];
+#pragma unroll
+  for (int m = 0; m < NSRC; ++m) s[m] = reinterpret_cast<const f32x4*>(j.src[m]);
+  const float lam = j.lam;
+  f32x4 v[4][NSRC];
+  f32x4 b[4];
+  uint64_t idx[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    idx[u] = start4 + threadIdx.x + u * TIES_THREADS;
+    if (idx[u] < n4) {
+#pragma unroll
+      for (int m = 0; m < NSRC; ++m) v[u][m] = __builtin_nontemporal_load(&s[m][idx[u]]);
+      b[u] = __builtin_nontemporal_load(&base[idx[u]]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    if (idx[u] < n4) {
+      f32x4 o;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float wv[NSRC];
+#pragma unroll
+        for (int m = 0; m < NSRC; ++m) wv[m] = v[u][m][c];
+        o[c] = ties_elem<NSRC>(b[u][c], wv, thr, lam, n);
+      }
+      __builtin_nontemporal_store(o, &dst[idx[u]]);
+    }
+  }
+}
+
+template <int NSRC>
+__device__ __forceinline__ void ties_apply_tail(const vlm_ties_job_t& j, const uint32_t* thr, uint64_t i, ties_counts_t& n) {
+  float wv[NSRC];
+#pragma unroll
+  for (int m = 0; m < NSRC; ++m) wv[m] = reinterpret_cast<const float*>(j.src[m])[i];
+  reinterpret_cast<float*>(j.dst)[i] = ties_elem<NSRC>(reinterpret_cast<const float*>(j.base)[i], wv, thr, j.lam, n);
+}
+
+// in-workgroup reduction of the six counters, then one 64-bit atomic per counter
+__device__ __forceinline__ void ties_flush_counts(ties_counts_t& n, u64_t* red, u64_t* counters) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < VLM_TIES_COUNTERS; ++k) {
+    uint32_t v = n.c[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) red[wave * VLM_TIES_COUNTERS + k] = v;
+    n.c[k] = 0;
+  }
+  __syncthreads();
+  if (threadIdx.x < VLM_TIES_COUNTERS) {
+    u64_t t = 0;
+    for (int wv = 0; wv < TIES_THREADS / 64; ++wv) t += red[wv * VLM_TIES_COUNTERS + threadIdx.x];
+    if (t) __hip_atomic_fetch_add(&counters[threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(TIES_THREADS) void vlm_ties_apply_kernel(unsigned char* __restrict__ ws) {
+  __shared__ u64_t red[(TIES_THREADS / 64) * VLM_TIES_COUNTERS];
+  const ties_view_t w = ties_view(ws);
+  uint64_t c0, c1;
+  ties_my_chunks(w.hdr->n_chunks, &c0, &c1);
+  if (c0 >= c1) return;
+  ties_counts_t n;
+#pragma unroll
+  for (int k = 0; k < VLM_TIES_COUNTERS; ++k) n.c[k] = 0;
+  uint32_t cur = 0xffffffffu, since = 0;
+  uint32_t thr[VLM_MERGE_MAX_SRC] = {0, 0, 0, 0};
+  for (uint64_t c = c0; c < c1; ++c) {
+    const ties_chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
+    if (ck.job != cur || since >= TIES_FLUSH_CHUNKS) {
+      if (cur != 0xffffffffu) ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS);
+      cur = ck.job;
+      since = 0;
+#pragma unroll
+      for (int m = 0; m < VLM_MERGE_MAX_SRC; ++m)
+        if (m < w.jobs[cur].n_src) thr[m] = w.state[w.unit0[cur] + m].key;
+    }
+    ++since;
+    const vlm_ties_job_t& j = w.jobs[cur];
+    const uint64_t n4 = j.n_elem >> 2;
+    const uint64_t start4 = ck.start4;
+    const uint64_t tail0 = n4 << 2;
+    const bool tail = (start4 + (TIES_CHUNK / 4) >= n4) && threadIdx.x < (j.n_elem - tail0);
+    const uint64_t ti = tail0 + threadIdx.x;
+    switch (j.n_src) {
+      case 1: ties_apply_vec<1>(j, thr, start4, n4, n); if (tail) ties_apply_tail<1>(j, thr, ti, n); break;
+      case 2: ties_apply_vec<2>(j, thr, start4, n4, n); if (tail) ties_apply_tail<2>(j, thr, ti, n); break;
+      case 3: ties_apply_vec<3>(j, thr, start4, n4, n); if (tail) ties_apply_tail<3>(j, thr, ti, n); break;
+      default: ties_apply_vec<4>(j, thr, start4, n4, n); if (tail) ties_apply_tail<4>(j, thr, ti, n); break;
+    }
+  }
+  ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS);
+}
+
+static inline size_t ties_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+static uint64_t ties_chunks_of(uint64_t n_elem) {
+  uint64_t n4 = n_elem >> 2;
+  uint64_t c = (n4 + TIES_CHUNK / 4 - 1) / (TIES_CHUNK / 4);
+  return c == 0 ? 1 : c;  // a job shorter than 4 floats still needs its tail chunk
+}
+
+// fills every offset of `h` for n_jobs jobs, n_units (job, source) pairs and n_chunks chunks; returns the total size
+static size_t ties_layout(vlm_ties_header_t* h, uint64_t n_jobs, uint64_t n_units, uint64_t n_chunks) {
+  h->n_jobs = n_jobs;
+  h->n_units = n_units;
+  h->n_chunks = n_chunks;
+  size_t off = ties_align_up(sizeof(vlm_ties_header_t), 256);
+  h->jobs_off = off;     off += ties_align_up(n_jobs * sizeof(vlm_ties_job_t), 256);
+  h->chunks_off = off;   off += ties_align_up(n_chunks * sizeof(ties_chunk_t), 256);
+  h->unit0_off = off;    off += ties_align_up(n_jobs * sizeof(uint32_t), 256);
+  h->units_off = off;    off += ties_align_up(n_units * sizeof(ties_unit_t), 256);
+  h->state_off = off;    off += ties_align_up(n_units * sizeof(vlm_ties_state_t), 256);
+  h->counters_off = off; off += ties_align_up(n_jobs * VLM_TIES_COUNTERS * sizeof(uint64_t), 256);
+  h->hist_off = off;     off += ties_align_up(n_units * TIES_BINS * sizeof(uint64_t), 256);
+  return off;
+}
+
+extern "C" size_t vlm_ties_plan_bytes(int n_jobs, uint64_t total_elems) {
+  if (n_jobs < 0) return 0;
+  // upper bounds: every job may add one partial chunk and has at most VLM_MERGE_MAX_SRC sources
+  vlm_ties_header_t h;
+  return ties_layout(&h, (uint64_t)n_jobs, (uint64_t)n_jobs * VLM_MERGE_MAX_SRC,
+                     total_elems / TIES_CHUNK + 2ull * (uint64_t)n_jobs + 1);
+}
+
+// do the byte ranges [a, a + 4 n) and [b, b + 4 n) meet?  (dst may not overlap an input: the selection passes re-read the inputs)
+static bool ties_overlap(const void* a, const void* b, uint64_t n_elem) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  const uint64_t bytes = n_elem * 4;
+  return x < y ? (y - x) < bytes : (x - y) < bytes;
+}
+
+extern "C" int vlm_ties_plan_upload(const vlm_ties_job_t* jobs, int n_jobs, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  if (!jobs || n_jobs <= 0 || !workspace || ((uintptr_t)workspace & 15)) return VLM_ERR_ARG;
+  uint64_t n_chunks = 0, n_units = 0;
+  for (int i = 0; i < n_jobs; ++i) {
+    const vlm_ties_job_t& j = jobs[i];
+    if (j.n_src < 1 || j.n_src > VLM_MERGE_MAX_SRC || !j.dst || !j.base || j.n_elem == 0) return VLM_ERR_ARG;
+    if ((j.n_elem >> 2) >= (1ull << 32)) return VLM_ERR_UNSUPPORTED;  // before the byte ranges are formed
+    if (((uintptr_t)j.dst & 15) || ((uintptr_t)j.base & 15) || ties_overlap(j.dst, j.base, j.n_elem)) return VLM_ERR_ARG;
+    for (int m = 0; m < j.n_src; ++m) {
+      if (!j.src[m] || ((uintptr_t)j.src[m] & 15) || ties_overlap(j.dst, j.src[m], j.n_elem)) return VLM_ERR_ARG;
+      if (j.k[m] < 1 || j.k[m] > j.n_elem) return VLM_ERR_ARG;
+    }
+    n_chunks += ties_chunks_of(j.n_elem);
+    n_units += (uint64_t)j.n_src;
+  }
+  if (n_chunks >= (1ull << 32) || n_units >= (1ull << 32)) return VLM_ERR_UNSUPPORTED;
+  vlm_ties_header_t hdr;
+  const size_t total = ties_layout(&hdr, (uint64_t)n_jobs, n_units, n_chunks);
+  if (total > workspace_bytes) return VLM_ERR_WORKSPACE;
+  // the host image ends where the state begins: state, counters and histograms are device-made
+  const size_t img_bytes = hdr.state_off;
+  std::vector<unsigned char> img(img_bytes, 0);
+  memcpy(img.data(), &hdr, sizeof(hdr));
+  memcpy(img.data() + hdr.jobs_off, jobs, (size_t)n_jobs * sizeof(vlm_ties_job_t));
+  ties_chunk_t* ck = reinterpret_cast<ties_chunk_t*>(img.data() + hdr.chunks_off);
+  uint32_t* unit0 = reinterpret_cast<uint32_t*>(img.data() + hdr.unit0_off);
+  ties_unit_t* units = reinterpret_cast<ties_unit_t*>(img.data() + hdr.units_off);
+  uint64_t c = 0, u = 0;
+  for (int i = 0; i < n_jobs; ++i) {  // job order: a workgroup's run of chunks stays inside few jobs
+    const uint64_t nc = ties_chunks_of(jobs[i].n_elem);
+    for (uint64_t k = 0; k < nc; ++k) {
+      ck[c].job = (uint32_t)i;
+      ck[c].start4 = (uint32_t)(k * (TIES_CHUNK / 4));
+      ++c;
+    }
+    unit0[i] = (uint32_t)u;
+    for (int m = 0; m < jobs[i].n_src; ++m) {
+      units[u].job = (uint32_t)i;
+      units[u].m = (uint32_t)m;
+      ++u;
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  if (hipMemcpyAsync(ws, img.data(), img_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return VLM_ERR_LAUNCH;
+  // the histograms start at zero; every scan launch leaves them at zero again
+  if (hipMemsetAsync(ws + hdr.state_off, 0, total - hdr.state_off, s) != hipSuccess) return VLM_ERR_LAUNCH;
+  // pageable temporary source: the copy is waited for before `img` dies (this call synchronises the stream, as vlm_merge_plan_upload)
+  if (hipStreamSynchronize(s) != hipSuccess) return VLM_ERR_LAUNCH;
+  return VLM_OK;
+}
+
+extern "C" int vlm_ties_run(void* workspace, void* stream) {
+  if (!workspace) return VLM_ERR_ARG;
+  int cus = vlm_device_cus();
+  if (cus <= 0) cus = 256;
+  unsigned char* ws = (unsigned char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 block(TIES_THREADS), hist_grid(cus * TIES_HIST_BLOCKS_PER_CU), scan_grid(TIES_SCAN_BLOCKS),
+      apply_grid(cus * TIES_APPLY_BLOCKS_PER_CU);
+  // seven launches, stream-ordered, no host synchronisation: the sizes of the plan live in the workspace header
+  hipLaunchKernelGGL((vlm_ties_hist_kernel<0>), hist_grid, block, 0, s, ws);
+  hipLaunchKernelGGL((vlm_ties_scan_kernel<0>), scan_grid, block, 0, s, ws);
+  hipLaunchKernelGGL((vlm_ties_hist_kernel<1>), hist_grid, block, 0, s, ws);
+  hipLaunchKernelGGL((vlm_ties_scan_kernel<1>), scan_grid, block, 0, s, ws);
+  hipLaunchKernelGGL((vlm_ties_hist_kernel<2>), hist_grid, block, 0, s, ws);
+  hipLaunchKernelGGL((vlm_ties_scan_kernel<2>), scan_grid, block, 0, s, ws);
+  hipLaunchKernelGGL(vlm_ties_apply_kernel, apply_grid, block, 0, s, ws);
+  VLM_CHECK_LAUNCH();
+  return VLM_OK;
+}

@@ -1,12 +1,18 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean.
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
 (reference src/vilt/modules/vilt_module.py:533-638, :640-746, :366-531): same `state_dict -> state_dict`
 contract, same key grammar, same pass-through-by-identity of non-block keys, same "already merged key
 passes through" and KeyError behaviour; the per-element arithmetic of all 156 output tensors runs in ONE
 launch of the HIP merge kernel (csrc/merge.hip) and is bit-exact with the reference's CPU result.
+
+ties_merge (TIES-merging, Yadav et al. 2023) has NO reference site: the reference has no TIES.  It takes what sum_task_vectors
+takes and follows its dictionary logic; its arithmetic (include/vlm_hip.h, csrc/ties.hip) is pinned to a numpy restatement of
+the rule (tests/ties_restatement.py), not to the reference.
 """
 import ctypes
+import math
+import struct
 from typing import Dict, List, Optional
 
 import torch
@@ -191,4 +197,140 @@ def sum_task_vectors(state_dict, config, central_weight=None, device="cuda", pla
         plan.run()
     if plan_out is not None:
         plan_out.append(plan)
+    return out
+
+
+def ties_keep_count(density, n):
+    """K of the trim step: max(1, min(n, ceil(density * n))) in python doubles."""
+    if not (0.0 < density <= 1.0):  # also rejects NaN
+        raise ValueError("TIES density must lie in (0, 1], got %r" % (density,))
+    return max(1, min(n, math.ceil(density * n)))
+
+
+class TiesPlan:
+    """A device-resident job table for csrc/ties.hip; build once, run() enqueues the seven launches of a TIES merge (three
+    histogram passes of the radix select, a bin pick after each, the apply pass) without a host synchronisation."""
+
+    PASSES = 4  # three selection passes + the apply pass: each streams every source and the central tensor once
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.VlmError("the TIES kernels run on the GPU only (got device %s)" % device)
+        self.jobs: List[L.TiesJob] = []
+        self.names: List[Optional[str]] = []
+        self.keep = []  # keeps staged tensors alive
+        self.total = 0
+        self.bytes_read = 0
+        self.bytes_written = 0
+        self.ws = None
+
+    _dev = MergePlan._dev
+
+    def add(self, srcs, base, density=None, lam=1.0, keep=None, name=None):
+        """One output tensor.  `density` gives K for every source (ties_keep_count); `keep` = explicit K per source instead."""
+        srcs = [self._dev(s) for s in srcs]
+        if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
+            raise L.VlmError("a TIES job takes 1 .. %d sources, got %d" % (L.MERGE_MAX_SRC, len(srcs)))
+        n = srcs[0].numel()
+        b = self._dev(base)
+        for s in srcs + [b]:
+            if s.shape != srcs[0].shape:
+                raise L.VlmError("merge sources disagree in shape: %s vs %s" % (s.shape, srcs[0].shape))
+        if keep is None:
+            keep = [ties_keep_count(density, n)] * len(srcs)
+        out = torch.empty_like(srcs[0])
+        self.keep.append(out)
+        job = L.TiesJob()
+        job.dst = out.data_ptr()
+        job.base = b.data_ptr()
+        for k, s in enumerate(srcs):
+            job.src[k] = s.data_ptr()
+            job.k[k] = int(keep[k])
+        job.n_src = len(srcs)
+        job.n_elem = n
+        job.lam = float(lam)
+        self.jobs.append(job)
+        self.names.append(name)
+        self.total += n
+        # what the passes move: every pass re-reads the sources and the central tensor (the task vectors are never stored);
+        # the histograms, thresholds and counters (16 KiB per source and tensor) are not counted
+        self.bytes_read += self.PASSES * 4 * n * (len(srcs) + 1)
+        self.bytes_written += 4 * n
+        return out
+
+    def upload(self):
+        lib = L.get_lib()
+        n = len(self.jobs)
+        arr = (L.TiesJob * n)(*self.jobs)
+        nbytes = lib.vlm_ties_plan_bytes(n, self.total)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(lib.vlm_ties_plan_upload(arr, n, L.ptr(self.ws), nbytes, L.stream_ptr()), "vlm_ties_plan_upload")
+        return self
+
+    def run(self):
+        if self.ws is None:
+            self.upload()
+        with torch.cuda.device(self.device):
+            L.check(L.get_lib().vlm_ties_run(L.ptr(self.ws), L.stream_ptr()), "vlm_ties_run")
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): the threshold per source as a float and as its key, how many
+        entries each source kept, the elements whose kept entries disagree in sign, the elements no source contributes to."""
+        if self.ws is None:
+            raise L.VlmError("TiesPlan.report() needs a plan that has run")
+        hdr = L.TiesHeader.from_buffer_copy(self.ws[: ctypes.sizeof(L.TiesHeader)].cpu().numpy().tobytes())
+        state = self.ws[hdr.state_off: hdr.state_off + 16 * hdr.n_units].cpu().numpy().view("<u4").reshape(-1, 4)
+        counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * L.TIES_COUNTERS * hdr.n_jobs].cpu().numpy()
+        counters = counters.view("<u8").reshape(-1, L.TIES_COUNTERS)
+        rows, unit = [], 0
+        for i, job in enumerate(self.jobs):
+            S = job.n_src
+            keys = [int(state[unit + m, 0]) for m in range(S)]
+            rows.append({"dst": self.names[i], "n": int(job.n_elem), "K": [int(job.k[m]) for m in range(S)],
+                         "threshold": [struct.unpack("<f", struct.pack("<I", k))[0] for k in keys], "threshold_bits": keys,
+                         "kept": [int(counters[i, m]) for m in range(S)],
+                         "conflict": int(counters[i, L.MERGE_MAX_SRC]), "empty": int(counters[i, L.MERGE_MAX_SRC + 1])})
+            unit += S
+        return rows
+
+
+def ties_merge(state_dict, config, central_weight=None, density=0.2, lam=None, device="cuda", plan_out: Optional[list] = None,
+               report_out: Optional[list] = None):
+    """TIES merge of the modality experts' task vectors `W_m - central` (no reference site; the rule: include/vlm_hip.h).
+    Same inputs, keys, pass-through and KeyError behaviour as sum_task_vectors; `lam=None` takes config["sum_lambda"].
+    Trimming is per tensor.  A layer with ONE source is not trimmed: it is the task-vector job with ratio 1 that
+    sum_task_vectors issues for it.  `plan_out` receives the TiesPlan FIRST whenever a layer has several sources, then the MergePlan of the single-source layers if
+    there are any (the order is part of the contract: callers index [0] for the TiesPlan);
+    `report_out` receives TiesPlan.report() (reading it back synchronises)."""
+    ties_keep_count(density, 1)  # ValueError before any device work
+    if lam is None:
+        lam = config["sum_lambda"]
+    plan = TiesPlan(device)
+    single = MergePlan(device)
+    out = _passthrough(state_dict)
+    if central_weight is None:
+        from . import checkpoint
+        central_weight = checkpoint.load_file(config["central_weight"])
+    if "state_dict" in central_weight:
+        central_weight = central_weight["state_dict"]
+    for i in range(NUM_MERGE_LAYERS):
+        mods = modalities_for_layer(config, i)
+        for src, dst in _tensor_names(i):
+            central = central_weight[dst]
+            srcs, through = _collect(state_dict, src, dst, mods)
+            if srcs is None:
+                out[dst] = through
+            elif len(mods) == 1:
+                out[dst] = single.add(L.MERGE_TASKVEC, [t for _, t in srcs], [1], base=central)
+            else:
+                out[dst] = plan.add([t for _, t in srcs], central, density=density, lam=lam, name=dst)
+    for p in (plan, single):
+        if p.jobs:
+            p.run()
+            if plan_out is not None:
+                plan_out.append(p)
+    if report_out is not None:
+        report_out.extend(plan.report() if plan.jobs else [])
     return out

@@ -275,6 +275,11 @@ class ViLTransformerSS(nn.Module):
     def sum_task_vectors(self, state_dict):
         return merge_ops.sum_task_vectors(state_dict, self.hparams.config, device=self._merge_device())
 
+    def ties_merge(self, state_dict, density=0.2, lam=None):
+        """TIES merge of the experts' task vectors (no reference site; merge.ties_merge).  Same contract as sum_task_vectors;
+        not wired to a config key and not called from __init__."""
+        return merge_ops.ties_merge(state_dict, self.hparams.config, density=density, lam=lam, device=self._merge_device())
+
     def regmean(self, state_dict):
         return regmean_ops.regmean(state_dict, self.hparams.config, device=self._merge_device())
 

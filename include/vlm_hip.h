@@ -7,9 +7,9 @@
  *   - every call is stream-ordered on `stream` (a hipStream_t passed as void*), re-entrant, allocates
  *     nothing: the caller owns outputs and workspaces;
  *   - return 0 on success, a negative VLM_ERR_* otherwise; nothing throws across the boundary;
- *   - process-wide state is limited to (1) diagnostic switches read ONCE from the environment at first use
- *     (VLM_GEMM_CUS, VLM_MERGE_VARIANT: thread-safe function-local statics,
- *     immutable afterwards) and (2) the hooks vlm_gemm_set_big_tile_mode and vlm_set_cu_budget (one atomic int each).  None changes results
+ *   - process-wide state is limited to (1) the diagnostic switch VLM_GEMM_CUS, read ONCE from the environment at first use
+ *     (a thread-safe function-local static, immutable afterwards; the merge kernel's grid and cache policy are fixed:
+ *     docs/experiments.md, "Merge kernel: grid and cache policy") and (2) the hooks vlm_gemm_set_big_tile_mode and vlm_set_cu_budget (one atomic int each).  None changes results
  *     beyond the fp32 summation order of a GEMM or of the bias-table gradient.
  *
  * Token layout ("segment-major"): a pass over B samples with n0 text and n1 image tokens per sample keeps

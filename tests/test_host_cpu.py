@@ -365,3 +365,24 @@ def test_attention_bwd_workspace_size(pkg):
     # SEPARATE looks at each part alone: 40 text + 1 000 image positions fit, the same 1 040 joint positions do not
     assert size(1, 40, 1000, 1, L.ATTN_SEPARATE)[0] == 1040
     assert size(1, 40, 1000, 1, L.ATTN_JOINT)[0] == 3 * 1040
+
+
+def test_merge_variant_switch_is_retired():
+    """The merge kernel's measurement switch and its sweep tool are gone (the sweep is recorded in docs/experiments.md): no
+    source file under vl-merging_amd/, tools/ or include/ reads or names either.  Documents may."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    words = ("VLM_MERGE_VARIANT", "bench_merge_variants")
+    hits = []
+    for top in ("vl-merging_amd", "tools", "include"):
+        for d, dirs, files in os.walk(os.path.join(root, top)):
+            dirs[:] = [x for x in dirs if x not in ("_build", "__pycache__", "lib")]
+            for f in files:
+                if f.endswith((".md", ".rst", ".txt", ".pyc", ".so", ".o")):
+                    continue
+                path = os.path.join(d, f)
+                with open(path, "rb") as fh:
+                    text = fh.read().decode("utf-8", "replace")
+                hits += [(os.path.relpath(path, root), w) for w in words if w in text]
+    assert not hits, hits
+    assert not os.path.exists(os.path.join(root, "tools", words[1] + ".py"))
+

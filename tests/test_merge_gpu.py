@@ -75,6 +75,40 @@ def test_merge_ragged_sizes(n, mode, merge):
     assert out.cpu().numpy().tobytes() == ref.tobytes()
 
 
+def test_merge_mixed_jobs_in_one_plan(merge):
+    """Eight jobs of mixed mode and source count (LERP with 1-4 sources, TASKVEC with 1 and 4, MEAN with 2 and 4) in ONE plan,
+    one per size at which tail ownership and the chunk boundary can go wrong; every output bit-equal to the oracle, and a second
+    run() of the same plan gives the same bytes."""
+    L = importlib.import_module("vl_merging_amd._lib")
+    sizes = [1, 3, 5, 4095, 4096, 4097, 8195, 12289]
+    kinds = [("lerp", 1), ("lerp", 2), ("lerp", 3), ("lerp", 4), ("taskvec", 1), ("taskvec", 4), ("mean", 2), ("mean", 4)]
+    ratios = [0.3, 0.45, 0.15, 0.1]
+    plan = merge.MergePlan("cuda")
+    outs, refs = [], []
+    for k, ((kind, s), n) in enumerate(zip(kinds, sizes[3:] + sizes[:3])):  # the four-source jobs meet 8195, 1 and 5
+        rng = np.random.default_rng(100 + k)
+        srcs = [rng.standard_normal(n).astype(np.float32) for _ in range(4)]
+        srcs[0][: min(n, 2)] = -0.0
+        base = rng.standard_normal(n).astype(np.float32)
+        d = [torch.from_numpy(a).cuda() for a in srcs]
+        if kind == "lerp":
+            outs.append(plan.add(L.MERGE_LERP, d[:s], ratios[:s])); refs.append(mo.lerp(srcs[:s], ratios[:s]))
+        elif kind == "taskvec":
+            outs.append(plan.add(L.MERGE_TASKVEC, d[:s], [0.75] * s, base=torch.from_numpy(base).cuda()))
+            refs.append(mo.taskvec(base, srcs[:s], [0.75] * s))
+        else:
+            outs.append(plan.add(L.MERGE_MEAN, d[:s], None)); refs.append(mo.mean(srcs[:s]))
+    assert len(plan.jobs) == 8
+    plan.run()
+    torch.cuda.synchronize()
+    first = [o.cpu().numpy().tobytes() for o in outs]
+    for k, (got, ref) in enumerate(zip(first, refs)):
+        assert got == ref.tobytes(), (kinds[k], len(ref))
+    plan.run()
+    torch.cuda.synchronize()
+    assert [o.cpu().numpy().tobytes() for o in outs] == first
+
+
 def test_merge_base_size_digests(merge, golden_dir):
     """BASELINE config 4: base-size all_moe -> ufo (1 077 239 808 algorithmic bytes), sha256 == reference."""
     dig = json.load(open(os.path.join(golden_dir, "merge_base_digests.json")))

@@ -4,7 +4,7 @@
 //
 // Trim needs, per (tensor, source), the K-th largest magnitude of the task vector t_m = W_m - c.  It is found exactly, on
 // the device, by a radix select over key(x) = bits(x) & 0x7fffffff in three passes of 11 + 10 + 10 bits:
-//   vlm_ties_hist_kernel<PASS>  one launch over the plan's 16-KiB chunk table (the chunk idea of merge.hip).  A workgroup owns a
+//   vlm_ties_hist_kernel<PASS>  one launch over the plan's 16-KiB chunk table (chunk_plan.h).  A workgroup owns a
 //                               CONTIGUOUS run of chunks, recomputes t_m from W_m and c (16-B non-temporal loads; the task vectors
 //                               are never stored), counts the digit of every key that still matches the prefix found so far in
 //                               LDS histograms (integer LDS atomics) and adds the non-empty bins to the (job, source) histogram in
@@ -16,11 +16,11 @@
 // Integer counters only, so nothing depends on the order workgroups run in.  HBM-bound: every pass streams 4 (S + 1) B per
 // element; the apply pass also writes 4 B.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
 #include "vlm_common.h"
+#include "chunk_plan.h"
 #include <string.h>
 #include <vector>
 
-#define TIES_CHUNK 4096u  // floats per chunk: 256 threads x 4 float4
-#define TIES_THREADS 256
+#define TIES_THREADS CHUNK_THREADS  // the chunk walkers need the chunk's 256; the scan kernel uses the same block
 #define TIES_BINS 2048u           // bins per source in LDS and in global memory (pass 0 uses all, passes 1 and 2 use 1024)
 #define TIES_FLUSH_CHUNKS (1u << 19)  // 2^19 chunks x 4096 keys < 2^32: the 32-bit LDS bins cannot wrap between flushes
 #define TIES_HIST_BLOCKS_PER_CU 4  // 110 VGPRs: four workgroups (one wave per SIMD each) are resident per CU; 32 KiB LDS each
@@ -31,10 +31,6 @@
 
 typedef unsigned long long u64_t;
 
-struct ties_chunk_t {
-  uint32_t job;
-  uint32_t start4;  // chunk start / 4 (float4 units)
-};
 struct ties_unit_t {  // one (job, source) pair
   uint32_t job;
   uint32_t m;
@@ -87,7 +83,7 @@ __device__ __forceinline__ void ties_hist_vec(const vlm_ties_job_t& j, const uin
 struct ties_view_t {
   const vlm_ties_header_t* hdr;
   const vlm_ties_job_t* jobs;
-  const ties_chunk_t* chunks;
+  const chunk_t* chunks;
   const uint32_t* unit0;
   const ties_unit_t* units;
   vlm_ties_state_t* state;
@@ -99,7 +95,7 @@ __device__ __forceinline__ ties_view_t ties_view(unsigned char* ws) {
   ties_view_t v;
   v.hdr = reinterpret_cast<const vlm_ties_header_t*>(ws);
   v.jobs = reinterpret_cast<const vlm_ties_job_t*>(ws + v.hdr->jobs_off);
-  v.chunks = reinterpret_cast<const ties_chunk_t*>(ws + v.hdr->chunks_off);
+  v.chunks = reinterpret_cast<const chunk_t*>(ws + v.hdr->chunks_off);
   v.unit0 = reinterpret_cast<const uint32_t*>(ws + v.hdr->unit0_off);
   v.units = reinterpret_cast<const ties_unit_t*>(ws + v.hdr->units_off);
   v.state = reinterpret_cast<vlm_ties_state_t*>(ws + v.hdr->state_off);
@@ -142,7 +138,7 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_hist_kernel(unsigned ch
   uint32_t cur = 0xffffffffu, since = 0;
   uint32_t prefix[VLM_MERGE_MAX_SRC] = {0, 0, 0, 0};
   for (uint64_t c = c0; c < c1; ++c) {
-    const ties_chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
+    const chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
     if (ck.job != cur || since >= TIES_FLUSH_CHUNKS) {
       if (cur != 0xffffffffu) ties_flush<PASS>(lds, w.hist + (uint64_t)w.unit0[cur] * TIES_BINS, w.jobs[cur].n_src);
       cur = ck.job;
@@ -163,11 +159,8 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_hist_kernel(unsigned ch
       case 3: ties_hist_vec<PASS, 3>(j, prefix, start4, n4, lds); break;
       default: ties_hist_vec<PASS, 4>(j, prefix, start4, n4, lds); break;
     }
-    // ragged tail (n_elem % 4) belongs to the chunk that holds the last float4 (or chunk 0 of a tiny job), as in merge.hip
-    const uint64_t tail0 = n4 << 2;
-    const bool last = (start4 + (TIES_CHUNK / 4) >= n4);
-    if (last && threadIdx.x < (j.n_elem - tail0)) {
-      const uint64_t i = tail0 + threadIdx.x;
+    if (threadIdx.x < chunk_tail_len(start4, j.n_elem)) {
+      const uint64_t i = (n4 << 2) + threadIdx.x;
       const float b = reinterpret_cast<const float*>(j.base)[i];
       for (int m = 0; m < j.n_src; ++m)
         ties_bin<PASS>(ties_key(reinterpret_cast<const float*>(j.src[m])[i], b), prefix[m], lds + m * TIES_BINS);
@@ -344,7 +337,7 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_apply_kernel(unsigned c
   uint32_t cur = 0xffffffffu, since = 0;
   uint32_t thr[VLM_MERGE_MAX_SRC] = {0, 0, 0, 0};
   for (uint64_t c = c0; c < c1; ++c) {
-    const ties_chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
+    const chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
     if (ck.job != cur || since >= TIES_FLUSH_CHUNKS) {
       if (cur != 0xffffffffu) ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS);
       cur = ck.job;
@@ -357,9 +350,8 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_apply_kernel(unsigned c
     const vlm_ties_job_t& j = w.jobs[cur];
     const uint64_t n4 = j.n_elem >> 2;
     const uint64_t start4 = ck.start4;
-    const uint64_t tail0 = n4 << 2;
-    const bool tail = (start4 + (TIES_CHUNK / 4) >= n4) && threadIdx.x < (j.n_elem - tail0);
-    const uint64_t ti = tail0 + threadIdx.x;
+    const bool tail = threadIdx.x < chunk_tail_len(start4, j.n_elem);
+    const uint64_t ti = (n4 << 2) + threadIdx.x;
     switch (j.n_src) {
       case 1: ties_apply_vec<1>(j, thr, start4, n4, n); if (tail) ties_apply_tail<1>(j, thr, ti, n); break;
       case 2: ties_apply_vec<2>(j, thr, start4, n4, n); if (tail) ties_apply_tail<2>(j, thr, ti, n); break;
@@ -370,36 +362,27 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_apply_kernel(unsigned c
   ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS);
 }
 
-static inline size_t ties_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static uint64_t ties_chunks_of(uint64_t n_elem) {
-  uint64_t n4 = n_elem >> 2;
-  uint64_t c = (n4 + TIES_CHUNK / 4 - 1) / (TIES_CHUNK / 4);
-  return c == 0 ? 1 : c;  // a job shorter than 4 floats still needs its tail chunk
-}
-
 // fills every offset of `h` for n_jobs jobs, n_units (job, source) pairs and n_chunks chunks; returns the total size
 static size_t ties_layout(vlm_ties_header_t* h, uint64_t n_jobs, uint64_t n_units, uint64_t n_chunks) {
   h->n_jobs = n_jobs;
   h->n_units = n_units;
   h->n_chunks = n_chunks;
-  size_t off = ties_align_up(sizeof(vlm_ties_header_t), 256);
-  h->jobs_off = off;     off += ties_align_up(n_jobs * sizeof(vlm_ties_job_t), 256);
-  h->chunks_off = off;   off += ties_align_up(n_chunks * sizeof(ties_chunk_t), 256);
-  h->unit0_off = off;    off += ties_align_up(n_jobs * sizeof(uint32_t), 256);
-  h->units_off = off;    off += ties_align_up(n_units * sizeof(ties_unit_t), 256);
-  h->state_off = off;    off += ties_align_up(n_units * sizeof(vlm_ties_state_t), 256);
-  h->counters_off = off; off += ties_align_up(n_jobs * VLM_TIES_COUNTERS * sizeof(uint64_t), 256);
-  h->hist_off = off;     off += ties_align_up(n_units * TIES_BINS * sizeof(uint64_t), 256);
+  size_t off = chunk_align_up(sizeof(vlm_ties_header_t), 256);
+  h->jobs_off = off;     off += chunk_align_up(n_jobs * sizeof(vlm_ties_job_t), 256);
+  h->chunks_off = off;   off += chunk_align_up(n_chunks * sizeof(chunk_t), 256);
+  h->unit0_off = off;    off += chunk_align_up(n_jobs * sizeof(uint32_t), 256);
+  h->units_off = off;    off += chunk_align_up(n_units * sizeof(ties_unit_t), 256);
+  h->state_off = off;    off += chunk_align_up(n_units * sizeof(vlm_ties_state_t), 256);
+  h->counters_off = off; off += chunk_align_up(n_jobs * VLM_TIES_COUNTERS * sizeof(uint64_t), 256);
+  h->hist_off = off;     off += chunk_align_up(n_units * TIES_BINS * sizeof(uint64_t), 256);
   return off;
 }
 
 extern "C" size_t vlm_ties_plan_bytes(int n_jobs, uint64_t total_elems) {
   if (n_jobs < 0) return 0;
-  // upper bounds: every job may add one partial chunk and has at most VLM_MERGE_MAX_SRC sources
+  // upper bounds: chunks_bound, and every job has at most VLM_MERGE_MAX_SRC sources
   vlm_ties_header_t h;
-  return ties_layout(&h, (uint64_t)n_jobs, (uint64_t)n_jobs * VLM_MERGE_MAX_SRC,
-                     total_elems / TIES_CHUNK + 2ull * (uint64_t)n_jobs + 1);
+  return ties_layout(&h, (uint64_t)n_jobs, (uint64_t)n_jobs * VLM_MERGE_MAX_SRC, chunks_bound(n_jobs, total_elems));
 }
 
 // do the byte ranges [a, a + 4 n) and [b, b + 4 n) meet?  (dst may not overlap an input: the selection passes re-read the inputs)
@@ -411,21 +394,21 @@ static bool ties_overlap(const void* a, const void* b, uint64_t n_elem) {
 
 extern "C" int vlm_ties_plan_upload(const vlm_ties_job_t* jobs, int n_jobs, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-  if (!jobs || n_jobs <= 0 || !workspace || ((uintptr_t)workspace & 15)) return VLM_ERR_ARG;
+  if (!jobs || n_jobs <= 0 || !chunk_ptr_ok(workspace)) return VLM_ERR_ARG;
   uint64_t n_chunks = 0, n_units = 0;
   for (int i = 0; i < n_jobs; ++i) {
     const vlm_ties_job_t& j = jobs[i];
     if (j.n_src < 1 || j.n_src > VLM_MERGE_MAX_SRC || !j.dst || !j.base || j.n_elem == 0) return VLM_ERR_ARG;
-    if ((j.n_elem >> 2) >= (1ull << 32)) return VLM_ERR_UNSUPPORTED;  // before the byte ranges are formed
-    if (((uintptr_t)j.dst & 15) || ((uintptr_t)j.base & 15) || ties_overlap(j.dst, j.base, j.n_elem)) return VLM_ERR_ARG;
+    if (!chunk_len_ok(j.n_elem)) return VLM_ERR_UNSUPPORTED;  // before the byte ranges are formed
+    if (!chunk_ptr_ok(j.dst) || !chunk_ptr_ok(j.base) || ties_overlap(j.dst, j.base, j.n_elem)) return VLM_ERR_ARG;
     for (int m = 0; m < j.n_src; ++m) {
-      if (!j.src[m] || ((uintptr_t)j.src[m] & 15) || ties_overlap(j.dst, j.src[m], j.n_elem)) return VLM_ERR_ARG;
+      if (!chunk_ptr_ok(j.src[m]) || ties_overlap(j.dst, j.src[m], j.n_elem)) return VLM_ERR_ARG;
       if (j.k[m] < 1 || j.k[m] > j.n_elem) return VLM_ERR_ARG;
     }
-    n_chunks += ties_chunks_of(j.n_elem);
+    n_chunks += chunks_of(j.n_elem);
     n_units += (uint64_t)j.n_src;
   }
-  if (n_chunks >= (1ull << 32) || n_units >= (1ull << 32)) return VLM_ERR_UNSUPPORTED;
+  if (!chunk_count_ok(n_chunks) || n_units >= (1ull << 32)) return VLM_ERR_UNSUPPORTED;
   vlm_ties_header_t hdr;
   const size_t total = ties_layout(&hdr, (uint64_t)n_jobs, n_units, n_chunks);
   if (total > workspace_bytes) return VLM_ERR_WORKSPACE;
@@ -434,17 +417,11 @@ extern "C" int vlm_ties_plan_upload(const vlm_ties_job_t* jobs, int n_jobs, void
   std::vector<unsigned char> img(img_bytes, 0);
   memcpy(img.data(), &hdr, sizeof(hdr));
   memcpy(img.data() + hdr.jobs_off, jobs, (size_t)n_jobs * sizeof(vlm_ties_job_t));
-  ties_chunk_t* ck = reinterpret_cast<ties_chunk_t*>(img.data() + hdr.chunks_off);
+  chunk_table_fill(reinterpret_cast<chunk_t*>(img.data() + hdr.chunks_off), jobs, n_jobs);
   uint32_t* unit0 = reinterpret_cast<uint32_t*>(img.data() + hdr.unit0_off);
   ties_unit_t* units = reinterpret_cast<ties_unit_t*>(img.data() + hdr.units_off);
-  uint64_t c = 0, u = 0;
-  for (int i = 0; i < n_jobs; ++i) {  // job order: a workgroup's run of chunks stays inside few jobs
-    const uint64_t nc = ties_chunks_of(jobs[i].n_elem);
-    for (uint64_t k = 0; k < nc; ++k) {
-      ck[c].job = (uint32_t)i;
-      ck[c].start4 = (uint32_t)(k * (TIES_CHUNK / 4));
-      ++c;
-    }
+  uint64_t u = 0;
+  for (int i = 0; i < n_jobs; ++i) {
     unit0[i] = (uint32_t)u;
     for (int m = 0; m < jobs[i].n_src; ++m) {
       units[u].job = (uint32_t)i;
@@ -454,12 +431,9 @@ extern "C" int vlm_ties_plan_upload(const vlm_ties_job_t* jobs, int n_jobs, void
   }
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
-  if (hipMemcpyAsync(ws, img.data(), img_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return VLM_ERR_LAUNCH;
   // the histograms start at zero; every scan launch leaves them at zero again
   if (hipMemsetAsync(ws + hdr.state_off, 0, total - hdr.state_off, s) != hipSuccess) return VLM_ERR_LAUNCH;
-  // pageable temporary source: the copy is waited for before `img` dies (this call synchronises the stream, as vlm_merge_plan_upload)
-  if (hipStreamSynchronize(s) != hipSuccess) return VLM_ERR_LAUNCH;
-  return VLM_OK;
+  return chunk_upload(ws, img.data(), img_bytes, s);
 }
 
 extern "C" int vlm_ties_run(void* workspace, void* stream) {

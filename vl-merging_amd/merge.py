@@ -68,14 +68,17 @@ def interpolation_ratios(modalities, merge_ratio):
     return {"v": merge_ratio, "l": 1 - merge_ratio}
 
 
-class MergePlan:
-    """A device-resident job table for csrc/merge.hip; build once, run() launches one kernel."""
+class _Plan:
+    """A device-resident job table of the merge family (csrc/chunk_plan.h): build with add(), upload once, run() enqueues the
+    kernels.  A subclass gives its ctypes job type and its three entry points, and writes add()."""
+
+    GPU_ONLY = JOB = BYTES = UPLOAD = RUN = None
 
     def __init__(self, device):
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise L.VlmError("the merge kernel runs on the GPU only (got device %s)" % device)
-        self.jobs: List[L.MergeJob] = []
+            raise L.VlmError("%s (got device %s)" % (self.GPU_ONLY, device))
+        self.jobs = []
         self.keep = []  # keeps staged tensors alive
         self.total = 0
         self.bytes_read = 0
@@ -91,12 +94,38 @@ class MergePlan:
         self.keep.append(t)
         return t
 
+    def _same_shape(self, tensors):
+        for t in tensors:
+            if t.shape != tensors[0].shape:
+                raise L.VlmError("merge sources disagree in shape: %s vs %s" % (t.shape, tensors[0].shape))
+
+    def upload(self):
+        lib = L.get_lib()
+        n = len(self.jobs)
+        arr = (self.JOB * n)(*self.jobs)
+        nbytes = getattr(lib, self.BYTES)(n, self.total)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(getattr(lib, self.UPLOAD)(arr, n, L.ptr(self.ws), nbytes, L.stream_ptr()), self.UPLOAD)
+        return self
+
+    def run(self):
+        if self.ws is None:
+            self.upload()
+        with torch.cuda.device(self.device):
+            L.check(getattr(L.get_lib(), self.RUN)(L.ptr(self.ws), L.stream_ptr()), self.RUN)
+
+
+class MergePlan(_Plan):
+    """The job table of csrc/merge.hip; run() launches one kernel."""
+
+    GPU_ONLY, JOB = "the merge kernel runs on the GPU only", L.MergeJob
+    BYTES, UPLOAD, RUN = "vlm_merge_plan_bytes", "vlm_merge_plan_upload", "vlm_merge_run"
+
     def add(self, mode, srcs, ratios, base=None, out=None):
         srcs = [self._dev(s) for s in srcs]
         n = srcs[0].numel()
-        for s in srcs:
-            if s.shape != srcs[0].shape:
-                raise L.VlmError("merge sources disagree in shape: %s vs %s" % (s.shape, srcs[0].shape))
+        self._same_shape(srcs)
         if out is None:
             out = torch.empty_like(srcs[0])
         self.keep.append(out)
@@ -119,22 +148,6 @@ class MergePlan:
         self.bytes_written += 4 * n
         return out
 
-    def upload(self):
-        lib = L.get_lib()
-        n = len(self.jobs)
-        arr = (L.MergeJob * n)(*self.jobs)
-        nbytes = lib.vlm_merge_plan_bytes(n, self.total)
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(lib.vlm_merge_plan_upload(arr, n, L.ptr(self.ws), nbytes, L.stream_ptr()), "vlm_merge_plan_upload")
-        return self
-
-    def run(self):
-        if self.ws is None:
-            self.upload()
-        with torch.cuda.device(self.device):
-            L.check(L.get_lib().vlm_merge_run(L.ptr(self.ws), L.stream_ptr()), "vlm_merge_run")
-
 
 def _passthrough(state_dict):
     # vilt_module.py:537-541: same tensor objects, not copies
@@ -153,19 +166,43 @@ def _collect(state_dict, src, dst, modalities):
     return srcs, None
 
 
+def _walk(state_dict, config, central=None, honour_only_used=True, want=None):
+    """The one walk over layers and tensor names: yields (dst, mods, srcs | None, through) in the reference's key order, `srcs`
+    as _collect returns them.  `central[dst]` is read BEFORE _collect, so a key the central checkpoint lacks raises before a
+    pass-through.  `want(dst)` = False skips a name."""
+    for i in range(NUM_MERGE_LAYERS):
+        mods = modalities_for_layer(config, i, honour_only_used)
+        for src, dst in _tensor_names(i):
+            if want is not None and not want(dst):
+                continue
+            if central is not None:
+                central[dst]
+            srcs, through = _collect(state_dict, src, dst, mods)
+            yield dst, mods, srcs, through
+
+
+def _central(central_weight, config):
+    """The central checkpoint: the argument, or torch.load(config["central_weight"]); unwrapped from "state_dict"."""
+    if central_weight is None:
+        from . import checkpoint
+        central_weight = checkpoint.load_file(config["central_weight"])
+    return central_weight["state_dict"] if "state_dict" in central_weight else central_weight
+
+
+def _tensors(srcs):
+    return [t for _, t in srcs]
+
+
 def merge_weights(state_dict: Dict[str, torch.Tensor], config, device="cuda", plan_out: Optional[list] = None):
     """Interpolation merge (vilt_module.py:533-638)."""
     out = _passthrough(state_dict)
     plan = MergePlan(device)
-    for i in range(NUM_MERGE_LAYERS):
-        mods = modalities_for_layer(config, i)
+    for dst, mods, srcs, through in _walk(state_dict, config):
         ratios = interpolation_ratios(mods, config["merge_ratio"])
-        for src, dst in _tensor_names(i):
-            srcs, through = _collect(state_dict, src, dst, mods)
-            if srcs is None:
-                out[dst] = through
-            else:
-                out[dst] = plan.add(L.MERGE_LERP, [t for _, t in srcs], [ratios[m] for m, _ in srcs])
+        if srcs is None:
+            out[dst] = through
+        else:
+            out[dst] = plan.add(L.MERGE_LERP, _tensors(srcs), [ratios[m] for m, _ in srcs])
     if plan.jobs:
         plan.run()
     if plan_out is not None:
@@ -176,23 +213,15 @@ def merge_weights(state_dict: Dict[str, torch.Tensor], config, device="cuda", pl
 def sum_task_vectors(state_dict, config, central_weight=None, device="cuda", plan_out: Optional[list] = None):
     """Task-vector merge (vilt_module.py:640-746).  `central_weight` defaults to torch.load(config[...])."""
     out = _passthrough(state_dict)
-    if central_weight is None:
-        from . import checkpoint
-        central_weight = checkpoint.load_file(config["central_weight"])
-    if "state_dict" in central_weight:
-        central_weight = central_weight["state_dict"]
+    central = _central(central_weight, config)
     plan = MergePlan(device)
     lam = config["sum_lambda"]
-    for i in range(NUM_MERGE_LAYERS):
-        mods = modalities_for_layer(config, i)
-        for src, dst in _tensor_names(i):
-            central = central_weight[dst]
-            srcs, through = _collect(state_dict, src, dst, mods)
-            if srcs is None:
-                out[dst] = through
-            else:
-                r = [1 if len(mods) == 1 else lam] * len(srcs)
-                out[dst] = plan.add(L.MERGE_TASKVEC, [t for _, t in srcs], r, base=central)
+    for dst, mods, srcs, through in _walk(state_dict, config, central):
+        if srcs is None:
+            out[dst] = through
+        else:
+            r = [1 if len(mods) == 1 else lam] * len(srcs)
+            out[dst] = plan.add(L.MERGE_TASKVEC, _tensors(srcs), r, base=central[dst])
     if plan.jobs:
         plan.run()
     if plan_out is not None:
@@ -207,25 +236,17 @@ def ties_keep_count(density, n):
     return max(1, min(n, math.ceil(density * n)))
 
 
-class TiesPlan:
-    """A device-resident job table for csrc/ties.hip; build once, run() enqueues the seven launches of a TIES merge (three
-    histogram passes of the radix select, a bin pick after each, the apply pass) without a host synchronisation."""
+class TiesPlan(_Plan):
+    """The job table of csrc/ties.hip; run() enqueues the seven launches of a TIES merge (three histogram passes of the radix
+    select, a bin pick after each, the apply pass) without a host synchronisation."""
 
+    GPU_ONLY, JOB = "the TIES kernels run on the GPU only", L.TiesJob
+    BYTES, UPLOAD, RUN = "vlm_ties_plan_bytes", "vlm_ties_plan_upload", "vlm_ties_run"
     PASSES = 4  # three selection passes + the apply pass: each streams every source and the central tensor once
 
     def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.VlmError("the TIES kernels run on the GPU only (got device %s)" % device)
-        self.jobs: List[L.TiesJob] = []
+        super().__init__(device)
         self.names: List[Optional[str]] = []
-        self.keep = []  # keeps staged tensors alive
-        self.total = 0
-        self.bytes_read = 0
-        self.bytes_written = 0
-        self.ws = None
-
-    _dev = MergePlan._dev
 
     def add(self, srcs, base, density=None, lam=1.0, keep=None, name=None):
         """One output tensor.  `density` gives K for every source (ties_keep_count); `keep` = explicit K per source instead."""
@@ -234,9 +255,7 @@ class TiesPlan:
             raise L.VlmError("a TIES job takes 1 .. %d sources, got %d" % (L.MERGE_MAX_SRC, len(srcs)))
         n = srcs[0].numel()
         b = self._dev(base)
-        for s in srcs + [b]:
-            if s.shape != srcs[0].shape:
-                raise L.VlmError("merge sources disagree in shape: %s vs %s" % (s.shape, srcs[0].shape))
+        self._same_shape(srcs + [b])
         if keep is None:
             keep = [ties_keep_count(density, n)] * len(srcs)
         out = torch.empty_like(srcs[0])
@@ -258,22 +277,6 @@ class TiesPlan:
         self.bytes_read += self.PASSES * 4 * n * (len(srcs) + 1)
         self.bytes_written += 4 * n
         return out
-
-    def upload(self):
-        lib = L.get_lib()
-        n = len(self.jobs)
-        arr = (L.TiesJob * n)(*self.jobs)
-        nbytes = lib.vlm_ties_plan_bytes(n, self.total)
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(lib.vlm_ties_plan_upload(arr, n, L.ptr(self.ws), nbytes, L.stream_ptr()), "vlm_ties_plan_upload")
-        return self
-
-    def run(self):
-        if self.ws is None:
-            self.upload()
-        with torch.cuda.device(self.device):
-            L.check(L.get_lib().vlm_ties_run(L.ptr(self.ws), L.stream_ptr()), "vlm_ties_run")
 
     def report(self):
         """Per job, read back after a run (this synchronises): the threshold per source as a float and as its key, how many
@@ -310,22 +313,14 @@ def ties_merge(state_dict, config, central_weight=None, density=0.2, lam=None, d
     plan = TiesPlan(device)
     single = MergePlan(device)
     out = _passthrough(state_dict)
-    if central_weight is None:
-        from . import checkpoint
-        central_weight = checkpoint.load_file(config["central_weight"])
-    if "state_dict" in central_weight:
-        central_weight = central_weight["state_dict"]
-    for i in range(NUM_MERGE_LAYERS):
-        mods = modalities_for_layer(config, i)
-        for src, dst in _tensor_names(i):
-            central = central_weight[dst]
-            srcs, through = _collect(state_dict, src, dst, mods)
-            if srcs is None:
-                out[dst] = through
-            elif len(mods) == 1:
-                out[dst] = single.add(L.MERGE_TASKVEC, [t for _, t in srcs], [1], base=central)
-            else:
-                out[dst] = plan.add([t for _, t in srcs], central, density=density, lam=lam, name=dst)
+    central = _central(central_weight, config)
+    for dst, mods, srcs, through in _walk(state_dict, config, central):
+        if srcs is None:
+            out[dst] = through
+        elif len(mods) == 1:
+            out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
+        else:
+            out[dst] = plan.add(_tensors(srcs), central[dst], density=density, lam=lam, name=dst)
     for p in (plan, single):
         if p.jobs:
             p.run()

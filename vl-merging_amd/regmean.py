@@ -175,6 +175,11 @@ class _Products:
         self.last_group = {}
 
 
+def _is_weight(dst):
+    """The linear weights take the Gram-matrix path; everything else of a block is a plain average."""
+    return dst.endswith(".weight") and "norm" not in dst
+
+
 def regmean(state_dict, config, gram_matrices=None, device="cuda", plan_out=None):
     passthrough = M._passthrough(state_dict)
     if gram_matrices is None:
@@ -185,16 +190,14 @@ def regmean(state_dict, config, gram_matrices=None, device="cuda", plan_out=None
     dev = plan.device
     solves = _Solves(dev)
     products = _Products()
-    merged, order, plain = {}, [], []
+    merged, order = {}, []
     # first the linear weights of every layer (they feed the device: ~150 launches of products, then the solves' ~420), then the
     # plain averages' bookkeeping while those run; `out` is assembled in the reference's key order at the end
     for i in range(M.NUM_MERGE_LAYERS):
         mods = M.modalities_for_layer(config, i, honour_only_used=False)
         for src, dst in M._tensor_names(i):
             order.append(dst)
-            is_weight = dst.endswith(".weight") and "norm" not in dst
-            if not is_weight:
-                plain.append((src, dst, mods))
+            if not _is_weight(dst):
                 continue
             num, den, through, terms = None, None, None, 0
             for m in mods:
@@ -226,9 +229,8 @@ def regmean(state_dict, config, gram_matrices=None, device="cuda", plan_out=None
                 merged[dst] = solves.submit(num, den, dst)
     products.flush()
     solves.launch(small_ready=products.small_event)
-    for src, dst, mods in plain:
-        srcs, through = M._collect(state_dict, src, dst, mods)
-        merged[dst] = through if srcs is None else plan.add(L.MERGE_MEAN, [t for _, t in srcs], None)
+    for dst, _, srcs, through in M._walk(state_dict, config, honour_only_used=False, want=lambda d: not _is_weight(d)):
+        merged[dst] = through if srcs is None else plan.add(L.MERGE_MEAN, M._tensors(srcs), None)
     if plan.jobs:
         plan.run()
     solves.collect(merged)

@@ -245,7 +245,7 @@ int vlm_gemm_set_big_tile_mode(int mode);
 int vlm_layernorm_fwd(const float* x, int ldx, int M, int D, const float* gamma, const float* beta, float eps,
                       void* y, int ldy, int y_is_f32, float* stats, void* stream);
 /* workspace (optional, f32, >= VLM_ROW_WS_BYTES(D)): per-workgroup partial column sums folded by a second tiny
- * launch; without it the column sums fall back to (heavily contended) float atomics.
+ * launch (the kernel of vlm_colreduce_batch); without it the column sums fall back to (heavily contended) float atomics.
  * deferred_blocks (optional, host int*): when non-NULL the fold is NOT launched; the call stores the number of partial
  * rows it wrote to `workspace` and the caller folds several such workspaces later with ONE vlm_colreduce_batch
  * (a transformer block's backward has four row kernels: three launches saved per block evaluation). */

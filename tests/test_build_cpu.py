@@ -105,3 +105,34 @@ def test_generated_dq_stream_is_current():
     import sys
     gen = os.path.join(CSRC, "gen", "attn_dq2_gen.py")
     assert subprocess.call([sys.executable, gen, "--check"]) == 0, "run python vl-merging_amd/csrc/gen/attn_dq2_gen.py"
+
+
+def _row_kernels(resources, prefix):
+    """Itanium names: ln_bwd_kernel<MAXU, DY_BF16, SCALE> = _Z13ln_bwd_kernelILi<MAXU>ELb<0|1>ELi<SCALE>EE..."""
+    return {k: v for k, v in resources.items() if k.startswith(prefix)}
+
+
+def test_row_kernels_keep_the_occupancy_their_grid_counts_on(resources):
+    """vlm_layernorm_bwd launches one round of resident workgroups: ln_bwd_per_cu (rowops.hip) per CU, which is also the
+    kernel's __launch_bounds__.  The allocator may meet that bound by spilling; these are the verdicts the grid and the
+    measured times rest on (bounds: the values the separate tails compiled to)."""
+    ln = _row_kernels(resources, "_Z13ln_bwd_kernelIL")
+    assert len(ln) == 18, sorted(ln)  # MAXU 1 / 3 / 4 x dy f32 / bf16 x plain / fused / fused with a folded LayerScale
+    for name, r in ln.items():
+        maxu, scale = int(name.split("ILi")[1][0]), int(name.split("ELi")[1][0])
+        if maxu == 3 and scale == 0:
+            assert r["Occupancy"] == 4 and r["VGPRs"] <= 128 and r["ScratchSize"] <= 20, (name, r)
+        elif maxu == 3:
+            assert r["Occupancy"] >= 3 and r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, (name, r)
+            assert 3 * r["LDS Size"] <= 160 * 1024, (name, r)
+        elif maxu == 4:
+            assert r["Occupancy"] == 2 and r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, (name, r)
+    sc = _row_kernels(resources, "_Z16scale_bwd_kernelILi3E")
+    assert len(sc) == 2, sorted(sc)
+    for name, r in sc.items():
+        assert r["Occupancy"] >= 6 and r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, (name, r)
+
+
+def test_one_fold_kernel(resources):
+    assert [k for k in resources if "colreduce_batch_kernel" in k]
+    assert not [k for k in resources if "colreduce_kernel" in k]

@@ -287,11 +287,17 @@ def test_layerscale_bwd_and_colsum(ops):
     assert_close(out2, a[:, 1536:].float().sum(0), 1e-4, 1e-3, "colsum slice")
 
 
-@pytest.mark.parametrize("M,D", [(1, 192), (37, 192), (880, 768), (13574, 768), (9, 1024)])
-@pytest.mark.parametrize("fold,with_rs", [(False, False), (True, True)])
-def test_layernorm_bwd_scale_is_the_two_calls(ops, M, D, fold, with_rs):
+# (37, 520): three granules per lane, the third mostly empty; (5, 200): the row ends inside a wave
+@pytest.mark.parametrize("M,D", [(1, 192), (37, 192), (880, 768), (13574, 768), (9, 1024), (37, 520), (5, 200)])
+@pytest.mark.parametrize("fold,with_rs,folded", [pytest.param(False, False, False, id="False-False"),
+                                                 pytest.param(True, True, False, id="True-True"),
+                                                 pytest.param(False, False, True, id="False-False-folded"),
+                                                 pytest.param(True, True, True, id="True-True-folded")])
+def test_layernorm_bwd_scale_is_the_two_calls(ops, M, D, fold, with_rs, folded):
     """vlm_layernorm_bwd_scale = vlm_layernorm_bwd, then vlm_layerscale_bwd on the row it produced: every output bit for bit
-    (dx, the branch's bf16 gradient; the four column sums to the order of their partial sums when folded from the same grid)."""
+    (dx, the branch's bf16 gradient; the four column sums to the order of their partial sums when folded from the same grid).
+    folded: the LayerScale lives in the branch's projection (y, its gamma and dgamma absent) -- the form a training step runs;
+    fold=False: the fused call folds its two jobs itself, in one launch."""
     gen = torch.Generator(device="cuda"); gen.manual_seed(M * 7 + D)
     x = torch.randn(M, D, device="cuda", generator=gen) * 2 + 0.3
     g = 1 + 0.1 * torch.randn(D, device="cuda", generator=gen)
@@ -302,17 +308,20 @@ def test_layernorm_bwd_scale_is_the_two_calls(ops, M, D, fold, with_rs):
     y = bf(torch.randn(M, D, device="cuda", generator=gen))
     sg = torch.randn(D, device="cuda", generator=gen) * 0.1
     rs = ((torch.rand(M, device="cuda", generator=gen) > 0.3).float() / 0.7) if with_rs else None
+    if folded:
+        y = sg = None
 
     def run(fused):
         dx = torch.empty(M, D, device="cuda"); sdy = torch.empty(M, D, device="cuda", dtype=torch.bfloat16)
         sums = [torch.full((D,), 0.5, device="cuda") for _ in range(4)]
+        dsgamma = None if folded else sums[2]
         fb = ops.FoldBatch(x.device, D) if fold else None
         if fused:
             ops.layernorm_bwd_scale(dy, x, stats, g, dx, dres, sums[0], sums[1], y=y, sgamma=sg, row_scale=rs, sdy=sdy,
-                                    dsgamma=sums[2], dsbias=sums[3], fold=fb)
+                                    dsgamma=dsgamma, dsbias=sums[3], fold=fb)
         else:
             ops.layernorm_bwd(dy, x, stats, g, dx, dres=dres, dgamma=sums[0], dbeta=sums[1], fold=fb)
-            ops.layerscale_bwd(dx, y, sg, rs, sdy, sums[2], sums[3], fold=fb)
+            ops.layerscale_bwd(dx, y, sg, rs, sdy, dsgamma, sums[3], fold=fb)
         if fb is not None:
             fb.flush()
         torch.cuda.synchronize()
@@ -323,6 +332,78 @@ def test_layernorm_bwd_scale_is_the_two_calls(ops, M, D, fold, with_rs):
     assert torch.equal(dx0, dx1) and torch.equal(sdy0, sdy1)
     for a, b, name in zip(s0, s1, ("dgamma", "dbeta", "dsgamma", "dsbias")):
         assert_close(b, a, 1e-5, 1e-4 * math.sqrt(M), name)  # the fused launch has half the workgroups: other partial sums
+    if folded:
+        assert torch.equal(s0[2], torch.full((D,), 0.5, device="cuda")) and torch.equal(s1[2], s0[2])  # no dgamma: untouched
+
+
+@pytest.mark.parametrize("M,D", [(37, 192), (300, 768)])
+@pytest.mark.parametrize("short_ws", [False, True])
+def test_row_kernels_without_a_partial_workspace_add_atomically(ops, L, M, D, short_ws):
+    """The documented fallback of the three backward row entry points: workspace NULL -- or one float short of the grid's
+    partial rows -- and deferred_blocks NULL: the column sums go through one atomicAdd per column per workgroup, the
+    workspace is not written, and everything equals the same call through ops.* (the workspace path).  A deferred call
+    that wants a column sum cannot fall back: VLM_ERR_ARG."""
+    import ctypes
+    lib, p = L.get_lib(), L.ptr
+    gen = torch.Generator(device="cuda"); gen.manual_seed(M * 5 + D)
+    x = torch.randn(M, D, device="cuda", generator=gen) * 2 + 0.3
+    g = 1 + 0.1 * torch.randn(D, device="cuda", generator=gen)
+    stats = torch.empty(M, 2, device="cuda")
+    ops.layernorm_fwd(x, g, torch.zeros(D, device="cuda"), 1e-6, torch.empty(M, D, device="cuda", dtype=torch.bfloat16), stats)
+    dy = bf(torch.randn(M, D, device="cuda", generator=gen))
+    dres = torch.randn(M, D, device="cuda", generator=gen)
+    y = bf(torch.randn(M, D, device="cuda", generator=gen))
+    sg = torch.randn(D, device="cuda", generator=gen) * 0.1
+    rs = (torch.rand(M, device="cuda", generator=gen) > 0.3).float() / 0.7
+    grid = (M + 3) // 4  # one wave per row, four per workgroup: far below every cap at these sizes
+    n_ws = grid * 2 * D - 1
+    new = lambda dtype=torch.float32: torch.full((M, D), 3.0, device="cuda", dtype=dtype)
+    sums = lambda: [torch.full((D,), 0.25, device="cuda") for _ in range(4)]
+
+    def direct(form, deferred=None):
+        """form 0: vlm_layernorm_bwd + vlm_layerscale_bwd; 1 / 2: vlm_layernorm_bwd_scale, unfolded / folded LayerScale."""
+        dx, sdy, s = new(), new(torch.bfloat16), sums()
+        ws = [torch.full((n_ws,), -7.0, device="cuda") if short_ws else None for _ in range(2)]
+        wsa = lambda k: (p(ws[k]), n_ws * 4 if short_ws else 0)
+        yy, gg, dsg = (None, None, None) if form == 2 else (y, sg, s[2])
+        head = (p(dy), D, 0, p(x), D, p(stats), p(g), M, D, p(dres), D, p(dx), D, p(s[0]), p(s[1]))
+        if form == 0:
+            rcs = [lib.vlm_layernorm_bwd(*head, *wsa(0), deferred, L.stream_ptr()),
+                   lib.vlm_layerscale_bwd(p(dx), D, p(yy), D, p(gg), p(rs), M, D, p(sdy), D, p(dsg), p(s[3]), *wsa(1), deferred,
+                                          L.stream_ptr())]
+        else:
+            sc = L.LayerScale()
+            sc.y, sc.ldy, sc.gamma, sc.row_scale, sc.dy, sc.lddy = p(yy), D, p(gg), p(rs), p(sdy), D
+            sc.dgamma, sc.dbias, (sc.workspace, sc.workspace_bytes) = p(dsg), p(s[3]), wsa(1)
+            rcs = [lib.vlm_layernorm_bwd_scale(*head, *wsa(0), ctypes.byref(sc), deferred, L.stream_ptr())]
+        torch.cuda.synchronize()
+        for w in ws:
+            assert w is None or bool((w == -7.0).all()), "a workspace too small for the grid was written"
+        return rcs, dx, sdy, s
+
+    def through_ops(form):
+        dx, sdy, s = new(), new(torch.bfloat16), sums()
+        yy, gg, dsg = (None, None, None) if form == 2 else (y, sg, s[2])
+        if form == 0:
+            ops.layernorm_bwd(dy, x, stats, g, dx, dres=dres, dgamma=s[0], dbeta=s[1])
+            ops.layerscale_bwd(dx, yy, gg, rs, sdy, dsg, s[3])
+        else:
+            ops.layernorm_bwd_scale(dy, x, stats, g, dx, dres, s[0], s[1], y=yy, sgamma=gg, row_scale=rs, sdy=sdy, dsgamma=dsg,
+                                    dsbias=s[3])
+        torch.cuda.synchronize()
+        return dx, sdy, s
+
+    for form in (0, 1, 2):
+        rcs, dx, sdy, s = direct(form)
+        assert rcs == [0] * len(rcs), (form, rcs)
+        dx_w, sdy_w, s_w = through_ops(form)
+        assert torch.equal(dx, dx_w) and torch.equal(sdy, sdy_w), form
+        for a, b in zip(s, s_w):
+            assert_close(a, b, 1e-4, 1e-3 * float(b.float().abs().max()) + 1e-6, "atomic fallback, form %d" % form)
+        assert float((s[3] - 0.25).abs().max()) > 0 and (form == 2) == bool((s[2] == 0.25).all())
+        nb = ctypes.c_int(-1)
+        rcs = direct(form, ctypes.byref(nb))[0]
+        assert rcs == [-1] * len(rcs), (form, rcs)  # VLM_ERR_ARG: deferral needs the partial workspace
 
 
 def test_adamw_matches_hf4_rule(ops):

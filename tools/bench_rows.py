@@ -1,6 +1,6 @@
 """Row-kernel micro-benchmark (LayerNorm fwd/bwd, LayerScale bwd, colsum) at the fused-pass size."""
-import importlib, sys, torch
-sys.path.insert(0, "/root/repo")
+import importlib, os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge
 ge.import_package()
 ops = importlib.import_module("vl_merging_amd.ops")
@@ -28,4 +28,8 @@ for M in (22 * 617, 88 * 617):
     sdy = torch.empty(M, D, device="cuda", dtype=torch.bfloat16)
     t = timeit(lambda: ops.layernorm_bwd_scale(dy, x, st, g, dx, dres, dg, db, y=y, sgamma=g, row_scale=rs, sdy=sdy, dsgamma=dg, dsbias=db))
     print("M=%d ln_bwd + scale_bwd in one pass %.1f us  %.2f TB/s" % (M, t, M * D * 18 / t / 1e6))
+    # the forms a training step runs: the LayerScale folded into the projection (no y, no column scale of its own)
+    t = timeit(lambda: ops.layerscale_bwd(dx, None, None, rs, dy, None, db)); print("M=%d scale_bwd folded %.1f us  %.2f TB/s" % (M, t, M * D * 6 / t / 1e6))
+    t = timeit(lambda: ops.layernorm_bwd_scale(dy, x, st, g, dx, dres, dg, db, y=None, sgamma=None, row_scale=rs, sdy=sdy, dsbias=db))
+    print("M=%d ln_bwd + scale_bwd folded in one pass %.1f us  %.2f TB/s" % (M, t, M * D * 16 / t / 1e6))
     t = timeit(lambda: ops.colsum(dh, cs)); print("M=%d colsum3072 %.1f us  %.2f TB/s" % (M, t, M * 3072 * 2 / t / 1e6))

@@ -6,6 +6,7 @@
 // Reference op sites: nn.LayerNorm(eps=1e-6) vision_transformer.py:831 / apply_ln :495-523; BertEmbeddings
 // LayerNorm(1e-12) vilt_module.py:63; LayerScale `x + drop_path(gamma * branch)` :586,:603; the backward of
 // each is what torch autograd derives for those ops.
+#include <type_traits>
 #include "vlm_common.h"
 
 #ifndef ROW_NT
@@ -99,9 +100,99 @@ __global__ __launch_bounds__(ROW_THREADS) void ln_fwd_kernel(const float* __rest
   }
 }
 
+// ------------------------------------------------------------------------- column sums of the backward kernels
+// The tail of a backward row kernel: two accumulator sets per lane (a0 absent when !HAS0: its plane is zero) -> LDS ->
+// summed over the workgroup's waves in the order w = 0..3 -> plane 0 / plane 1 of this workgroup's row of
+// partials[blocks][2][D] (contention-free plain stores, folded by colreduce_batch_kernel), or without a partial region
+// one atomicAdd per column per workgroup (fp32 grads are accumulated across passes anyway).
+template <int MAXU, bool HAS0>
+__device__ __forceinline__ void column_tail(float (&red)[ROW_WAVES][2][MAXU * 256], const f32x4 (&a0)[HAS0 ? MAXU : 1],
+                                            const f32x4 (&a1)[MAXU], int D, float* __restrict__ partials,
+                                            float* __restrict__ out0, float* __restrict__ out1) {
+  if (!partials && !out0 && !out1) return;  // (kernel arguments: the whole workgroup leaves together)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int u = 0; u < MAXU; ++u)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (HAS0) red[wave][0][u * 256 + lane * 4 + r] = a0[HAS0 ? u : 0][r];
+      red[wave][1][u * 256 + lane * 4 + r] = a1[u][r];
+    }
+  __syncthreads();
+  for (int c = threadIdx.x; c < D; c += ROW_THREADS) {
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int w = 0; w < ROW_WAVES; ++w) {
+      if (HAS0) s0 += red[w][0][c];
+      s1 += red[w][1][c];
+    }
+    if (partials) {
+      partials[((size_t)blockIdx.x * 2 + 0) * D + c] = s0;
+      partials[((size_t)blockIdx.x * 2 + 1) * D + c] = s1;
+    } else {
+      if (out0) atomicAdd(out0 + c, s0);
+      if (out1) atomicAdd(out1 + c, s1);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------- LayerScale backward
+// forward was x_new = x + rs[m]*gamma[n]*y[m,n]  (y = branch output incl. its bias, saved in bf16)
+//   dy[m,n]   = rs[m]*gamma[n]*dx[m,n]          (bf16, feeds the dgrad/wgrad GEMMs)
+//   dgamma[n] += sum_m rs[m]*dx[m,n]*y[m,n]  ;  dbias[n] += sum_m dy[m,n]
+// !HAS_Y (y == NULL, round 5): the LayerScale is folded into the branch's output projection (layerscale.hip) -- only
+// dy = bf16(rs * gamma * dx) and its column sums remain (6 instead of 8 B per element, one accumulator set).
+// One 4-column granule of a row held in registers; g is the caller's: registers held across the rows in the stand-alone
+// kernel, a re-read per row from the cache in the fused kernel (where twelve registers held across the loop cost the third
+// workgroup per CU).
+template <bool HAS_Y>
+__device__ __forceinline__ void scale_bwd_granule(const f32x4& dx, const f32x4& yy, float rs, const f32x4& g,
+                                                  bf16_t* __restrict__ dy, f32x4& ag, f32x4& ab) {
+  bf16x4 h;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float sd = rs * dx[r];
+    const float o = sd * g[r];
+    if (HAS_Y) ag[r] += sd * yy[r];
+    h[r] = (bf16_t)o;
+    ab[r] += (float)h[r];  // the bias gradient the GEMMs see is the rounded dy
+  }
+  *reinterpret_cast<bf16x4*>(dy) = h;
+}
+
+template <int MAXU, bool CAST = false>
+__global__ __launch_bounds__(ROW_THREADS) void scale_bwd_kernel(const float* __restrict__ dx, int lddx,
+                                                                const bf16_t* __restrict__ y, int ldy,
+                                                                const float* __restrict__ gamma,
+                                                                const float* __restrict__ row_scale, int M, int D,
+                                                                bf16_t* __restrict__ dy, int lddy,
+                                                                float* __restrict__ dgamma,
+                                                                float* __restrict__ dbias,
+                                                                float* __restrict__ partials) {
+  __shared__ float red[ROW_WAVES][2][MAXU * 256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  f32x4 g[MAXU], ag[CAST ? 1 : MAXU], ab[MAXU];
+  load_vec<MAXU>(gamma, D, lane, g, 1.0f);
+#pragma unroll
+  for (int u = 0; u < MAXU; ++u) ab[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < (CAST ? 1 : MAXU); ++u) ag[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (size_t row = (size_t)blockIdx.x * ROW_WAVES + wave; row < (size_t)M; row += (size_t)gridDim.x * ROW_WAVES) {
+    f32x4 d[MAXU], yy[CAST ? 1 : MAXU];
+    load_row<MAXU, false>(dx, row, lddx, D, lane, d);
+    if (!CAST) load_row<CAST ? 1 : MAXU, true, ROW_NT>(y, row, ldy, D, lane, yy);
+    const float rs = row_scale ? row_scale[row] : 1.0f;
+#pragma unroll
+    for (int u = 0; u < MAXU; ++u) {
+      const int c = lane * 4 + 256 * u;
+      if (c < D) scale_bwd_granule<!CAST>(d[u], yy[CAST ? 0 : u], rs, g[u], dy + row * lddy + c, ag[CAST ? 0 : u], ab[u]);
+    }
+  }
+  column_tail<MAXU, !CAST>(red, ag, ab, D, partials, dgamma, dbias);
+}
+
 // ------------------------------------------------------------------------------------------ LayerNorm backward
-// dx[m,:] = rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy*gamma ; dx_out = dx (+ dres) ; column sums by
-// one atomicAdd per column per block (fp32 grads are accumulated across passes anyway).
+// dx[m,:] = rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy*gamma ; dx_out = dx (+ dres) ; column sums: column_tail.
 // SCALE (vlm_layernorm_bwd_scale): the row this kernel has just produced is the residual-stream gradient the LayerScale backward
 // of the branch BELOW this LayerNorm reads next (Block.forward: x = x + gamma_1 * attn(norm1(x)); x = x + gamma_2 * mlp(norm2(x)),
 // vision_transformer.py:586,:603) -- taken while it is in registers (ls_t: that branch's saved output, its gamma and row
@@ -117,10 +208,14 @@ struct ls_t {
   float* dbias;
   float* partials;
 };
+// Workgroups per CU (= waves per SIMD) the register allocator is held to, and the launcher's grid counts on
+// (tests/test_build_cpu.py watches the verdict): 4 at <= 128 registers; the fused forms hold one or two more accumulator sets
+// (past 128 registers): 3; four granules per lane: 2.
+__host__ __device__ constexpr int ln_bwd_per_cu(int maxu, bool fused) { return maxu <= 3 ? (fused ? 3 : 4) : 2; }
 // SCALE == 2 (round 5): that LayerScale is folded into the branch's output projection (layerscale.hip) -- ls.y / ls.gamma are
 // absent, only dy = bf16(row_scale * dx) and its column sums are taken with the row (one more accumulator set instead of two).
 template <int MAXU, bool DY_BF16, int SCALE = 0>
-__global__ __launch_bounds__(ROW_THREADS, MAXU <= 3 ? (SCALE ? 3 : 4) : 2) void ln_bwd_kernel(const void* __restrict__ dy, int lddy,
+__global__ __launch_bounds__(ROW_THREADS, ln_bwd_per_cu(MAXU, SCALE)) void ln_bwd_kernel(const void* __restrict__ dy, int lddy,
                                                              const float* __restrict__ x, int ldx,
                                                              const float* __restrict__ stats,
                                                              const float* __restrict__ gamma, int M, int D,
@@ -128,10 +223,10 @@ __global__ __launch_bounds__(ROW_THREADS, MAXU <= 3 ? (SCALE ? 3 : 4) : 2) void 
                                                              float* __restrict__ dx, int lddx,
                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                              float* __restrict__ partials, const ls_t ls) {
-  __shared__ float red[ROW_WAVES][SCALE ? 4 : 2][MAXU * 256];
+  __shared__ float red[SCALE ? 2 : 1][ROW_WAVES][2][MAXU * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   f32x4 g[SCALE ? 1 : MAXU], ag[MAXU], ab[MAXU];
-  f32x4 g2[1], ag2[SCALE == 1 ? MAXU : 1], ab2[SCALE ? MAXU : 1];
+  f32x4 ag2[SCALE == 1 ? MAXU : 1], ab2[SCALE ? MAXU : 1];
   if (SCALE) g[0] = (f32x4){1.f, 1.f, 1.f, 1.f};
   else load_vec<SCALE ? 1 : MAXU>(gamma, D, lane, g, 1.0f);
 #pragma unroll
@@ -185,104 +280,26 @@ __global__ __launch_bounds__(ROW_THREADS, MAXU <= 3 ? (SCALE ? 3 : 4) : 2) void 
         for (int r = 0; r < 4; ++r) o[r] = rstd * (d[u][r] - m1 - v[u][r] * m2);
         if (dres) o += rs[u];
         *reinterpret_cast<f32x4*>(dx + row * lddx + c) = o;
-        if (SCALE) {  // the same operations, in the same order, as scale_bwd_kernel on the stored row
-          // (the branch's gamma is re-read per row from the cache: twelve registers held across the loop cost the third workgroup per CU)
-          const int c2 = lane * 4 + 256 * u;
-          g2[0] = (SCALE == 1 && ls.gamma) ? *reinterpret_cast<const f32x4*>(ls.gamma + c2) : (f32x4){1.f, 1.f, 1.f, 1.f};
-          bf16x4 h;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float sd = srow * o[r];
-            const float q = sd * g2[0][r];
-            if (SCALE == 1) ag2[SCALE == 1 ? u : 0][r] += sd * yy[SCALE == 1 ? u : 0][r];
-            h[r] = (bf16_t)q;
-            ab2[u][r] += (float)h[r];
-          }
-          *reinterpret_cast<bf16x4*>(ls.dy + row * ls.lddy + c) = h;
+        if constexpr (SCALE != 0) {  // scale_bwd_kernel's granule on the row just stored
+          const f32x4 g2 = (SCALE == 1 && ls.gamma) ? *reinterpret_cast<const f32x4*>(ls.gamma + c) : (f32x4){1.f, 1.f, 1.f, 1.f};
+          scale_bwd_granule<SCALE == 1>(o, yy[SCALE == 1 ? u : 0], srow, g2, ls.dy + row * ls.lddy + c, ag2[SCALE == 1 ? u : 0], ab2[u]);
         }
       }
     }
   }
-  if (SCALE) {
-#pragma unroll
-    for (int u = 0; u < (SCALE ? MAXU : 1); ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[wave][SCALE ? 2 : 0][u * 256 + lane * 4 + r] = SCALE == 1 ? ag2[SCALE == 1 ? u : 0][r] : 0.f;
-        red[wave][SCALE ? 3 : 1][u * 256 + lane * 4 + r] = ab2[u][r];
-      }
-  }
-  if (dgamma || dbeta || SCALE) {
-#pragma unroll
-    for (int u = 0; u < MAXU; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[wave][0][u * 256 + lane * 4 + r] = ag[u][r];
-        red[wave][1][u * 256 + lane * 4 + r] = ab[u][r];
-      }
-    __syncthreads();
-    for (int c = threadIdx.x; c < D; c += ROW_THREADS) {
-      float sg = 0.f, sb = 0.f;
-#pragma unroll
-      for (int w = 0; w < ROW_WAVES; ++w) {
-        sg += red[w][0][c];
-        sb += red[w][1][c];
-      }
-      if (partials) {  // contention-free: per-block partial sums, folded by colreduce_kernel
-        partials[((size_t)blockIdx.x * 2 + 0) * D + c] = sg;
-        partials[((size_t)blockIdx.x * 2 + 1) * D + c] = sb;
-      } else {
-        if (dgamma) atomicAdd(dgamma + c, sg);
-        if (dbeta) atomicAdd(dbeta + c, sb);
-      }
-      if (SCALE) {
-        float tg = 0.f, tb = 0.f;
-#pragma unroll
-        for (int w = 0; w < ROW_WAVES; ++w) {
-          tg += red[w][SCALE ? 2 : 0][c];
-          tb += red[w][SCALE ? 3 : 1][c];
-        }
-        if (ls.partials) {
-          ls.partials[((size_t)blockIdx.x * 2 + 0) * D + c] = tg;
-          ls.partials[((size_t)blockIdx.x * 2 + 1) * D + c] = tb;
-        } else {
-          if (ls.dgamma) atomicAdd(ls.dgamma + c, tg);
-          if (ls.dbias) atomicAdd(ls.dbias + c, tb);
-        }
-      }
-    }
-  }
+  column_tail<MAXU, true>(red[0], ag, ab, D, partials, dgamma, dbeta);
+  if constexpr (SCALE != 0) column_tail<MAXU, SCALE == 1>(red[1], ag2, ab2, D, ls.partials, ls.dgamma, ls.dbias);
 }
 
-// out0[c] += sum_b partials[b][0][c] ; out1[c] += sum_b partials[b][1][c].  The per-column float atomics of ~1500
-// workgroups all hit the same 6 KiB (measured ~14x below the un-contended atomic rate: 90 us of a 180 us kernel);
-// plain partial stores + this fold cost ~3 us.
-__global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict__ partials, int nblocks, int D,
-                                                        float* __restrict__ out0, float* __restrict__ out1) {
-  // grid.x covers the 2*D columns, grid.y = COLRED_SPLITS slices of the workgroup axis; 32 atomics per address
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 2 * D) return;
-  const int which = i / D, c = i - which * D;
-  float* out = which ? out1 : out0;
-  if (!out) return;
-  const int per = (nblocks + gridDim.y - 1) / gridDim.y;
-  const int b0 = blockIdx.y * per, b1 = min(nblocks, b0 + per);
-  float s0 = 0.f, s1 = 0.f;
-  int b = b0;
-  for (; b + 1 < b1; b += 2) {
-    s0 += partials[((size_t)(b + 0) * 2 + which) * D + c];
-    s1 += partials[((size_t)(b + 1) * 2 + which) * D + c];
-  }
-  if (b < b1) s0 += partials[((size_t)b * 2 + which) * D + c];
-  if (b0 < b1) atomicAdd(out + c, s0 + s1);
-}
-
-// Several folds in one launch (blockIdx.z = job): a transformer block's backward runs four row kernels whose partials
-// can wait until the block is done, saving three ~10 us launches per block evaluation.
+// out0[c] += sum_b partials[b][0][c] ; out1[c] += sum_b partials[b][1][c], several folds in one launch (blockIdx.z = job).
+// The per-column float atomics of ~1500 workgroups all hit the same 6 KiB (measured ~14x below the un-contended atomic rate:
+// 90 us of a 180 us kernel); plain partial stores + this fold cost ~3 us.  A transformer block's backward runs four row
+// kernels whose partials can wait until the block is done, saving three ~10 us launches per block evaluation.
 struct fold_jobs_t {
   vlm_fold_job_t j[VLM_MAX_FOLD_JOBS];
 };
 __global__ __launch_bounds__(256) void colreduce_batch_kernel(const fold_jobs_t jobs) {
+  // grid.x covers the 2*D columns, grid.y = 32 slices of the workgroup axis: 32 atomics per address
   const vlm_fold_job_t job = jobs.j[blockIdx.z];
   const int D = job.D, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * D) return;
@@ -316,76 +333,6 @@ extern "C" int vlm_colreduce_batch(const vlm_fold_job_t* jobs, int n_jobs, void*
   return VLM_OK;
 }
 
-// ---------------------------------------------------------------------------------------- LayerScale backward
-// forward was x_new = x + rs[m]*gamma[n]*y[m,n]  (y = branch output incl. its bias, saved in bf16)
-//   dy[m,n]   = rs[m]*gamma[n]*dx[m,n]          (bf16, feeds the dgrad/wgrad GEMMs)
-//   dgamma[n] += sum_m rs[m]*dx[m,n]*y[m,n]  ;  dbias[n] += sum_m dy[m,n]
-// CAST (y == NULL, round 5): the LayerScale is folded into the branch's output projection (layerscale.hip) -- only
-// dy = bf16(rs * dx) and its column sums remain (6 instead of 8 B per element, one accumulator set).
-template <int MAXU, bool CAST = false>
-__global__ __launch_bounds__(ROW_THREADS) void scale_bwd_kernel(const float* __restrict__ dx, int lddx,
-                                                                const bf16_t* __restrict__ y, int ldy,
-                                                                const float* __restrict__ gamma,
-                                                                const float* __restrict__ row_scale, int M, int D,
-                                                                bf16_t* __restrict__ dy, int lddy,
-                                                                float* __restrict__ dgamma,
-                                                                float* __restrict__ dbias,
-                                                                float* __restrict__ partials) {
-  __shared__ float red[ROW_WAVES][2][MAXU * 256];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  f32x4 g[MAXU], ag[CAST ? 1 : MAXU], ab[MAXU];
-  load_vec<MAXU>(gamma, D, lane, g, 1.0f);
-#pragma unroll
-  for (int u = 0; u < MAXU; ++u) ab[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int u = 0; u < (CAST ? 1 : MAXU); ++u) ag[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (size_t row = (size_t)blockIdx.x * ROW_WAVES + wave; row < (size_t)M; row += (size_t)gridDim.x * ROW_WAVES) {
-    f32x4 d[MAXU], yy[CAST ? 1 : MAXU];
-    load_row<MAXU, false>(dx, row, lddx, D, lane, d);
-    if (!CAST) load_row<CAST ? 1 : MAXU, true, ROW_NT>(y, row, ldy, D, lane, yy);
-    const float rs = row_scale ? row_scale[row] : 1.0f;
-#pragma unroll
-    for (int u = 0; u < MAXU; ++u) {
-      const int c = lane * 4 + 256 * u;
-      if (c < D) {
-        bf16x4 h;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float sd = rs * d[u][r];
-          const float o = sd * g[u][r];
-          if (!CAST) ag[CAST ? 0 : u][r] += sd * yy[CAST ? 0 : u][r];
-          h[r] = (bf16_t)o;
-          ab[u][r] += (float)h[r];  // the bias gradient the GEMMs see is the rounded dy
-        }
-        *reinterpret_cast<bf16x4*>(dy + row * lddy + c) = h;
-      }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < MAXU; ++u)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      red[wave][0][u * 256 + lane * 4 + r] = CAST ? 0.f : ag[CAST ? 0 : u][r];
-      red[wave][1][u * 256 + lane * 4 + r] = ab[u][r];
-    }
-  __syncthreads();
-  for (int c = threadIdx.x; c < D; c += ROW_THREADS) {
-    float sg = 0.f, sb = 0.f;
-#pragma unroll
-    for (int w = 0; w < ROW_WAVES; ++w) {
-      sg += red[w][0][c];
-      sb += red[w][1][c];
-    }
-    if (partials) {
-      partials[((size_t)blockIdx.x * 2 + 0) * D + c] = sg;
-      partials[((size_t)blockIdx.x * 2 + 1) * D + c] = sb;
-    } else {
-      if (dgamma) atomicAdd(dgamma + c, sg);
-      if (dbias) atomicAdd(dbias + c, sb);
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ column sum
 // out[n] += sum_m a[m, n]  for bf16 a; lane owns 8 columns (16-B loads), the block's 4 waves split the rows.
 __global__ __launch_bounds__(ROW_THREADS) void colsum_kernel(const bf16_t* __restrict__ a, int lda, int M, int N,
@@ -412,11 +359,30 @@ __global__ __launch_bounds__(ROW_THREADS) void colsum_kernel(const bf16_t* __res
   }
 }
 
+// D -> the 256-column granules a lane holds (D = 768: no dead fourth register slot), and the same as a compile-time constant
+static int row_maxu(int D) { return D <= 256 ? 1 : D <= 768 ? 3 : 4; }
+template <class F>
+static void with_maxu(int D, F&& f) {
+  switch (row_maxu(D)) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{});
+  }
+}
+template <class F>
+static void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+static int row_cus() {
+  const int cus = vlm_device_cus();
+  return cus > 0 ? cus : 256;
+}
+
 static int row_grid(int M) {
-  int cus = vlm_device_cus();
-  if (cus <= 0) cus = 256;
   int want = (M + ROW_WAVES - 1) / ROW_WAVES;
-  int cap = cus * 8;
+  int cap = row_cus() * 8;
   return want < cap ? (want > 0 ? want : 1) : cap;
 }
 
@@ -425,16 +391,46 @@ extern "C" int vlm_layernorm_fwd(const float* x, int ldx, int M, int D, const fl
   if (M == 0) return VLM_OK;
   if (!x || !y || M < 0 || D <= 0 || (D & 3) || (ldx & 3) || (ldy & 3)) return VLM_ERR_ARG;
   if (D > 1024) return VLM_ERR_UNSUPPORTED;
-  dim3 grid(row_grid(M)), block(ROW_THREADS);
-  hipStream_t s = (hipStream_t)stream;
-#define LN_FWD(U, F) hipLaunchKernelGGL((ln_fwd_kernel<U, F>), grid, block, 0, s, x, ldx, M, D, gamma, beta, eps, y, ldy, stats)
-  if (D <= 256) { if (y_is_f32) LN_FWD(1, true); else LN_FWD(1, false); }
-  else if (D <= 768) { if (y_is_f32) LN_FWD(3, true); else LN_FWD(3, false); }  // D = 768: no dead fourth register slot
-  else { if (y_is_f32) LN_FWD(4, true); else LN_FWD(4, false); }
-#undef LN_FWD
+  with_maxu(D, [&](auto u) {
+    with_bool(y_is_f32, [&](auto f32) {
+      hipLaunchKernelGGL((ln_fwd_kernel<decltype(u)::value, decltype(f32)::value>), dim3(row_grid(M)), dim3(ROW_THREADS), 0,
+                         (hipStream_t)stream, x, ldx, M, D, gamma, beta, eps, y, ldy, stats);
+    });
+  });
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }
+
+// The launch rule of the backward row kernels.  Grid: one wave per row, at most one round of resident workgroups (per_cu
+// on each CU; 0: no such limit) and never more than ROW_MAX_BLOCKS, the partial rows a VLM_ROW_WS_BYTES workspace holds.
+// Each wanted column-sum pair goes through its partial region [grid][2][D] when that region is large enough (one fold job),
+// else through atomics -- which a deferred fold cannot accept.  After the launch the jobs are reported (*deferred_blocks =
+// the grid whenever ANY pair left partials: a frozen LayerNorm still leaves the LayerScale's) or folded in one launch.
+#define ROW_MAX_BLOCKS 1536
+static_assert(VLM_ROW_WS_BYTES(1) == (size_t)ROW_MAX_BLOCKS * 2 * sizeof(float), "VLM_ROW_WS_BYTES holds ROW_MAX_BLOCKS partial rows");
+struct row_bwd_plan {
+  int grid, D, n_jobs = 0;
+  vlm_fold_job_t jobs[2];
+  row_bwd_plan(int M, int D_, int per_cu) : grid(row_grid(M)), D(D_) {
+    if (per_cu && grid > per_cu * row_cus()) grid = per_cu * row_cus();
+    if (grid > ROW_MAX_BLOCKS) grid = ROW_MAX_BLOCKS;
+  }
+  int partials(float* workspace, size_t workspace_bytes, float* out0, float* out1, const int* deferred_blocks, float** part) {
+    *part = nullptr;
+    if (!out0 && !out1) return VLM_OK;
+    if (workspace && workspace_bytes >= (size_t)grid * 2 * D * sizeof(float)) {
+      *part = workspace;
+      jobs[n_jobs++] = {workspace, grid, D, out0, out1};
+      return VLM_OK;
+    }
+    return deferred_blocks ? VLM_ERR_ARG : VLM_OK;  // deferral needs the partial workspace
+  }
+  int finish(int* deferred_blocks, void* stream) const {
+    if (!deferred_blocks) return vlm_colreduce_batch(jobs, n_jobs, stream);
+    *deferred_blocks = n_jobs ? grid : 0;
+    return VLM_OK;
+  }
+};
 
 static int layernorm_bwd_impl(const void* dy, int lddy, int dy_is_f32, const float* x, int ldx,
                               const float* stats, const float* gamma, int M, int D, const float* dres,
@@ -445,49 +441,33 @@ static int layernorm_bwd_impl(const void* dy, int lddy, int dy_is_f32, const flo
       (dres && (lddres & 3)))
     return VLM_ERR_ARG;
   if (D > 1024) return VLM_ERR_UNSUPPORTED;
-  int g = row_grid(M);
-  // one round of resident workgroups: D <= 768 runs at 4 waves/SIMD (<= 128 VGPRs) = 4 workgroups per CU
-  const int resident = (D <= 768 ? 4 : 2) * (vlm_device_cus() > 0 ? vlm_device_cus() : 256);
-  if (g > resident) g = resident;
-  if (sc && D <= 768 && g > resident * 3 / 4) g = resident * 3 / 4;  // the fused forms hold one or two more accumulator sets: three workgroups per CU (140 / 167 registers)
-  float* part = (workspace && workspace_bytes >= (size_t)g * 2 * D * sizeof(float) && (dgamma || dbeta)) ? workspace : nullptr;
-  dim3 grid(g), block(ROW_THREADS);
-  hipStream_t s = (hipStream_t)stream;
+  row_bwd_plan plan(M, D, ln_bwd_per_cu(row_maxu(D), sc != nullptr));
+  int rc;
+  float* part;
   ls_t ls = {};
   if (sc) {
     if (!sc->dy || (sc->y && (sc->ldy & 3)) || (sc->lddy & 3)) return VLM_ERR_ARG;
     if (!sc->y && (sc->gamma || sc->dgamma)) return VLM_ERR_ARG;  // the folded form (y == NULL) has no column scale of its own
-    const bool want = sc->dgamma || sc->dbias;
-    float* part2 = (sc->workspace && sc->workspace_bytes >= (size_t)g * 2 * D * sizeof(float) && want) ? sc->workspace : nullptr;
-    if (deferred_blocks && want && !part2) return VLM_ERR_ARG;  // deferral needs both partial workspaces
     ls.y = reinterpret_cast<const bf16_t*>(sc->y); ls.ldy = sc->ldy; ls.gamma = sc->gamma; ls.row_scale = sc->row_scale;
-    ls.dy = reinterpret_cast<bf16_t*>(sc->dy); ls.lddy = sc->lddy; ls.dgamma = sc->dgamma; ls.dbias = sc->dbias; ls.partials = part2;
+    ls.dy = reinterpret_cast<bf16_t*>(sc->dy); ls.lddy = sc->lddy; ls.dgamma = sc->dgamma; ls.dbias = sc->dbias;
+    if ((rc = plan.partials(sc->workspace, sc->workspace_bytes, sc->dgamma, sc->dbias, deferred_blocks, &ls.partials)) != VLM_OK) return rc;
   }
-#define LN_BWD(U, B)                                                                                                             \
-  do {                                                                                                                           \
-    if (sc && sc->y) hipLaunchKernelGGL((ln_bwd_kernel<U, B, 1>), grid, block, 0, s, dy, lddy, x, ldx, stats, gamma, M, D, dres, lddres, dx, lddx, dgamma, dbeta, part, ls); \
-    else if (sc) hipLaunchKernelGGL((ln_bwd_kernel<U, B, 2>), grid, block, 0, s, dy, lddy, x, ldx, stats, gamma, M, D, dres, lddres, dx, lddx, dgamma, dbeta, part, ls); \
-    else hipLaunchKernelGGL((ln_bwd_kernel<U, B, 0>), grid, block, 0, s, dy, lddy, x, ldx, stats, gamma, M, D, dres, lddres, dx, lddx, dgamma, dbeta, part, ls); \
-  } while (0)
-  if (D <= 256) { if (dy_is_f32) LN_BWD(1, false); else LN_BWD(1, true); }
-  else if (D <= 768) { if (dy_is_f32) LN_BWD(3, false); else LN_BWD(3, true); }
-  else { if (dy_is_f32) LN_BWD(4, false); else LN_BWD(4, true); }
-#undef LN_BWD
+  if ((rc = plan.partials(workspace, workspace_bytes, dgamma, dbeta, deferred_blocks, &part)) != VLM_OK) return rc;
+  with_maxu(D, [&](auto u) {
+    with_bool(!dy_is_f32, [&](auto bf16) {
+      constexpr int U = decltype(u)::value;
+      constexpr bool B = decltype(bf16)::value;
+      const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(ROW_THREADS), 0, (hipStream_t)stream, dy, lddy, x, ldx, stats, gamma, M, D,
+                           dres, lddres, dx, lddx, dgamma, dbeta, part, ls);
+      };
+      if (sc && sc->y) launch(ln_bwd_kernel<U, B, 1>);
+      else if (sc) launch(ln_bwd_kernel<U, B, 2>);
+      else launch(ln_bwd_kernel<U, B, 0>);
+    });
+  });
   VLM_CHECK_LAUNCH();
-  if (deferred_blocks) {
-    if (!part && (dgamma || dbeta)) return VLM_ERR_ARG;  // deferral needs the partial workspace
-    *deferred_blocks = (part || ls.partials) ? g : 0;     // either set of partials: a frozen LayerNorm still leaves the LayerScale's
-  } else {
-    if (part) {
-      hipLaunchKernelGGL(colreduce_kernel, dim3((2 * D + 255) / 256, 32), dim3(256), 0, s, part, g, D, dgamma, dbeta);
-      VLM_CHECK_LAUNCH();
-    }
-    if (ls.partials) {
-      hipLaunchKernelGGL(colreduce_kernel, dim3((2 * D + 255) / 256, 32), dim3(256), 0, s, ls.partials, g, D, ls.dgamma, ls.dbias);
-      VLM_CHECK_LAUNCH();
-    }
-  }
-  return VLM_OK;
+  return plan.finish(deferred_blocks, stream);
 }
 
 extern "C" int vlm_layernorm_bwd(const void* dy, int lddy, int dy_is_f32, const float* x, int ldx,
@@ -515,31 +495,19 @@ extern "C" int vlm_layerscale_bwd(const float* dx, int lddx, const void* y, int 
   if (!dx || !dy || M < 0 || D <= 0 || (D & 3) || (lddx & 3) || (y && (ldy & 3)) || (lddy & 3)) return VLM_ERR_ARG;
   if (!y && dgamma) return VLM_ERR_ARG;  // y == NULL: the folded form, dy = bf16(row_scale * gamma * dx) and its column sums only
   if (D > 1024) return VLM_ERR_UNSUPPORTED;
-  int g = row_grid(M);
-  if (g > 1536) g = 1536;
-  float* part = (workspace && workspace_bytes >= (size_t)g * 2 * D * sizeof(float) && (dgamma || dbias)) ? workspace : nullptr;
-  dim3 grid(g), block(ROW_THREADS);
-  hipStream_t s = (hipStream_t)stream;
-#define SC_BWD(U)                                                                                                                    \
-  do {                                                                                                                               \
-    if (y) hipLaunchKernelGGL((scale_bwd_kernel<U, false>), grid, block, 0, s, dx, lddx, (const bf16_t*)y, ldy, gamma, row_scale, M,   \
-                              D, (bf16_t*)dy, lddy, dgamma, dbias, part);                                                            \
-    else hipLaunchKernelGGL((scale_bwd_kernel<U, true>), grid, block, 0, s, dx, lddx, (const bf16_t*)y, ldy, gamma, row_scale, M,      \
-                            D, (bf16_t*)dy, lddy, dgamma, dbias, part);                                                              \
-  } while (0)
-  if (D <= 256) SC_BWD(1);
-  else if (D <= 768) SC_BWD(3);
-  else SC_BWD(4);
-#undef SC_BWD
+  row_bwd_plan plan(M, D, 0);
+  int rc;
+  float* part;
+  if ((rc = plan.partials(workspace, workspace_bytes, dgamma, dbias, deferred_blocks, &part)) != VLM_OK) return rc;
+  with_maxu(D, [&](auto u) {
+    with_bool(y == nullptr, [&](auto cast) {
+      hipLaunchKernelGGL((scale_bwd_kernel<decltype(u)::value, decltype(cast)::value>), dim3(plan.grid), dim3(ROW_THREADS), 0,
+                         (hipStream_t)stream, dx, lddx, (const bf16_t*)y, ldy, gamma, row_scale, M, D, (bf16_t*)dy, lddy, dgamma,
+                         dbias, part);
+    });
+  });
   VLM_CHECK_LAUNCH();
-  if (deferred_blocks) {
-    if (!part && (dgamma || dbias)) return VLM_ERR_ARG;
-    *deferred_blocks = part ? g : 0;
-  } else if (part) {
-    hipLaunchKernelGGL(colreduce_kernel, dim3((2 * D + 255) / 256, 32), dim3(256), 0, s, part, g, D, dgamma, dbias);
-    VLM_CHECK_LAUNCH();
-  }
-  return VLM_OK;
+  return plan.finish(deferred_blocks, stream);
 }
 
 extern "C" int vlm_colsum_bf16(const void* a, int lda, int M, int N, float* out, void* stream) {

@@ -185,14 +185,18 @@ def layernorm_fwd(x, gamma, beta, eps, out, stats=None):
 _ROW_WS = {}
 
 
+def _row_ws_floats(D):
+    """One partial region, VLM_ROW_WS_BYTES(D) / 4, never below the D = 1024 size: one allocation serves every width."""
+    return 1536 * 2 * max(D, 1024)
+
+
 def _row_workspace(device, D, slot=0):
-    """Per-device scratch for the row kernels' per-workgroup column partials (VLM_ROW_WS_BYTES); slot 1: the second
-    partial region of a fused call."""
+    """Per-device scratch for the row kernels' per-workgroup column partials; slot 1: the second partial region of a fused
+    call."""
     key = (device.index, torch.cuda.current_stream().cuda_stream, slot)
-    n = 1536 * 2 * max(D, 1024)
     ws = _ROW_WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _ROW_WS[key] = torch.empty(n, device=device, dtype=F32)
+    if ws is None or ws.numel() < _row_ws_floats(D):
+        ws = _ROW_WS[key] = torch.empty(_row_ws_floats(D), device=device, dtype=F32)
     return ws
 
 
@@ -203,7 +207,7 @@ class FoldBatch:
     MAX = 16  # VLM_MAX_FOLD_JOBS: an all_moe block's backward parks 10 (two experts x five row kernels / epilogues)
 
     def __init__(self, device, D=1024):
-        self.region = 1536 * 2 * max(D, 1024)
+        self.region = _row_ws_floats(D)
         key = ("fold", device.index, torch.cuda.current_stream().cuda_stream)
         ws = _ROW_WS.get(key)
         if ws is None or ws.numel() < self.MAX * self.region:
@@ -241,19 +245,35 @@ class FoldBatch:
         self.jobs = []
 
 
+def _row_bwd(name, fold, device, D, head, pairs, sc=None):
+    """Call the backward row kernel `name`(*head, workspace, bytes[, scale], deferred_blocks, stream) with one partial region
+    per column-sum pair (out0, out1): regions of the batch and a job each when the fold is deferred, else the private
+    scratch and deferred_blocks = NULL (the call folds by itself).  The call reports its grid whenever ANY pair left
+    partials (a frozen LayerNorm, no dgamma / dbeta, still leaves the LayerScale's): only a pair with an output has a job."""
+    ws = fold.next_regions(len(pairs)) if fold is not None else [_row_workspace(device, D, slot=k) for k in range(len(pairs))]
+    nb = ctypes.c_int(0)
+    tail = (ctypes.byref(nb) if fold is not None else None, L.stream_ptr())
+    if sc is not None:
+        sc.workspace, sc.workspace_bytes = L.ptr(ws[1]), ws[1].numel() * 4
+        tail = (ctypes.byref(sc),) + tail
+    L.check(getattr(L.get_lib(), name)(*head, L.ptr(ws[0]), ws[0].numel() * 4, *tail), name)
+    if fold is not None:
+        for region, outs in zip(ws, pairs):
+            fold.add(region, nb.value if any(o is not None for o in outs) else 0, D, *outs)
+
+
+def _layernorm_bwd(name, fold, dy, x, stats, gamma, dx, dres, dgamma, dbeta, more_pairs=(), sc=None):
+    M, D = x.shape
+    _row_bwd(name, fold, x.device, D,
+             (L.ptr(dy), _ld(dy), int(dy.dtype == F32), L.ptr(x), _ld(x), L.ptr(stats), L.ptr(gamma), M, D, L.ptr(dres),
+              _ld(dres) if dres is not None else 0, L.ptr(dx), _ld(dx), L.ptr(dgamma), L.ptr(dbeta)),
+             [(dgamma, dbeta), *more_pairs], sc)
+    return dx
+
+
 def layernorm_bwd(dy, x, stats, gamma, dx, dres=None, dgamma=None, dbeta=None, fold=None):
     L.require_cuda(dy, x, stats, gamma, dx, dres, dgamma, dbeta)
-    M, D = x.shape
-    ws = fold.next_region() if fold is not None else _row_workspace(x.device, D)
-    nb = ctypes.c_int(0)
-    rc = L.get_lib().vlm_layernorm_bwd(L.ptr(dy), _ld(dy), int(dy.dtype == F32), L.ptr(x), _ld(x), L.ptr(stats),
-                                       L.ptr(gamma), M, D, L.ptr(dres), _ld(dres) if dres is not None else 0,
-                                       L.ptr(dx), _ld(dx), L.ptr(dgamma), L.ptr(dbeta), L.ptr(ws), ws.numel() * 4,
-                                       ctypes.byref(nb) if fold is not None else None, L.stream_ptr())
-    L.check(rc, "vlm_layernorm_bwd")
-    if fold is not None:
-        fold.add(ws, nb.value, D, dgamma, dbeta)
-    return dx
+    return _layernorm_bwd("vlm_layernorm_bwd", fold, dy, x, stats, gamma, dx, dres, dgamma, dbeta)
 
 
 def layernorm_bwd_scale(dy, x, stats, gamma, dx, dres, dgamma, dbeta, *, y, sgamma, row_scale, sdy, dsgamma=None, dsbias=None,
@@ -262,27 +282,10 @@ def layernorm_bwd_scale(dy, x, stats, gamma, dx, dres, dgamma, dbeta, *, y, sgam
     (vlm_layernorm_bwd_scale): the LayerScale backward of the branch below this LayerNorm reads the row while it is in
     registers.  Bit-identical to the two calls."""
     L.require_cuda(dy, x, stats, gamma, dx, dres, dgamma, dbeta, y, sgamma, row_scale, sdy, dsgamma, dsbias)
-    M, D = x.shape
-    nb = ctypes.c_int(0)
-    if fold is not None:
-        ws, ws2 = fold.next_regions(2)  # two jobs of the batch: this LayerNorm's sums and the LayerScale's
-    else:
-        ws, ws2 = _row_workspace(x.device, D), _row_workspace(x.device, D, slot=1)
     sc = L.LayerScale()
     sc.y, sc.ldy, sc.gamma, sc.row_scale = L.ptr(y), _ld(y) if y is not None else 0, L.ptr(sgamma), L.ptr(row_scale)
     sc.dy, sc.lddy, sc.dgamma, sc.dbias = L.ptr(sdy), _ld(sdy), L.ptr(dsgamma), L.ptr(dsbias)
-    sc.workspace, sc.workspace_bytes = L.ptr(ws2), ws2.numel() * 4
-    rc = L.get_lib().vlm_layernorm_bwd_scale(L.ptr(dy), _ld(dy), int(dy.dtype == F32), L.ptr(x), _ld(x), L.ptr(stats),
-                                             L.ptr(gamma), M, D, L.ptr(dres), _ld(dres) if dres is not None else 0,
-                                             L.ptr(dx), _ld(dx), L.ptr(dgamma), L.ptr(dbeta), L.ptr(ws), ws.numel() * 4,
-                                             ctypes.byref(sc), ctypes.byref(nb) if fold is not None else None, L.stream_ptr())
-    L.check(rc, "vlm_layernorm_bwd_scale")
-    if fold is not None:
-        # nb = the grid whenever EITHER partial set was written: a frozen LayerNorm (no dgamma / dbeta) still leaves the
-        # LayerScale's partials in ws2
-        fold.add(ws, nb.value if (dgamma is not None or dbeta is not None) else 0, D, dgamma, dbeta)
-        fold.add(ws2, nb.value if (dsgamma is not None or dsbias is not None) else 0, D, dsgamma, dsbias)
-    return dx
+    return _layernorm_bwd("vlm_layernorm_bwd_scale", fold, dy, x, stats, gamma, dx, dres, dgamma, dbeta, [(dsgamma, dsbias)], sc)
 
 
 def layerscale_bwd(dx, y, gamma, row_scale, dy, dgamma=None, dbias=None, fold=None):
@@ -290,14 +293,9 @@ def layerscale_bwd(dx, y, gamma, row_scale, dy, dgamma=None, dbias=None, fold=No
     dy = bf16(row_scale * dx) and its column sums (the raw bias gradient) remain."""
     L.require_cuda(dx, y, gamma, row_scale, dy, dgamma, dbias)
     M, D = dx.shape
-    ws = fold.next_region() if fold is not None else _row_workspace(dx.device, D)
-    nb = ctypes.c_int(0)
-    rc = L.get_lib().vlm_layerscale_bwd(L.ptr(dx), _ld(dx), L.ptr(y), _ld(y) if y is not None else 0, L.ptr(gamma), L.ptr(row_scale), M, D,
-                                        L.ptr(dy), _ld(dy), L.ptr(dgamma), L.ptr(dbias), L.ptr(ws), ws.numel() * 4,
-                                        ctypes.byref(nb) if fold is not None else None, L.stream_ptr())
-    L.check(rc, "vlm_layerscale_bwd")
-    if fold is not None:
-        fold.add(ws, nb.value, D, dgamma, dbias)
+    _row_bwd("vlm_layerscale_bwd", fold, dx.device, D,
+             (L.ptr(dx), _ld(dx), L.ptr(y), _ld(y) if y is not None else 0, L.ptr(gamma), L.ptr(row_scale), M, D, L.ptr(dy),
+              _ld(dy), L.ptr(dgamma), L.ptr(dbias)), [(dgamma, dbias)])
     return dy
 
 

@@ -32,7 +32,7 @@ extern "C" {
 #define VLM_ERR_WORKSPACE (-3)
 #define VLM_ERR_UNSUPPORTED (-4)
 
-#define VLM_ABI_VERSION 10
+#define VLM_ABI_VERSION 11
 int vlm_abi_version(void);
 /* Number of compute units grid sizing and split-K slice counts plan for, or negative error: the current device's count,
  * or the smaller budget set by VLM_GEMM_CUS=n (environment, read once) / vlm_set_cu_budget(n) -- room for RCCL's kernels
@@ -454,26 +454,23 @@ int vlm_patch_im2col(const float* image, void* patches_bf16, int B, int H, int W
  * RegMean (K14, src/vilt/modules/vilt_module.py:388-392, 407-434): vlm_scale_gram_f64 forms a*G + (1-a)*diag(G)
  * (optionally accumulating the sum over modalities); vlm_gemm_f64 is C = alpha*op(A) op(B) + beta*C in fp64 (A may be the
  * fp32 checkpoint weight); the reference's torch.inverse of the SPD sum is replaced by a blocked Cholesky
- * factorisation + two triangular solves built from vlm_potrf_block_f64 (in-place lower factor of one <= 64-wide
- * diagonal block; *status gets 1 + the index of a non-positive pivot), vlm_trsm_block_f64 (X <- X op(L)^-1 for a
- * row panel against one diagonal block; trans = 1: X L^T = B, trans = 0: X L = B) and vlm_gemm_f64 for the block
- * updates.  vlm_cholesky_f64 (in-place lower factor of a contiguous SPD [n, n] matrix; *status as above, checked by the
- * caller whenever it chooses to synchronise) and vlm_solve_spd_right_f64 (rhs [rows, ld] <- rhs (L L^T)^-1 in place) walk the
- * block columns inside the library: one call each per merged weight.  vlm_accumulate_f32_f64 (dst += src) is kept for
- * callers that already hold an fp32 product. */
+ * factorisation + two triangular solves, each ONE call that walks the 64-wide block columns inside the library:
+ * vlm_cholesky_f64 (in-place lower factor of a contiguous SPD [n, n] matrix, the upper triangle is left undefined; *status,
+ * zero on entry, gets 1 + the index of the first non-positive pivot, checked by the caller whenever it chooses to
+ * synchronise) and vlm_solve_spd_right_f64 (rhs [rows, ld] <- rhs (L L^T)^-1 in place: Y L^T = rhs forward over the block
+ * columns, then X L = Y backward).  vlm_accumulate_f32_f64 (dst += src) is kept for callers that already hold an fp32
+ * product. */
 int vlm_accumulate_f32_f64(const float* src, double* dst_f64, uint64_t n, void* stream);
 int vlm_gram_f64(const void* x, int ldx, int M, int D, int x_is_f32, double* gram, void* stream);
 int vlm_gemm_f64(int ta, int tb, int M, int N, int K, double alpha, const void* A, int lda, int a_is_f32, const double* B,
                  int ldb, double beta, double* C, int ldc, void* stream);
 int vlm_scale_gram_f64(const double* src, double* dst, int n, double alpha, int accumulate, void* stream);
-int vlm_potrf_block_f64(double* A, int lda, int j0, int nb, int* status, void* stream);
-int vlm_trsm_block_f64(const double* L, int ldl, int l0, int nb, int trans, double* B, int ldb, int rows, int c0, void* stream);
 int vlm_cholesky_f64(double* A, int n, int* status, void* stream);
 int vlm_solve_spd_right_f64(const double* chol, int n, double* rhs, int ld, int rows, void* stream);
-/* The same factorisation / solve for `count` (<= 64) matrices of ONE shape in lock step: every block step is ONE launch over all of
- * them (RegMean's 36 solves of 768^2 and 12 of 3072^2, vilt_module.py:432-434: ~420 launches instead of ~5 000).  A_list / chol_list /
- * rhs_list: HOST arrays of device pointers; status: device int[count], zero on entry, verdict per matrix as in vlm_cholesky_f64.
- * Per matrix bit-identical to the unbatched calls. */
+/* The same product / factorisation / solve for `count` (<= 64) matrices of ONE shape in lock step: every block step is ONE launch
+ * over all of them (RegMean's 36 solves of 768^2 and 12 of 3072^2, vilt_module.py:432-434: ~420 launches instead of ~5 000).  A_list /
+ * chol_list / rhs_list: HOST arrays of device pointers; status: device int[count], zero on entry, verdict per matrix as in
+ * vlm_cholesky_f64.  The three single-matrix calls above ARE these at count = 1: per matrix the same bits. */
 int vlm_gemm_f64_batched(int ta, int tb, int M, int N, int K, double alpha, const void* const* A_list, int lda, int a_is_f32,
                          const double* const* B_list, int ldb, double beta, double* const* C_list, int ldc, int count, void* stream);
 int vlm_cholesky_f64_batched(double* const* A_list, int count, int n, int* status, void* stream);

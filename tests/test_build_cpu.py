@@ -133,6 +133,23 @@ def test_row_kernels_keep_the_occupancy_their_grid_counts_on(resources):
         assert r["Occupancy"] >= 6 and r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, (name, r)
 
 
+def test_f64_block_entry_points_and_switch_are_retired(resources):
+    """The library no longer exports the per-block steps of the float64 factorisation (the drivers own them), f64ops.hip
+    reads no environment variable (the columns per right-looking update are the constant 256), and each float64 operation
+    has its table kernel only.  `resources` brings the build up to date first."""
+    import ctypes
+    lib = ctypes.CDLL(os.path.join(HERE, "..", "vl-merging_amd", "lib", "libvlm_hip.so"))
+    for gone in ("vlm_potrf_block_f64", "vlm_trsm_block_f64"):
+        assert not hasattr(lib, gone), gone
+    assert hasattr(lib, "vlm_cholesky_f64_batched")  # (the probe does find what is there)
+    with open(os.path.join(CSRC, "f64ops.hip")) as f:
+        text = f.read()
+    assert "getenv" not in text and "environ" not in text and "stdlib.h" not in text
+    assert not [k for k in resources if "gemm_f64_kernel" in k or "potrf_block_kernel" in k or "trsm_block_kernel" in k]
+    assert len([k for k in resources if "gemm_f64_batched_kernel" in k]) == 2  # A as float64 / float32
+    assert len([k for k in resources if "potrf_block_batched_kernel" in k or "trsm_block_batched_kernel" in k]) == 2
+
+
 def test_one_fold_kernel(resources):
     assert [k for k in resources if "colreduce_batch_kernel" in k]
     assert not [k for k in resources if "colreduce_kernel" in k]

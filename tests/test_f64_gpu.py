@@ -29,11 +29,8 @@ def test_gram_f64_matches_torch(ops, M, D, dtype):
     assert torch.allclose(acc, acc.t(), rtol=1e-13, atol=1e-10)  # mirrored tiles (the row slices meet through atomics in any order)
 
 
-@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
-@pytest.mark.parametrize("a32", [False, True])
-def test_gemm_f64_matches_torch(ops, ta, tb, a32):
+def _check_gemm_f64(ops, ta, tb, a32, M, N, K):
     g = torch.Generator(device="cuda"); g.manual_seed(7)
-    M, N, K = 150, 97, 333
     a = torch.randn((K, M) if ta else (M, K), device="cuda", generator=g, dtype=torch.float32 if a32 else torch.float64)
     b = torch.randn((N, K) if tb else (K, N), device="cuda", generator=g, dtype=torch.float64)
     c0 = torch.randn(M, N, device="cuda", generator=g, dtype=torch.float64)
@@ -48,6 +45,20 @@ def test_gemm_f64_matches_torch(ops, ta, tb, a32):
     assert float(big[:2].abs().max()) == 0 and float(big[:, :3].abs().max()) == 0
 
 
+@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
+@pytest.mark.parametrize("a32", [False, True])
+def test_gemm_f64_matches_torch(ops, ta, tb, a32):
+    _check_gemm_f64(ops, ta, tb, a32, 150, 97, 333)
+
+
+def test_gemm_f64_one_element_short_reduction(ops):
+    """M = N = 1, K = 5: one tile with one live element, the reduction shorter than one 16-row staged step; every transpose pair
+    and both A types through the one-entry table, strided output view included."""
+    for a32 in (False, True):
+        for ta, tb in ((False, False), (False, True), (True, False), (True, True)):
+            _check_gemm_f64(ops, ta, tb, a32, 1, 1, 5)
+
+
 def test_scale_gram(ops):
     g = torch.randn(130, 130, device="cuda", dtype=torch.float64)
     g = g @ g.t()
@@ -60,8 +71,11 @@ def test_scale_gram(ops):
 
 
 # (264, 520, 600: the 256-column blocks of the drivers end in a ragged block / a ragged 64-column step; 17 / 50 rows: fewer than one
-# workgroup of the triangular block solve)
-@pytest.mark.parametrize("n,rows", [(64, 10), (200, 333), (264, 17), (520, 50), (600, 129), (768, 3072), (3072, 768)])
+# workgroup of the triangular block solve; 40: a single ragged block, potrf and trsm padded with the identity, no GEMM at all; 65: one
+# full block + a 1-wide ragged one, the smallest left-looking GEMM, fewer rows than one wave's four; 257: one column past the 256-column
+# boundary, the smallest case of the trailing update on the lower triangle and of the right-looking GEMM of both solves)
+@pytest.mark.parametrize("n,rows", [(40, 5), (64, 10), (65, 3), (200, 333), (257, 20), (264, 17), (520, 50), (600, 129), (768, 3072),
+                                    (3072, 768)])
 def test_cholesky_solve_matches_inverse(ops, n, rows):
     g = torch.Generator(device="cuda"); g.manual_seed(n)
     x = torch.randn(n + 64, n, device="cuda", generator=g, dtype=torch.float64)

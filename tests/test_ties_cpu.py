@@ -57,7 +57,7 @@ def test_ties_entry_points_declared_exported_bound(pkg):
         assert re.search(r"\b" + s + r"\s*\(", txt), "header does not declare " + s
         assert hasattr(lib, s), "library does not export " + s
         assert s in L.SIGNATURES, "ctypes binding lacks " + s
-    assert lib.vlm_abi_version() == 10  # additive
+    assert lib.vlm_abi_version() == 11
 
 
 def test_ties_struct_layouts_match_the_header(pkg):

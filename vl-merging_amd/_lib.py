@@ -174,8 +174,6 @@ SIGNATURES = {
     "vlm_gemm_f64": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int, c_int, c_void_p, c_int,
                              ctypes.c_double, c_void_p, c_int, c_void_p]),
     "vlm_scale_gram_f64": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_double, c_int, c_void_p]),
-    "vlm_potrf_block_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "vlm_trsm_block_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "vlm_cholesky_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "vlm_solve_spd_right_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "vlm_gemm_f64_batched": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.POINTER(c_void_p), c_int, c_int,

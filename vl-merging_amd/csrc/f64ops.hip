@@ -2,13 +2,12 @@
 // src/cache_gram_matrices.py:246-254: `to(float64)` then matmul) and RegMean's W* = (sum_m W_m G'_m)(sum_m G'_m)^-1
 // (src/vilt/modules/vilt_module.py:407-434, 459-484: `W.double() @ G`, `torch.inverse`).  All products run on
 // v_mfma_f64_16x16x4_f64 (exact fp64 FMA chains); the inverse is replaced by a blocked Cholesky factorisation of the
-// SPD sum of Gram matrices and two triangular solves (the driver, vl_merging_amd/regmean.py, walks the 64-wide block
-// columns and launches the kernels below).
+// SPD sum of Gram matrices and two triangular solves (the blocked drivers at the end of this file walk the 64-wide block
+// columns; vl_merging_amd/regmean.py collects the solves of one shape and calls them once per shape).
 //
 // MFMA f64 16x16x4 operand layout: A[16][4]: lane l holds A[l & 15][l >> 4]; B[4][16]: lane l holds B[l >> 4][l & 15];
 // C/D[16][16]: register r of lane l holds row 4*r + (l >> 4) of column l & 15.
 #include "vlm_common.h"
-#include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
@@ -76,6 +75,32 @@ __device__ __forceinline__ void f64_tile_mac(f64x4 (&acc)[2][2], int k0, int k1,
   }
 }
 
+// A wave's share of a 64 x 64 output tile: the 2 x 2 MFMA blocks of its 32 x 32 quarter, zero on construction.
+struct f64_acc_t {
+  f64x4 v[2][2];
+  __device__ __forceinline__ f64_acc_t() {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) v[a][b] = (f64x4){0.0, 0.0, 0.0, 0.0};
+  }
+  // fn(i, j, value) for every element this lane holds of the tile at (i0, j0) that lies inside the rows x cols matrix
+  template <typename F>
+  __device__ __forceinline__ void for_each(int i0, int j0, int rows, int cols, F fn) const {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = i0 + wi + 16 * a + 4 * r + (lane >> 4), j = j0 + wj + 16 * b + (lane & 15);
+          if (i < rows && j < cols) fn(i, j, v[a][b][r]);
+        }
+  }
+};
+
 // ---------------------------------------------------------------------------------------------------- Gram (SYRK)
 // G[D][D] += X^T X for X [M][D] (bf16 or fp32 activations, converted exactly), upper-triangular tiles only, mirrored on
 // the way out; the M rows are cut into gridDim.z slices that meet in G through fp64 atomics.
@@ -90,34 +115,15 @@ __global__ __launch_bounds__(256) void gram_f64_kernel(const T* __restrict__ x, 
   const int i0 = ti * F64_TILE, j0 = tj * F64_TILE;
   const int per = ((M + gridDim.z - 1) / gridDim.z + F64_KC - 1) / F64_KC * F64_KC;
   const int k0 = blockIdx.z * per, k1 = k0 + per < M ? k0 + per : M;
-  f64x4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (f64x4){0.0, 0.0, 0.0, 0.0};
+  f64_acc_t acc;
   if (k0 < k1)
-    f64_tile_mac(acc, k0, k1,
+    f64_tile_mac(acc.v, k0, k1,
                  [&](int k, int c) { return i0 + c < D ? f64_load(x + (size_t)k * ldx + i0 + c) : 0.0; },
                  [&](int k, int c) { return j0 + c < D ? f64_load(x + (size_t)k * ldx + j0 + c) : 0.0; }, sa, sb);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = i0 + wi + 16 * a + 4 * r + (lane >> 4), j = j0 + wj + 16 * b + (lane & 15);
-        if (i < D && j < D) {
-          const double v = acc[a][b][r];
-          if (ti != tj) {
-            atomicAdd(g + (size_t)i * D + j, v);
-            atomicAdd(g + (size_t)j * D + i, v);
-          } else {
-            atomicAdd(g + (size_t)i * D + j, v);  // diagonal tile: computed in full
-          }
-        }
-      }
+  acc.for_each(i0, j0, D, D, [&](int i, int j, double v) {
+    atomicAdd(g + (size_t)i * D + j, v);
+    if (ti != tj) atomicAdd(g + (size_t)j * D + i, v);  // (a diagonal tile is computed in full)
+  });
 }
 
 extern "C" int vlm_gram_f64(const void* x, int ldx, int M, int D, int x_is_f32, double* gram, void* stream) {
@@ -153,85 +159,82 @@ extern "C" int vlm_gram_f64(const void* x, int ldx, int M, int D, int x_is_f32, 
 // ---------------------------------------------------------------------------------------------------- GEMM
 // C[M][N] = alpha * op(A) op(B) + beta * C, fp64, row-major; op(A)[i][k] = ta ? A[k][i] : A[i][k], op(B)[k][j] = tb ?
 // B[j][k] : B[k][j].  A may be fp32 (a_is_f32: the fp32 checkpoint weights of RegMean enter without a host-side cast).
-template <typename TA_>
-__device__ __forceinline__ void gemm_f64_body(int ta, int tb, int M, int N, int K, double alpha, const TA_* __restrict__ A,
-                                              int lda, const double* __restrict__ B, int ldb, double beta,
-                                              double* __restrict__ C, int ldc) {
-  __shared__ double sa[F64_LDS_DOUBLES], sb[F64_LDS_DOUBLES];
-  const int i0 = blockIdx.y * F64_TILE, j0 = blockIdx.x * F64_TILE;
-  f64x4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (f64x4){0.0, 0.0, 0.0, 0.0};
-  auto a_at = [&](int k, int c) { return i0 + c < M ? (double)(ta ? A[(size_t)k * lda + i0 + c] : A[(size_t)(i0 + c) * lda + k]) : 0.0; };
-  auto b_at = [&](int k, int c) { return j0 + c < N ? (tb ? B[(size_t)(j0 + c) * ldb + k] : B[(size_t)k * ldb + j0 + c]) : 0.0; };
-  // (ta, tb are launch-uniform) the reduction index is contiguous in a row-major A and in a transposed B
-  if (!ta && tb) f64_tile_mac<true, true>(acc, 0, K, a_at, b_at, sa, sb);
-  else if (!ta) f64_tile_mac<true, false>(acc, 0, K, a_at, b_at, sa, sb);
-  else if (tb) f64_tile_mac<false, true>(acc, 0, K, a_at, b_at, sa, sb);
-  else f64_tile_mac<false, false>(acc, 0, K, a_at, b_at, sa, sb);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = i0 + wi + 16 * a + 4 * r + (lane >> 4), j = j0 + wj + 16 * b + (lane & 15);
-        if (i < M && j < N) {
-          double* c = C + (size_t)i * ldc + j;
-          *c = alpha * acc[a][b][r] + (beta != 0.0 ? beta * *c : 0.0);
-        }
-      }
-}
-
-template <typename TA_>
-__global__ __launch_bounds__(256, 4) void gemm_f64_kernel(int ta, int tb, int M, int N, int K, double alpha, const TA_* __restrict__ A,
-                                                       int lda, const double* __restrict__ B, int ldb, double beta,
-                                                       double* __restrict__ C, int ldc, int lower) {
-  if (lower && blockIdx.x > blockIdx.y) return;  // (a symmetric update: only the tiles on and below the diagonal)
-  gemm_f64_body<TA_>(ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc);
-}
-
-// Batched forms (round 5): the 36 + 12 independent solves of a RegMean merge have two shapes; ONE launch performs the same block
-// step for every matrix of a shape (blockIdx.z / .y / .x = the matrix, pointers from a kernel-argument table) -- the chain of
-// ~5 000 dependent 64-wide block launches, dealt over four streams, becomes ~420 launches that fill the chip.
+// Every kernel below the Gram takes its matrices from kernel-argument tables: `count` (<= VLM_F64_MAX_BATCH) problems of ONE shape
+// per launch, blockIdx.z / .y / .x = the problem (the 36 + 12 independent solves of a RegMean merge have two shapes: a chain of
+// ~5 000 dependent 64-wide block launches becomes ~420 launches that fill the chip).  A single matrix is a one-entry table.
 #define VLM_F64_MAX_BATCH 64
 struct f64_tab_t {
   double* p[VLM_F64_MAX_BATCH];
 };
-template <typename TA_ = double>
-__global__ __launch_bounds__(256, 4) void gemm_f64_batched_kernel(int ta, int tb, int M, int N, int K, double alpha, const f64_tab_t A,
-                                                               size_t offA, int lda, const f64_tab_t B, size_t offB, int ldb,
-                                                               double beta, const f64_tab_t C, size_t offC, int ldc, int lower) {
-  if (lower && blockIdx.x > blockIdx.y) return;
-  gemm_f64_body<TA_>(ta, tb, M, N, K, alpha, reinterpret_cast<const TA_*>(A.p[blockIdx.z]) + offA, lda, B.p[blockIdx.z] + offB, ldb,
-                     beta, C.p[blockIdx.z] + offC, ldc);
+static int f64_tab(double* const* list, int count, f64_tab_t& t) {
+  if (!list || count <= 0 || count > VLM_F64_MAX_BATCH) return VLM_ERR_ARG;
+  for (int i = 0; i < count; ++i) {
+    if (!list[i]) return VLM_ERR_ARG;
+    t.p[i] = list[i];
+  }
+  return VLM_OK;
 }
 
 // lower: C is a symmetric update (M == N) of which only the tiles on and below the diagonal are computed -- the Cholesky trailing
 // update A22 -= L21 L21^T, whose upper triangle nothing reads (round 5: half the flops and half the C traffic of a K = 64 GEMM
 // that is bound by reading and writing C)
-static int gemm_f64_launch(int ta, int tb, int M, int N, int K, double alpha, const void* A, int lda, int a_is_f32, const double* B,
-                           int ldb, double beta, double* C, int ldc, int lower, void* stream) {
-  if (M == 0 || N == 0) return VLM_OK;
-  if (!A || !B || !C || M < 0 || N < 0 || K < 0 || ldc < N) return VLM_ERR_ARG;
-  dim3 grid((N + F64_TILE - 1) / F64_TILE, (M + F64_TILE - 1) / F64_TILE);
-  if (a_is_f32)
-    hipLaunchKernelGGL((gemm_f64_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, ta, tb, M, N, K, alpha,
-                       reinterpret_cast<const float*>(A), lda, B, ldb, beta, C, ldc, lower);
-  else
-    hipLaunchKernelGGL((gemm_f64_kernel<double>), grid, dim3(256), 0, (hipStream_t)stream, ta, tb, M, N, K, alpha,
-                       reinterpret_cast<const double*>(A), lda, B, ldb, beta, C, ldc, lower);
+template <typename TA_>
+__global__ __launch_bounds__(256, 4) void gemm_f64_batched_kernel(int ta, int tb, int M, int N, int K, double alpha, const f64_tab_t At,
+                                                               size_t offA, int lda, const f64_tab_t Bt, size_t offB, int ldb,
+                                                               double beta, const f64_tab_t Ct, size_t offC, int ldc, int lower) {
+  if (lower && blockIdx.x > blockIdx.y) return;
+  __shared__ double sa[F64_LDS_DOUBLES], sb[F64_LDS_DOUBLES];
+  const TA_* __restrict__ A = reinterpret_cast<const TA_*>(At.p[blockIdx.z]) + offA;
+  const double* __restrict__ B = Bt.p[blockIdx.z] + offB;
+  double* __restrict__ C = Ct.p[blockIdx.z] + offC;
+  const int i0 = blockIdx.y * F64_TILE, j0 = blockIdx.x * F64_TILE;
+  f64_acc_t acc;
+  auto a_at = [&](int k, int c) { return i0 + c < M ? (double)(ta ? A[(size_t)k * lda + i0 + c] : A[(size_t)(i0 + c) * lda + k]) : 0.0; };
+  auto b_at = [&](int k, int c) { return j0 + c < N ? (tb ? B[(size_t)(j0 + c) * ldb + k] : B[(size_t)k * ldb + j0 + c]) : 0.0; };
+  // (ta, tb are launch-uniform) the reduction index is contiguous in a row-major A and in a transposed B
+  if (!ta && tb) f64_tile_mac<true, true>(acc.v, 0, K, a_at, b_at, sa, sb);
+  else if (!ta) f64_tile_mac<true, false>(acc.v, 0, K, a_at, b_at, sa, sb);
+  else if (tb) f64_tile_mac<false, true>(acc.v, 0, K, a_at, b_at, sa, sb);
+  else f64_tile_mac<false, false>(acc.v, 0, K, a_at, b_at, sa, sb);
+  acc.for_each(i0, j0, M, N, [&](int i, int j, double v) {
+    double* c = C + (size_t)i * ldc + j;
+    *c = alpha * v + (beta != 0.0 ? beta * *c : 0.0);
+  });
+}
+
+// The one launch of the GEMM: the entry points and every GEMM step of the blocked drivers.
+template <typename TA_ = double>
+static int gemm_f64_launch(int ta, int tb, int M, int N, int K, double alpha, const f64_tab_t& A, size_t offA, int lda, const f64_tab_t& B,
+                           size_t offB, int ldb, double beta, const f64_tab_t& C, size_t offC, int ldc, int count, hipStream_t s,
+                           int lower = 0) {
+  if (M == 0 || N == 0 || count == 0) return VLM_OK;
+  if (M < 0 || N < 0 || K < 0 || ldc < N) return VLM_ERR_ARG;
+  dim3 grid((N + F64_TILE - 1) / F64_TILE, (M + F64_TILE - 1) / F64_TILE, count);
+  hipLaunchKernelGGL((gemm_f64_batched_kernel<TA_>), grid, dim3(256), 0, s, ta, tb, M, N, K, alpha, A, offA, lda, B, offB, ldb, beta, C, offC,
+                     ldc, lower);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }
 
+// `count` products of ONE shape in one launch (round 5: RegMean's 96 W_m G'_m products ran one 144..576-workgroup launch each on
+// 1024 slots; per shape they now fill the chip).  Contiguous operands only: transposed and strided ones go one at a time.
+extern "C" int vlm_gemm_f64_batched(int ta, int tb, int M, int N, int K, double alpha, const void* const* A_list, int lda, int a_is_f32,
+                                    const double* const* B_list, int ldb, double beta, double* const* C_list, int ldc, int count,
+                                    void* stream) {
+  if (M == 0 || N == 0 || count == 0) return VLM_OK;  // (before the lists are looked at)
+  f64_tab_t A, B, C;
+  int rc = f64_tab(reinterpret_cast<double* const*>(const_cast<void* const*>(A_list)), count, A);
+  if (!rc) rc = f64_tab(const_cast<double* const*>(B_list), count, B);
+  if (!rc) rc = f64_tab(C_list, count, C);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  return a_is_f32 ? gemm_f64_launch<float>(ta, tb, M, N, K, alpha, A, 0, lda, B, 0, ldb, beta, C, 0, ldc, count, s)
+                  : gemm_f64_launch<double>(ta, tb, M, N, K, alpha, A, 0, lda, B, 0, ldb, beta, C, 0, ldc, count, s);
+}
+
 extern "C" int vlm_gemm_f64(int ta, int tb, int M, int N, int K, double alpha, const void* A, int lda, int a_is_f32,
                             const double* B, int ldb, double beta, double* C, int ldc, void* stream) {
-  return gemm_f64_launch(ta, tb, M, N, K, alpha, A, lda, a_is_f32, B, ldb, beta, C, ldc, 0, stream);
+  return vlm_gemm_f64_batched(ta, tb, M, N, K, alpha, &A, lda, a_is_f32, &B, ldb, beta, &C, ldc, 1, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------- G' = a G + (1-a) diag(G), summed
@@ -304,17 +307,14 @@ __device__ __forceinline__ void potrf_block_body(double* __restrict__ A, int lda
   }
 }
 
-__global__ __launch_bounds__(64) void potrf_block_kernel(double* __restrict__ A, int lda, int j0, int nb, int* __restrict__ status) {
-  potrf_block_body(A, lda, j0, nb, status);
-}
+// (the block step stays a function of its own with __restrict__ parameters: written out inside the kernel on pointers read from the
+// table, hipcc allocates this 256-register kernel differently)
 __global__ __launch_bounds__(64) void potrf_block_batched_kernel(const f64_tab_t A, int lda, int j0, int nb, int* __restrict__ status) {
   potrf_block_body(A.p[blockIdx.x], lda, j0, nb, status + blockIdx.x);
 }
 
-extern "C" int vlm_potrf_block_f64(double* A, int lda, int j0, int nb, int* status, void* stream) {
-  if (nb == 0) return VLM_OK;
-  if (!A || nb < 0 || nb > 64 || j0 < 0 || lda < j0 + nb) return VLM_ERR_ARG;
-  hipLaunchKernelGGL(potrf_block_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, A, lda, j0, nb, status);
+static int potrf_block_launch(const f64_tab_t& A, int lda, int j0, int nb, int* status, int count, hipStream_t s) {
+  hipLaunchKernelGGL(potrf_block_batched_kernel, dim3(count), dim3(64), 0, s, A, lda, j0, nb, status);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }
@@ -379,21 +379,15 @@ __device__ __forceinline__ void trsm_block_body(const double* __restrict__ L, in
     if (lane < nb && row0 + i < rows) x[(size_t)i * ldb + lane] = b[i];
 }
 
-__global__ __launch_bounds__(256) void trsm_block_kernel(const double* __restrict__ L, int ldl, int l0, int nb, int trans,
-                                                         double* __restrict__ Bm, int ldb, int rows, int c0) {
-  trsm_block_body(L, ldl, l0, nb, trans, Bm, ldb, rows, c0);
-}
 __global__ __launch_bounds__(256) void trsm_block_batched_kernel(const f64_tab_t L, size_t offL, int ldl, int l0, int nb, int trans,
                                                                  const f64_tab_t Bm, size_t offB, int ldb, int rows, int c0) {
   trsm_block_body(L.p[blockIdx.y] + offL, ldl, l0, nb, trans, Bm.p[blockIdx.y] + offB, ldb, rows, c0);
 }
 
-extern "C" int vlm_trsm_block_f64(const double* L, int ldl, int l0, int nb, int trans, double* Bm, int ldb, int rows, int c0,
-                                  void* stream) {
-  if (nb == 0 || rows == 0) return VLM_OK;
-  if (!L || !Bm || nb < 0 || nb > 64 || rows < 0 || l0 < 0 || c0 < 0) return VLM_ERR_ARG;
-  hipLaunchKernelGGL(trsm_block_kernel, dim3((rows + 4 * F64_TRSM_ROWS - 1) / (4 * F64_TRSM_ROWS)), dim3(256), 0, (hipStream_t)stream, L, ldl, l0, nb, trans, Bm, ldb,
-                     rows, c0);
+static int trsm_block_launch(const f64_tab_t& L, int ldl, int l0, int nb, int trans, const f64_tab_t& Bm, size_t offB, int ldb, int rows,
+                             int c0, int count, hipStream_t s) {
+  dim3 grid((rows + 4 * F64_TRSM_ROWS - 1) / (4 * F64_TRSM_ROWS), count);
+  hipLaunchKernelGGL(trsm_block_batched_kernel, grid, dim3(256), 0, s, L, (size_t)0, ldl, l0, nb, trans, Bm, offB, ldb, rows, c0);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }
@@ -401,56 +395,15 @@ extern "C" int vlm_trsm_block_f64(const double* L, int ldl, int l0, int nb, int 
 // ---------------------------------------------------------------------------------------------------- blocked drivers
 // The whole factorisation / solve as ONE call: the block-column loops run here instead of in the Python host code (a 3072^2
 // factor is 48 block columns x 3 launches, the solve 2 x 48 x 2 more: issuing them through ctypes cost more host time than the
-// kernels take).  Built from the block kernels above and the tile GEMM; `count` (<= VLM_F64_MAX_BATCH) matrices of ONE shape walk
-// in lock step, every step ONE launch over all of them; the single-matrix entry points are the same code at count = 1.
-static int f64_tab(double* const* list, int count, f64_tab_t& t) {
-  if (!list || count <= 0 || count > VLM_F64_MAX_BATCH) return VLM_ERR_ARG;
-  for (int i = 0; i < count; ++i) {
-    if (!list[i]) return VLM_ERR_ARG;
-    t.p[i] = list[i];
-  }
-  return VLM_OK;
-}
-static int gemm_f64_batched(int ta, int tb, int M, int N, int K, double alpha, const f64_tab_t& A, size_t offA, int lda,
-                            const f64_tab_t& B, size_t offB, int ldb, double beta, const f64_tab_t& C, size_t offC, int ldc, int count,
-                            hipStream_t s, int lower = 0) {
-  if (M <= 0 || N <= 0) return VLM_OK;
-  dim3 grid((N + F64_TILE - 1) / F64_TILE, (M + F64_TILE - 1) / F64_TILE, count);
-  hipLaunchKernelGGL((gemm_f64_batched_kernel<double>), grid, dim3(256), 0, s, ta, tb, M, N, K, alpha, A, offA, lda, B, offB, ldb, beta, C, offC, ldc, lower);
-  VLM_CHECK_LAUNCH();
-  return VLM_OK;
-}
-
-// `count` products of ONE shape in one launch (round 5: RegMean's 96 W_m G'_m products ran one 144..576-workgroup launch each on
-// 1024 slots; per shape they now fill the chip).  Per matrix bit-identical to vlm_gemm_f64.
-extern "C" int vlm_gemm_f64_batched(int ta, int tb, int M, int N, int K, double alpha, const void* const* A_list, int lda, int a_is_f32,
-                                    const double* const* B_list, int ldb, double beta, double* const* C_list, int ldc, int count,
-                                    void* stream) {
-  if (M == 0 || N == 0 || count == 0) return VLM_OK;
-  if (M < 0 || N < 0 || K < 0 || ldc < N) return VLM_ERR_ARG;
-  f64_tab_t A, B, C;
-  int rc = f64_tab(reinterpret_cast<double* const*>(const_cast<void* const*>(A_list)), count, A);
-  if (!rc) rc = f64_tab(const_cast<double* const*>(B_list), count, B);
-  if (!rc) rc = f64_tab(C_list, count, C);
-  if (rc) return rc;
-  if (!a_is_f32) return gemm_f64_batched(ta, tb, M, N, K, alpha, A, 0, lda, B, 0, ldb, beta, C, 0, ldc, count, (hipStream_t)stream);
-  dim3 grid((N + F64_TILE - 1) / F64_TILE, (M + F64_TILE - 1) / F64_TILE, count);
-  hipLaunchKernelGGL((gemm_f64_batched_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, ta, tb, M, N, K, alpha, A, (size_t)0, lda,
-                     B, (size_t)0, ldb, beta, C, (size_t)0, ldc, 0);
-  VLM_CHECK_LAUNCH();
-  return VLM_OK;
-}
-
+// kernels take).  `count` (<= VLM_F64_MAX_BATCH) matrices of ONE shape walk in lock step, every step ONE launch over all of them.
+//
 // Blocking (round 5): the factorisation and the solves walk 64-wide block columns (the block kernels' width), but the updates
 // that touch everything to the right are taken once per F64_BIG = 256 columns with K = 256 -- a K = 64 update GEMM is bound by reading
 // and writing its C (the trailing matrix / the right-hand side's remaining columns: 35 GB per RegMean merge at the base width, 21 ms of
 // its 49); inside a 256-column block the next 64 columns first receive the block's earlier columns' contribution (a GEMM with 64
 // output columns), left-looking.  Same flops, a quarter of the C traffic, the same number of launches.
-static int f64_big(void) {  // VLM_F64_BIG: experiments
-  static const int v = [] { const char* e = getenv("VLM_F64_BIG"); const int x = e ? atoi(e) : 256; return x >= 64 && x % 64 == 0 ? x : 256; }();
-  return v;
-}
-#define F64_BIG f64_big()
+// (64 ... 1 024 columns all measured within 0.042 - 0.047 s per merge: docs/experiments.md)
+#define F64_BIG 256
 
 extern "C" int vlm_cholesky_f64_batched(double* const* A_list, int count, int n, int* status, void* stream) {
   if (n == 0 || count == 0) return VLM_OK;
@@ -464,19 +417,19 @@ extern "C" int vlm_cholesky_f64_batched(double* const* A_list, int count, int n,
     for (int c = J0; c < J1; c += 64) {
       const int nb = n - c < 64 ? n - c : 64, c1 = c + nb, r = n - c1;
       if (c > J0) {  // A[c:, c:c1] -= L[c:, J0:c] L[c:c1, J0:c]^T
-        rc = gemm_f64_batched(0, 1, n - c, nb, c - J0, -1.0, A, (size_t)c * n + J0, n, A, (size_t)c * n + J0, n, 1.0, A, (size_t)c * n + c, n, count, s);
+        rc = gemm_f64_launch(0, 1, n - c, nb, c - J0, -1.0, A, (size_t)c * n + J0, n, A, (size_t)c * n + J0, n, 1.0, A, (size_t)c * n + c, n, count, s);
         if (rc) return rc;
       }
-      hipLaunchKernelGGL(potrf_block_batched_kernel, dim3(count), dim3(64), 0, s, A, n, c, nb, status);
-      VLM_CHECK_LAUNCH();
+      rc = potrf_block_launch(A, n, c, nb, status, count, s);
+      if (rc) return rc;
       if (r > 0) {  // panel: L[c1:, c:c1] = A[c1:, c:c1] L[c:c1, c:c1]^-T
-        hipLaunchKernelGGL(trsm_block_batched_kernel, dim3((r + 4 * F64_TRSM_ROWS - 1) / (4 * F64_TRSM_ROWS), count), dim3(256), 0, s, A, (size_t)0, n, c, nb, 1, A, (size_t)c1 * n, n, r, c);
-        VLM_CHECK_LAUNCH();
+        rc = trsm_block_launch(A, n, c, nb, 1, A, (size_t)c1 * n, n, r, c, count, s);
+        if (rc) return rc;
       }
     }
     const int r = n - J1;
     if (r > 0) {  // trailing update A[J1:, J1:] -= L[J1:, J0:J1] L[J1:, J0:J1]^T, tiles on and below the diagonal
-      rc = gemm_f64_batched(0, 1, r, r, J1 - J0, -1.0, A, (size_t)J1 * n + J0, n, A, (size_t)J1 * n + J0, n, 1.0, A, (size_t)J1 * n + J1, n, count, s, 1);
+      rc = gemm_f64_launch(0, 1, r, r, J1 - J0, -1.0, A, (size_t)J1 * n + J0, n, A, (size_t)J1 * n + J0, n, 1.0, A, (size_t)J1 * n + J1, n, count, s, /*lower=*/1);
       if (rc) return rc;
     }
   }
@@ -502,14 +455,14 @@ extern "C" int vlm_solve_spd_right_f64_batched(double* const* chol_list, int n, 
     for (int c = J0; c < J1; c += 64) {
       const int nb = n - c < 64 ? n - c : 64;
       if (c > J0) {  // B[:, c:c1] -= Y[:, J0:c] L[c:c1, J0:c]^T
-        rc = gemm_f64_batched(0, 1, rows, nb, c - J0, -1.0, R, (size_t)J0, ld, Lt, (size_t)c * n + J0, n, 1.0, R, (size_t)c, ld, count, s);
+        rc = gemm_f64_launch(0, 1, rows, nb, c - J0, -1.0, R, (size_t)J0, ld, Lt, (size_t)c * n + J0, n, 1.0, R, (size_t)c, ld, count, s);
         if (rc) return rc;
       }
-      hipLaunchKernelGGL(trsm_block_batched_kernel, dim3((rows + 4 * F64_TRSM_ROWS - 1) / (4 * F64_TRSM_ROWS), count), dim3(256), 0, s, Lt, (size_t)0, n, c, nb, 1, R, (size_t)0, ld, rows, c);
-      VLM_CHECK_LAUNCH();
+      rc = trsm_block_launch(Lt, n, c, nb, 1, R, 0, ld, rows, c, count, s);
+      if (rc) return rc;
     }
     if (J1 < n) {  // B[:, J1:] -= Y[:, J0:J1] L[J1:, J0:J1]^T
-      rc = gemm_f64_batched(0, 1, rows, n - J1, J1 - J0, -1.0, R, (size_t)J0, ld, Lt, (size_t)J1 * n + J0, n, 1.0, R, (size_t)J1, ld, count, s);
+      rc = gemm_f64_launch(0, 1, rows, n - J1, J1 - J0, -1.0, R, (size_t)J0, ld, Lt, (size_t)J1 * n + J0, n, 1.0, R, (size_t)J1, ld, count, s);
       if (rc) return rc;
     }
   }
@@ -518,14 +471,14 @@ extern "C" int vlm_solve_spd_right_f64_batched(double* const* chol_list, int n, 
     for (int c = J0 + ((J1 - J0 - 1) / 64) * 64; c >= J0; c -= 64) {
       const int nb = n - c < 64 ? n - c : 64, c1 = c + nb;
       if (c1 < J1) {  // Y[:, c:c1] -= X[:, c1:J1] L[c1:J1, c:c1]
-        rc = gemm_f64_batched(0, 0, rows, nb, J1 - c1, -1.0, R, (size_t)c1, ld, Lt, (size_t)c1 * n + c, n, 1.0, R, (size_t)c, ld, count, s);
+        rc = gemm_f64_launch(0, 0, rows, nb, J1 - c1, -1.0, R, (size_t)c1, ld, Lt, (size_t)c1 * n + c, n, 1.0, R, (size_t)c, ld, count, s);
         if (rc) return rc;
       }
-      hipLaunchKernelGGL(trsm_block_batched_kernel, dim3((rows + 4 * F64_TRSM_ROWS - 1) / (4 * F64_TRSM_ROWS), count), dim3(256), 0, s, Lt, (size_t)0, n, c, nb, 0, R, (size_t)0, ld, rows, c);
-      VLM_CHECK_LAUNCH();
+      rc = trsm_block_launch(Lt, n, c, nb, 0, R, 0, ld, rows, c, count, s);
+      if (rc) return rc;
     }
     if (J0 > 0) {  // Y[:, :J0] -= X[:, J0:J1] L[J0:J1, :J0]
-      rc = gemm_f64_batched(0, 0, rows, J0, J1 - J0, -1.0, R, (size_t)J0, ld, Lt, (size_t)J0 * n, n, 1.0, R, (size_t)0, ld, count, s);
+      rc = gemm_f64_launch(0, 0, rows, J0, J1 - J0, -1.0, R, (size_t)J0, ld, Lt, (size_t)J0 * n, n, 1.0, R, (size_t)0, ld, count, s);
       if (rc) return rc;
     }
   }
@@ -534,15 +487,9 @@ extern "C" int vlm_solve_spd_right_f64_batched(double* const* chol_list, int n, 
 
 // The single-matrix calls are the batched ones at count = 1 (one algorithm, one set of kernels: bit-identical by construction).
 extern "C" int vlm_cholesky_f64(double* A, int n, int* status, void* stream) {
-  if (n == 0) return VLM_OK;
-  if (!A || n < 0 || !status) return VLM_ERR_ARG;
-  double* list[1] = {A};
-  return vlm_cholesky_f64_batched(list, 1, n, status, stream);
+  return vlm_cholesky_f64_batched(&A, 1, n, status, stream);
 }
 extern "C" int vlm_solve_spd_right_f64(const double* chol, int n, double* rhs, int ld, int rows, void* stream) {
-  if (n == 0 || rows == 0) return VLM_OK;
-  if (!chol || !rhs || n < 0 || rows < 0 || ld < n) return VLM_ERR_ARG;
-  double* cl[1] = {const_cast<double*>(chol)};
-  double* rl[1] = {rhs};
-  return vlm_solve_spd_right_f64_batched(cl, n, rl, ld, rows, 1, stream);
+  double* L = const_cast<double*>(chol);
+  return vlm_solve_spd_right_f64_batched(&L, n, &rhs, ld, rows, 1, stream);
 }

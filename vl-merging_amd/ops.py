@@ -714,41 +714,7 @@ def scale_gram(src, dst, alpha, accumulate=False):
     return dst
 
 
-def cholesky_(s, status=None):
-    """In-place lower Cholesky factor of the SPD float64 matrix s [n,n] (upper triangle left undefined): blocked
-    right-looking factorisation, 64-wide block columns (potrf block, panel solve, MFMA-f64 trailing update), all block columns
-    issued by ONE library call (vlm_cholesky_f64).  `status` (int32 [1] device tensor, zero on entry): when given, the
-    positive-definiteness verdict is left there for the caller to read whenever it synchronises (several factorisations in
-    flight on several streams); without it this call synchronises and raises on a non-positive pivot."""
-    L.require_cuda(s, status)
-    n = s.shape[0]
-    if s.dtype != F64 or tuple(s.shape) != (n, n) or not s.is_contiguous():
-        raise L.VlmError("cholesky_: contiguous float64 [n,n]")
-    own = status is None
-    if own:
-        status = torch.zeros(1, device=s.device, dtype=torch.int32)
-    L.check(L.get_lib().vlm_cholesky_f64(L.ptr(s), n, L.ptr(status), L.stream_ptr()), "vlm_cholesky_f64")
-    if own:
-        bad = int(status.item())
-        if bad:
-            raise L.VlmError("cholesky_: matrix is not positive definite (pivot %d)" % (bad - 1))
-    return s
-
-
-def solve_spd_right_(rhs, chol):
-    """rhs [rows, n] <- rhs (L L^T)^-1 in place, `chol` from cholesky_: Y L^T = rhs forward over the block columns, then
-    X L = Y backward (triangular block solves on the diagonal blocks, MFMA-f64 GEMMs for the off-diagonal updates), one
-    library call (vlm_solve_spd_right_f64)."""
-    L.require_cuda(rhs, chol)
-    rows, n = rhs.shape
-    if rhs.dtype != F64 or chol.dtype != F64 or tuple(chol.shape) != (n, n) or not chol.is_contiguous() or rhs.stride(1) != 1:
-        raise L.VlmError("solve_spd_right_: float64 rhs [rows, n], contiguous float64 factor [n, n]")
-    L.check(L.get_lib().vlm_solve_spd_right_f64(L.ptr(chol), n, L.ptr(rhs), _ld(rhs), rows, L.stream_ptr()),
-            "vlm_solve_spd_right_f64")
-    return rhs
-
-
-F64_MAX_BATCH = 64
+F64_MAX_BATCH = 64  # entries of a kernel-argument table (VLM_F64_MAX_BATCH): longer lists take one call per 64
 
 
 def _ptr_list(ts):
@@ -756,6 +722,30 @@ def _ptr_list(ts):
     for i, t in enumerate(ts):
         arr[i] = t.data_ptr()
     return arr
+
+
+def _f64_chunks(*lists):
+    """The lists (or a tensor indexed alike), cut side by side into pieces of at most F64_MAX_BATCH entries."""
+    for i in range(0, len(lists[0]), F64_MAX_BATCH):
+        yield [x[i:i + F64_MAX_BATCH] for x in lists]
+
+
+def _f64_squares(mats, who):
+    """n of a list of contiguous float64 [n, n] matrices of one size."""
+    n = mats[0].shape[0]
+    for m in mats:
+        if m.dtype != F64 or tuple(m.shape) != (n, n) or not m.is_contiguous():
+            raise L.VlmError(who + ": contiguous float64 [n,n] matrices of one size")
+    return n
+
+
+def _f64_rhs(rhs, n, who):
+    """(rows, leading dimension) of a list of float64 right-hand sides [rows, n] of one shape and one row stride."""
+    rows, ld = rhs[0].shape[0], _ld(rhs[0])
+    for r in rhs:
+        if r.dtype != F64 or tuple(r.shape) != (rows, n) or _ld(r) != ld:
+            raise L.VlmError(who + ": float64 right-hand sides [rows, n] of one shape")
+    return rows, ld
 
 
 def gemm_f64_batched(a_list, b_list, c_list, alpha=1.0, beta=0.0):
@@ -778,42 +768,56 @@ def gemm_f64_batched(a_list, b_list, c_list, alpha=1.0, beta=0.0):
             for c in c_list:
                 c.zero_()
         return c_list
-    for i in range(0, len(a_list), F64_MAX_BATCH):
-        j = i + F64_MAX_BATCH
-        L.check(L.get_lib().vlm_gemm_f64_batched(0, 0, M, N, K, float(alpha), _ptr_list(a_list[i:j]), K, int(a0.dtype == F32),
-                                                 _ptr_list(b_list[i:j]), N, float(beta), _ptr_list(c_list[i:j]), N,
-                                                 len(a_list[i:j]), L.stream_ptr()), "vlm_gemm_f64_batched")
+    for a, b, c in _f64_chunks(a_list, b_list, c_list):
+        L.check(L.get_lib().vlm_gemm_f64_batched(0, 0, M, N, K, float(alpha), _ptr_list(a), K, int(a0.dtype == F32), _ptr_list(b), N,
+                                                 float(beta), _ptr_list(c), N, len(a), L.stream_ptr()), "vlm_gemm_f64_batched")
     return c_list
 
 
 def cholesky_batched_(mats, status):
-    """cholesky_ of every matrix of `mats` (contiguous float64 [n, n], ONE n) in lock step: each block step is one launch over all
-    of them (vlm_cholesky_f64_batched).  status: int32 device tensor [len(mats)], zero on entry."""
+    """In-place lower Cholesky factors of the SPD float64 matrices `mats` (contiguous [n, n], ONE n; upper triangles left undefined)
+    in lock step: blocked factorisation over 64-wide block columns (potrf block, panel solve, MFMA-f64 trailing update), each block
+    step one launch over all matrices, all of them issued by one library call per 64 matrices (vlm_cholesky_f64_batched).
+    status: int32 device tensor [len(mats)], zero on entry; 1 + the index of a non-positive pivot is left there per matrix for the
+    caller to read whenever it synchronises."""
     L.require_cuda(status, *mats)
-    n = mats[0].shape[0]
-    for m in mats:
-        if m.dtype != F64 or tuple(m.shape) != (n, n) or not m.is_contiguous():
-            raise L.VlmError("cholesky_batched_: contiguous float64 [n,n] matrices of one size")
-    for i in range(0, len(mats), F64_MAX_BATCH):
-        chunk = mats[i:i + F64_MAX_BATCH]
-        L.check(L.get_lib().vlm_cholesky_f64_batched(_ptr_list(chunk), len(chunk), n, L.ptr(status[i:i + len(chunk)]), L.stream_ptr()),
-                "vlm_cholesky_f64_batched")
+    n = _f64_squares(mats, "cholesky_batched_")
+    for m, st in _f64_chunks(mats, status):
+        L.check(L.get_lib().vlm_cholesky_f64_batched(_ptr_list(m), len(m), n, L.ptr(st), L.stream_ptr()), "vlm_cholesky_f64_batched")
     return mats
 
 
 def solve_spd_right_batched_(rhs, chols):
-    """solve_spd_right_ for every (rhs[i], chols[i]) pair, all of ONE shape, in lock step (vlm_solve_spd_right_f64_batched)."""
+    """rhs[i] [rows, n] <- rhs[i] (L_i L_i^T)^-1 in place for every pair, all of ONE shape, in lock step; chols from
+    cholesky_batched_: Y L^T = rhs forward over the block columns, then X L = Y backward (triangular block solves on the diagonal
+    blocks, MFMA-f64 GEMMs for the off-diagonal updates), one library call per 64 pairs (vlm_solve_spd_right_f64_batched)."""
     L.require_cuda(*rhs, *chols)
-    rows, n = rhs[0].shape
-    ld = _ld(rhs[0])
-    for r, c in zip(rhs, chols):
-        if r.dtype != F64 or c.dtype != F64 or tuple(r.shape) != (rows, n) or _ld(r) != ld or r.stride(1) != 1 \
-                or tuple(c.shape) != (n, n) or not c.is_contiguous():
-            raise L.VlmError("solve_spd_right_batched_: float64 rhs [rows, n] of one shape, contiguous float64 factors [n, n]")
-    for i in range(0, len(rhs), F64_MAX_BATCH):
-        rc, cc = rhs[i:i + F64_MAX_BATCH], chols[i:i + F64_MAX_BATCH]
-        L.check(L.get_lib().vlm_solve_spd_right_f64_batched(_ptr_list(cc), n, _ptr_list(rc), ld, rows, len(rc), L.stream_ptr()),
+    n = _f64_squares(chols, "solve_spd_right_batched_")
+    rows, ld = _f64_rhs(rhs, n, "solve_spd_right_batched_")
+    for r, c in _f64_chunks(rhs, chols):
+        L.check(L.get_lib().vlm_solve_spd_right_f64_batched(_ptr_list(c), n, _ptr_list(r), ld, rows, len(r), L.stream_ptr()),
                 "vlm_solve_spd_right_f64_batched")
+    return rhs
+
+
+def cholesky_(s, status=None):
+    """cholesky_batched_ of the one matrix s.  `status` (int32 [1] device tensor, zero on entry): when given, the verdict is left
+    there (several factorisations in flight on several streams); without it this call synchronises and raises on a non-positive
+    pivot."""
+    own = status is None
+    if own:
+        status = torch.zeros(1, device=s.device, dtype=torch.int32)
+    cholesky_batched_([s], status)
+    if own:
+        bad = int(status.item())
+        if bad:
+            raise L.VlmError("cholesky_: matrix is not positive definite (pivot %d)" % (bad - 1))
+    return s
+
+
+def solve_spd_right_(rhs, chol):
+    """solve_spd_right_batched_ of the one pair: rhs [rows, n] <- rhs (L L^T)^-1 in place, `chol` from cholesky_."""
+    solve_spd_right_batched_([rhs], [chol])
     return rhs
 
 

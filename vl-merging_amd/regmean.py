@@ -3,10 +3,12 @@
 Biases / q_bias / v_bias / LayerNorm tensors: plain averages through the HIP merge kernel (VLM_MERGE_MEAN,
 bit-exact with the reference: add in order, then divide by the count).  Linear weights:
 W* = (sum_m W_m G'_m)(sum_m G'_m)^-1 with G' = a*G + (1-a)*diag(G), kept in float64 like the reference.
-The fp64 products run on v_mfma_f64_16x16x4_f64 (csrc/f64ops.hip: vlm_gemm_f64 takes the fp32 weight directly); the
-reference's torch.inverse of the sum of Gram matrices is replaced by a blocked Cholesky factorisation (the sum of
-a*G + (1-a)*diag(G) of SPD Gram matrices is SPD for 0 <= a <= 1) and two triangular solves, ops.cholesky_ /
-ops.solve_spd_right_.  Same W* up to fp64 rounding (tests: 1e-8 relative against the reference's outputs).
+The fp64 products run on v_mfma_f64_16x16x4_f64 (csrc/f64ops.hip; ops.gemm_f64_batched takes the fp32 weights directly,
+one launch per shape: _Products); the reference's torch.inverse of the sum of Gram matrices is replaced by a blocked
+Cholesky factorisation (the sum of a*G + (1-a)*diag(G) of SPD Gram matrices is SPD for 0 <= a <= 1) and two triangular
+solves, ops.cholesky_batched_ / ops.solve_spd_right_batched_ over all solves of one shape (_Solves); a Gram sum without a
+Cholesky factor goes through torch.linalg.inv and ops.gemm_f64.  Same W* up to fp64 rounding (tests: 1e-8 relative against
+the reference's outputs).
 """
 import torch
 

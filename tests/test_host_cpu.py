@@ -291,6 +291,127 @@ def test_round6_host_fallbacks_and_dispatch_rules(pkg, cfgmod, vm):
             call()
 
 
+def test_pass_ends_keep_no_settled_switch_and_no_private_cache(pkg, cfgmod, vm, monkeypatch):
+    """The two retired A/B switches are gone from the package (their records live in docs/experiments.md), the objectives
+    reach the engine through public names only, ops keeps ONE scratch cache, and the environment no longer decides whether
+    the unimodal passes are fused: fuse_unimodal_passes is a plain attribute, True by default."""
+    engine = importlib.import_module("vl_merging_amd.engine")
+    ops = importlib.import_module("vl_merging_amd.ops")
+    root = os.path.dirname(os.path.abspath(pkg.__file__))
+    gone = (b"VLM_FUSED_LOSS", b"VLM_FUSE_UNIMODAL", b"_FUSED_LOSS")
+    seen = 0
+    for d, dirs, files in os.walk(root):
+        dirs[:] = [x for x in dirs if x != "__pycache__"]
+        for f in files:
+            data = open(os.path.join(d, f), "rb").read()
+            seen += 1
+            for word in gone:
+                assert word not in data, (os.path.join(d, f), word)
+    assert seen > 20
+    src = open(os.path.join(root, "vilt", "modules", "objectives.py")).read()
+    assert "engine._" not in src
+    for name in ("_SPLITK_WS", "_ROW_WS", "_FRONT_WS", "_splitk_workspace", "_row_workspace", "_front_ws"):
+        assert not hasattr(ops, name), name
+    for name in ("_FUSED_LOSS", "_WVEC", "_KEEPS_CACHE"):
+        assert not hasattr(engine, name), name
+    monkeypatch.setenv("VLM_FUSE_UNIMODAL", "0")
+    monkeypatch.setenv("VLM_FUSED_LOSS", "0")
+    cfg = tiny_cfg(cfgmod, "ufo")
+    model = vm.ViLTransformerSS(cfg, *cfgmod.routing_configs(cfg))
+    assert model.fuse_unimodal_passes is True and model.fuse_joint_passes is True
+    assert not hasattr(model, "_ones_cache")
+
+
+def test_const_cache_is_bounded_and_zero_scalar_stays(pkg, monkeypatch):
+    """engine.const builds a key's tensor once, holds at most CONST_MAX entries and drops the one that has been in longest;
+    the placeholder zero of _TableT.backward lives outside it (one tensor per device, whatever is evicted)."""
+    engine = importlib.import_module("vl_merging_amd.engine")
+    monkeypatch.setattr(engine, "_CONSTS", {})
+    built = []
+
+    def make(i):
+        def build():
+            built.append(i)
+            return torch.full((), float(i))
+        return build
+
+    z = engine._zero_scalar(torch.device("cpu"))
+    first = engine.const(("k", 0), make(0))
+    assert engine.const(("k", 0), make(0)) is first and built == [0]
+    for i in range(1, engine.CONST_MAX + 3):
+        assert float(engine.const(("k", i), make(i))) == i
+    assert len(engine._CONSTS) == engine.CONST_MAX
+    assert ("k", 0) not in engine._CONSTS and ("k", 2) not in engine._CONSTS and ("k", 3) in engine._CONSTS
+    assert engine.const(("k", 0), make(0)) is not first and built[-1] == 0  # rebuilt after its eviction
+    assert engine._zero_scalar(torch.device("cpu")) is z
+
+
+def test_rows2d_matches_the_five_forms_it_replaced(pkg):
+    """engine._rows2d(g, D, dtypes, contiguous) against the inline forms the backward functions used to carry, on every layout
+    and dtype that tells them apart: same dtype, shape and strides, and a copy exactly where they made one."""
+    engine = importlib.import_module("vl_merging_amd.engine")
+    BF16, F32 = torch.bfloat16, torch.float32
+
+    def old_rows2d(g, D):  # _FeatureViewsFn / _RowRangeFn / _LinearFn.backward
+        g2 = g.reshape(-1, D)
+        if g2.dtype not in (BF16, F32):
+            g2 = g2.float()
+        return g2 if g2.stride(1) == 1 else g2.contiguous()
+
+    def old_l2norm(g, D):
+        g2 = g.reshape(-1, D)
+        return g2.float().contiguous() if g2.dtype != F32 or not g2.is_contiguous() else g2
+
+    def old_layernorm(g, D):
+        g2 = g.reshape(-1, D).contiguous()
+        return g2 if g2.dtype in (BF16, F32) else g2.float()
+
+    def old_front(g, D):  # _EmbeddingFn.backward / _PassRowsFn.backward
+        g2 = g.reshape(-1, D)
+        return g2.float().contiguous() if g2.dtype != F32 or g2.stride(1) != 1 else g2
+
+    forms = ((old_rows2d, {}), (old_l2norm, dict(dtypes=(F32,), contiguous=True)), (old_layernorm, dict(contiguous=True)),
+             (old_front, dict(dtypes=(F32,))))
+    D = 8
+    base = torch.randn(6, 2 * D)
+    layouts = {"contiguous": lambda t: t[:, :D].contiguous(), "row-strided": lambda t: t[:, :D], "column-strided": lambda t: t[:, ::2],
+               "transposed": lambda t: t[:, :D].contiguous().t().contiguous().t(), "3-d": lambda t: t[:, :D].contiguous().view(2, 3, D),
+               "broadcast": lambda t: t[:1, :D].expand(6, D)}
+    for dt in (F32, BF16, torch.float16, torch.float64):
+        for lname, lay in layouts.items():
+            g = lay(base.to(dt))
+            for old, kw in forms:
+                want, got = old(g, D), engine._rows2d(g, D, **kw)
+                what = (old.__name__, lname, dt)
+                assert got.dtype == want.dtype and got.shape == want.shape and got.stride() == want.stride(), what
+                assert (got.data_ptr() == g.data_ptr()) == (want.data_ptr() == g.data_ptr()), what
+                assert torch.equal(got, want), what
+
+
+def test_epilogue_builder_checks_in_the_old_order(pkg):
+    """ops._epilogue (shared by gemm and gemm_grouped) fills vlm_epilogue_t and raises what the two used to raise, in their
+    order: a strided residual / aux before a short col_sum before a wrong dtype, the dtypes in the order bias .. col_sum."""
+    ops = importlib.import_module("vl_merging_amd.ops")
+    L = importlib.import_module("vl_merging_amd._lib")
+    N = 8
+    f32, bf = torch.zeros(4, N), torch.zeros(4, N, dtype=torch.bfloat16)
+    vec = torch.zeros(N)
+    e = ops._epilogue(N, bias=vec, residual=f32[:, :4], aux=bf, act=L.ACT_GELU, alpha=0.5, accumulate=True, col_sum=vec)
+    assert (e.bias, e.col_sum, e.residual, e.ld_res, e.aux, e.ld_aux) == (vec.data_ptr(), vec.data_ptr(), f32.data_ptr(), N, bf.data_ptr(), N)
+    assert (e.act, e.alpha, e.accumulate, e.col_scale, e.row_scale, e.col_sum_ws, e.splitk_ws) == (L.ACT_GELU, 0.5, 1, None, None, None, None)
+    e = ops._epilogue(N)
+    assert (e.bias, e.residual, e.ld_res, e.aux, e.ld_aux, e.act, e.alpha, e.accumulate, e.col_sum) == (None, None, 0, None, 0, L.ACT_NONE, 1.0, 0, None)
+    for kw, msg in ((dict(residual=f32[:, ::2], col_sum=vec[:4], bias=bf[0]), "unit inner stride"),
+                    (dict(aux=bf[:, ::2], col_sum=vec[:4]), "unit inner stride"),
+                    (dict(col_sum=vec[:4], bias=bf[0]), "col_sum must be"),
+                    (dict(col_sum=torch.zeros(2 * N)[::2], aux=f32), "col_sum must be"),
+                    (dict(bias=bf[0], aux=f32), "dtype torch.bfloat16, expected torch.float32"),
+                    (dict(aux=f32, col_sum=vec.double()), "dtype torch.float32, expected torch.bfloat16"),
+                    (dict(col_sum=vec.double()), "dtype torch.float64, expected torch.float32")):
+        with pytest.raises(L.VlmError, match=msg):
+            ops._epilogue(N, **kw)
+
+
 def test_table_transpose_keeps_broadcast_gradients(pkg):
     """_TableT.backward drops only _BlockFn's placeholder (an expanded engine._zero_scalar); a genuine broadcast gradient
     of the transposed table, such as the one of bias_t.sum(), reaches the table."""

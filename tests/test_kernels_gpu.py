@@ -1229,3 +1229,157 @@ def test_feature_views_gradient_matches_autograd_views(pkg, ops, B, T, I, D, dty
         gg = torch.randn(ra.shape, device="cuda", generator=g).to(dtype)
         ra.backward(gg); rb.backward(gg)
         assert torch.equal(ta.grad, tb_.grad)
+
+
+# ---- the dispatch rule of the pass ends (engine._kernel_rows): the smallest eligible input and its nearest ineligible twins --------
+def _ran(t, fn):
+    """Which side produced `t`: "kernel" when its autograd node belongs to the engine function `fn`, else "torch"."""
+    return "kernel" if type(t.grad_fn).__name__ == fn + "Backward" else "torch"
+
+
+def test_pass_end_dispatch_kernel_or_torch_by_input(pkg, ops, L):
+    """Each of the seven entry points that choose between a HIP kernel and its torch formulation (l2_normalize, cross_entropy,
+    small_cross_entropy, weighted_sum, contrastive_loss, feature_views, row_range), on the smallest input its kernel takes and on
+    the nearest inputs it does not: which side ran (the type of the result's grad_fn), and that either side agrees with the torch
+    expression, to the tolerances of the neighbouring tests of the same kernels above (bf16 gradients: one bf16 ulp on top, as
+    in the header of this file)."""
+    engine = importlib.import_module("vl_merging_amd.engine")
+    F = torch.nn.functional
+    g = torch.Generator(device="cuda"); g.manual_seed(11)
+    BF, ULP = torch.bfloat16, 2.0 ** -7
+
+    def randn(*shape, dtype=torch.float32):
+        return torch.randn(*shape, device="cuda", generator=g).to(dtype)
+
+    # ---- l2_normalize: CUDA bf16 / fp32 of any layout (the node lays the rows out itself); fp16 is torch's
+    wide = randn(3, 16, dtype=BF)
+    for x0, want in ((randn(3, 8, dtype=BF), "kernel"), (randn(3, 8, dtype=torch.float16), "torch"), (wide[:, ::2], "kernel")):
+        def leaf():  # keeps the layout: clone() of a strided view would be dense
+            return (x0.clone() if x0.stride(1) == 1 else wide.clone()[:, ::2]).requires_grad_(True)
+
+        a, b = leaf(), leaf()
+        assert a.stride() == x0.stride() and torch.equal(a, x0)
+        ya = engine.l2_normalize(a)
+        assert _ran(ya, "_L2NormFn") == want, (x0.dtype, x0.stride(), type(ya.grad_fn).__name__)
+        bf32 = b.float()
+        yb = bf32 / bf32.norm(dim=-1, keepdim=True)
+        w = randn(3, 8)
+        (ya * w).sum().backward(); (yb * w).sum().backward()
+        assert ya.dtype == torch.float32 and a.grad.dtype == x0.dtype
+        assert_close(ya, yb, 1e-6, 1e-7, "l2 forward")
+        assert_close(a.grad, b.grad, 1e-2, 1e-4, "l2 backward")
+
+    # ---- cross_entropy: bf16, row stride a multiple of 8 elements, 16-byte aligned base, int64 labels
+    labels = torch.tensor([3, 0, -100, 9, 1], device="cuda")
+    flat = randn(5 * 16 + 8, dtype=BF)
+    cases = ((flat[:80].view(5, 16), labels, "kernel"),
+             (flat[:50].view(5, 10), labels, "torch"),       # row stride 10
+             (flat[4:84].view(5, 16), labels, "torch"),      # starts 8 bytes into the aligned buffer
+             (flat[:80].view(5, 16), labels.int(), "torch"))
+    assert flat.data_ptr() % 16 == 0 and cases[2][0].data_ptr() % 16 == 8
+    for lg, lab, want in cases:
+        a = lg.detach().requires_grad_(True)
+        assert a.stride() == lg.stride() and a.data_ptr() == lg.data_ptr()
+        try:
+            loss = engine.cross_entropy(a, lab)
+        except L.VlmError:
+            raise
+        except RuntimeError:  # torch's own refusal of int32 targets: torch is what ran
+            assert want == "torch" and lab.dtype == torch.int32
+            continue
+        assert _ran(loss, "_CrossEntropyFn") == want, (lg.shape, lg.stride(), lab.dtype, type(loss.grad_fn).__name__)
+        r = lg.detach().float().requires_grad_(True)
+        ref = F.cross_entropy(r, lab.long())
+        assert abs(float(loss) - float(ref)) <= 2e-5 * max(1.0, abs(float(ref)))
+        (loss * 1.7).backward(); (ref * 1.7).backward()
+        assert a.grad.dtype == BF
+        assert_close(a.grad, r.grad, 1e-2, 1e-7, "cross-entropy gradient")
+
+    # ---- small_cross_entropy: at most 64 classes
+    lab6 = torch.tensor([0, 1, 1, 0, 1, 0], device="cuda")
+    for lg, want in ((randn(6, 2), "kernel"), (randn(6, 2, dtype=BF), "kernel"), (randn(6, 65), "torch")):
+        a = lg.detach().requires_grad_(True)
+        loss = engine.small_cross_entropy(a, lab6)
+        assert _ran(loss, "_SmallCrossEntropyFn") == want, (lg.shape, lg.dtype)
+        r = lg.detach().float().requires_grad_(True)
+        ref = F.cross_entropy(r, lab6)
+        assert abs(float(loss) - float(ref)) <= 1e-5 * max(1.0, abs(float(ref)))
+        loss.backward(); ref.backward()
+        assert a.grad.dtype == lg.dtype
+        assert_close(a.grad, r.grad, 1e-5 + (ULP if lg.dtype == BF else 0.0), 1e-6, "small ce grad")
+
+    # ---- weighted_sum: one to eight fp32 CUDA scalars
+    def scalars(k, dtype=torch.float32):
+        return [torch.tensor(0.5 * i - 1.25, device="cuda", dtype=dtype, requires_grad=True) for i in range(k)]
+
+    for terms, want in ((scalars(2), "kernel"), (scalars(9), "torch"), (scalars(1) + scalars(1, torch.float64), "torch")):
+        ws = [0.5 + 0.25 * i for i in range(len(terms))]
+        s = engine.weighted_sum(terms, ws)
+        assert _ran(s, "_WeightedSumFn") == want, (len(terms), [t.dtype for t in terms])
+        assert abs(float(s) - sum(w * float(t) for w, t in zip(ws, terms))) < 1e-6
+        s.backward()
+        assert all(abs(float(t.grad) - w) < 1e-6 for w, t in zip(ws, terms))
+
+    # ---- contrastive_loss: CUDA features and ONE log_scale
+    img0, txt0 = F.normalize(randn(3, 8), dim=-1), F.normalize(randn(3, 8), dim=-1)
+    for ls0, want in ((torch.tensor(2.3, device="cuda"), "kernel"), (torch.tensor([2.3, 2.1], device="cuda"), "torch")):
+        got, ref = [], []
+        for out, fn in ((got, engine.contrastive_loss), (ref, None)):
+            i, t, ls = (x.clone().requires_grad_(True) for x in (img0, txt0, ls0))
+            if fn is not None:
+                loss, li, scale = fn(i, t, ls)
+                assert _ran(loss, "_ContrastiveFn") == want, (ls0.shape, type(loss.grad_fn).__name__)
+            else:
+                scale = ls.exp().mean()
+                li = scale * i @ t.t()
+                gt = torch.arange(3, device="cuda")
+                loss = (F.cross_entropy(li, gt) + F.cross_entropy(li.t(), gt)) / 2
+            loss.backward()
+            out += [loss.detach(), li.detach(), scale.detach(), ls.grad, i.grad, t.grad]
+        assert abs(float(got[0]) - float(ref[0])) <= 1e-5 * max(1.0, abs(float(ref[0])))
+        assert_close(got[1], ref[1], 1e-5, 1e-5, "logits")
+        assert abs(float(got[2]) - float(ref[2])) <= 1e-5 * float(ref[2])
+        assert float((got[3] - ref[3]).abs().max()) <= 1e-4 * max(1.0, float(ref[3].abs().max()))
+        assert_close(got[4], ref[4], 1e-4, 1e-6, "d img")
+        assert_close(got[5], ref[5], 1e-4, 1e-6, "d txt")
+
+    # ---- feature_views / row_range: width a multiple of 4, grad enabled and required
+    B, T, I = 2, 3, 2
+    for D, grad, want in ((8, True, "kernel"), (6, True, "torch"), (8, False, "torch")):
+        x0 = randn(B * T + B * I, D)
+        xa, xb = x0.clone().requires_grad_(True), x0.clone().requires_grad_(True)
+        with torch.enable_grad() if grad else torch.no_grad():
+            va = engine.feature_views(xa, B, T, I)
+            ra = engine.row_range(va[0], 1, None)
+        tb, ib = xb[:B * T].view(B, T, D), xb[B * T:].view(B, I, D)
+        vb = (tb, ib, tb[:, 0], ib[:, 0])
+        assert all(torch.equal(p, q) for p, q in zip(va, vb)) and torch.equal(ra, tb[1:])
+        assert va[0].data_ptr() == xa.data_ptr() and ra.data_ptr() == va[0][1:].data_ptr()  # views either way
+        if not grad:
+            assert all(v.grad_fn is None for v in va + (ra,))
+            continue
+        assert [_ran(v, "_FeatureViewsFn") for v in va] == [want] * 4 and _ran(ra, "_RowRangeFn") == want, D
+        w = [randn(*v.shape) for v in va] + [randn(*ra.shape)]
+        (sum((p * q).sum() for p, q in zip(va, w)) + (ra * w[4]).sum()).backward()
+        (sum((p * q).sum() for p, q in zip(vb, w)) + (tb[1:] * w[4]).sum()).backward()
+        assert_close(xa.grad, xb.grad, 0.0, 1e-6, "feature_views / row_range grad D=%d" % D)
+
+
+def test_scratch_is_one_grow_only_tensor_per_kind_device_and_stream(ops):
+    """ops._scratch: the same storage twice on one stream, another under another stream, a larger one when asked for more (and
+    from then on that one for smaller requests too)."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    a = ops._scratch("test-kind", 100, dev)
+    assert a.dtype == torch.float32 and a.numel() >= 100 and a.device == dev
+    assert ops._scratch("test-kind", 100, dev).data_ptr() == a.data_ptr()
+    assert ops._scratch("test-kind", 7, dev).data_ptr() == a.data_ptr()
+    assert ops._scratch("other-kind", 100, dev).data_ptr() != a.data_ptr()
+    other = torch.cuda.Stream()
+    with torch.cuda.stream(other):
+        b = ops._scratch("test-kind", 100, dev)
+        assert b.data_ptr() != a.data_ptr() and ops._scratch("test-kind", 100, dev).data_ptr() == b.data_ptr()
+    big = ops._scratch("test-kind", a.numel() + 1000, dev)
+    assert big.numel() == a.numel() + 1000 and big.data_ptr() != a.data_ptr()
+    assert ops._scratch("test-kind", 100, dev).data_ptr() == big.data_ptr()
+    for k in [k for k in ops._SCRATCH if k[0] in ("test-kind", "other-kind")]:
+        del ops._SCRATCH[k]

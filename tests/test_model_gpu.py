@@ -978,3 +978,28 @@ def test_ten_step_trajectory_follows_the_oracle(mods, golden_dir):
     assert n_checked > 100
     print("trajectory: loss err %.2e; drift worst (update-carrying elements) %s %.3f; (all elements) %s %.3f"
           % (rec["loss max abs err over 10 steps"], worst_big[0], worst_big[1], worst_all[0], worst_all[1]))
+
+
+def test_train_step_scratch_is_the_known_kinds_at_their_sizes(mods, golden_dir, monkeypatch):
+    """After one train-mode step of the tiny ufo model, ops' one scratch cache holds exactly: the split-K workspace (B = 3: the
+    joint pass over 4B samples has 12 x 237 = 2 844 token rows, past the 2 048 from which a weight-gradient GEMM cuts its
+    reduction into slices), row slot 0 (the LayerNorms outside the blocks fold by themselves),
+    the FoldBatch arena (every block's backward), the two front-end partials and the contrastive n x n workspace -- each at the
+    size its user asks for.  Row slot 1 is absent: only an unbatched layernorm_bwd_scale takes a second region, and a step
+    always batches (_BlockFn passes its FoldBatch)."""
+    ops = importlib.import_module("vl_merging_amd.ops")
+    lib = importlib.import_module("vl_merging_amd._lib").get_lib()
+    monkeypatch.setattr(ops, "_SCRATCH", {})
+    model = build(mods, "ufo", "tiny_ufo", golden_dir, {"itm": 1, "mlm": 1, "ifm": 1}, train=True)
+    B, D = 3, 192
+    model.training_step({"vl": gpu_batch(det_batch(B, 224, 40, 1024, seed=77))}).backward()
+    torch.cuda.synchronize()
+    want = {"splitk": ops.SPLITK_WS_BYTES // 4, "row0": ops._row_ws_floats(D), "fold": ops.FoldBatch.MAX * ops._row_ws_floats(D),
+            "text_rows": max(1, lib.vlm_text_rows_bwd_ws_floats(D)), "image_rows": max(1, lib.vlm_image_rows_bwd_ws_floats(D)),
+            "contrastive": max(1, lib.vlm_contrastive_ws_floats(B))}
+    got = {}
+    for (kind, dev, stream), t in ops._SCRATCH.items():
+        assert dev == torch.cuda.current_device() and t.dtype == torch.float32
+        got.setdefault(kind, set()).add(t.numel())
+    print("scratch after one step:", sorted((k, sorted(v)) for k, v in got.items()), "entries", len(ops._SCRATCH))
+    assert got == {k: {n} for k, n in want.items()}

@@ -377,6 +377,25 @@ class RelPos:
         return self.holder["dbias_t"]
 
 
+_CONSTS = {}
+CONST_MAX = 64
+
+
+def const(key, build):
+    """The small device constant `build()` makes (a weight vector, an arange, a mask of ones), built once per `key` and never
+    written afterwards: an upload or a fill inside a step would cost a launch, a pageable copy a stall of the queue.  `key`
+    holds everything the value depends on, device included, so two callers with one key want the same tensor.  Bounded: the
+    entry that has been in longest goes when CONST_MAX are held (whoever still holds the tensor keeps it alive)."""
+    t = _CONSTS.get(key)
+    if t is None:
+        if len(_CONSTS) >= CONST_MAX:
+            del _CONSTS[next(iter(_CONSTS))]
+        t = _CONSTS[key] = build()
+    return t
+
+
+# Kept apart from const(): _TableT.backward recognises the placeholder by its address, so it must be ONE tensor per device
+# that no eviction ever replaces.
 _ZERO = {}
 
 
@@ -444,9 +463,6 @@ def make_relpos(table, index16, index16_t, index_tag=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------
-_KEEPS_CACHE = {}
-
-
 class PassCtx:
     """Static description of one pass (one `infer*` call) shared by its 12(+2) block evaluations."""
 
@@ -488,11 +504,9 @@ class PassCtx:
         if self._dp_sites is not None and i < len(self._dp_sites) and abs(self._dp_sites[i] - prob) < 1e-12:
             if self._dp_all is None:
                 S = len(self._dp_sites)
-                key = (tuple(self._dp_sites), str(device))
-                keeps = _KEEPS_CACHE.get(key)
-                if keeps is None:  # uploaded once per schedule: a pageable H2D copy inside a step would stall the queue
-                    keeps = _KEEPS_CACHE[key] = torch.tensor([1.0 - p if p > 0.0 else 1.0 for p in self._dp_sites],
-                                                             dtype=F32).to(device)
+                sites = tuple(self._dp_sites)  # the keep vector is uploaded once per schedule
+                keeps = const(("keeps", sites, str(device)),
+                              lambda: torch.tensor([1.0 - p if p > 0.0 else 1.0 for p in sites], dtype=F32).to(device))
                 streams = 2 if (self.independent_segments and s.n0 and s.n1) else 1
                 if self.uniform_source is not None:
                     # injected draws (parity tests): fp32 [streams, S, B] in [0, 1); a sample's branch is kept where
@@ -834,6 +848,28 @@ def run_block(x, plan: BlockPlan, pc: PassCtx, training: bool, hook=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# The two ends of a pass: the front-end rows, the heads' activations and the loss tail.  Each public function below sends what its
+# kernel takes to the kernel and anything else (CPU tensors, other dtypes, strides the kernel does not take) to the torch
+# formulation beside it; _kernel_rows is the one place that says what "takes" means, _rows2d the one that brings an incoming
+# gradient into that form.
+def _kernel_rows(t, dtypes=(BF16, F32), row_align=1, ptr_align=1, layout=True):
+    """May `t` go to a row kernel as it stands: a CUDA tensor of one of `dtypes` that is a matrix with unit column stride, its row
+    stride a multiple of `row_align` elements and its address of `ptr_align` bytes.  layout=False asks for device and dtype alone
+    (scalars, and functions whose autograd node lays the rows out itself)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype in dtypes):
+        return False
+    return not layout or (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % row_align == 0 and t.data_ptr() % ptr_align == 0)
+
+
+def _rows2d(g, D, dtypes=(BF16, F32), contiguous=False):
+    """An incoming gradient as the [rows, D] operand a kernel takes: fp32 unless its dtype is one of `dtypes`, unit column stride
+    (every stride dense with `contiguous`); no copy where it already is all that."""
+    g2 = g.reshape(-1, D)
+    if g2.dtype not in dtypes:
+        g2 = g2.float()
+    return g2.contiguous() if contiguous or g2.stride(1) != 1 else g2
+
+
 class _LinearFn(torch.autograd.Function):
     """y = act(x W^T + b) through the MFMA GEMM; bf16 in/out (fp32 out for act = "tanh"), wgrad accumulated into W.grad in place.
     Covers heads.py (Pooler.dense + tanh, ITMHead.fc, IFMHead.fc, MLMHead.transform.dense + GELU / decoder).  x may be a row-strided
@@ -864,11 +900,7 @@ class _LinearFn(torch.autograd.Function):
         x2, saved = ctx.saved_tensors
         weight, bias, N, Np, act = ctx.weight, ctx.bias, ctx.N, ctx.Np, ctx.act
         M, K = x2.shape
-        gy2 = gy.reshape(M, N)
-        if gy2.dtype not in (BF16, F32):
-            gy2 = gy2.float()
-        if gy2.stride(1) != 1:
-            gy2 = gy2.contiguous()
+        gy2 = _rows2d(gy, N)
         if (act is None and gy2.dtype == BF16 and gy2.stride() == (Np, 1) and gy2.storage_offset() == 0
                 and _is_padded_grad(gy2, M, Np)):
             # the fused cross-entropy's gradient: already the zero-padded bf16 [M, Np] operand (registered by _CrossEntropyFn)
@@ -924,10 +956,7 @@ class _L2NormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        x2 = x.reshape(-1, x.shape[-1])
-        if x2.stride(-1) != 1:
-            x2 = x2.contiguous()
-        y, inv = ops.l2norm_fwd(x2)
+        y, inv = ops.l2norm_fwd(_rows2d(x, x.shape[-1]))
         ctx.save_for_backward(y, inv)
         ctx.dtype, ctx.shape = x.dtype, x.shape
         return y.view(x.shape)
@@ -935,33 +964,26 @@ class _L2NormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         y, inv = ctx.saved_tensors
-        g2 = g.reshape(y.shape)
-        if g2.dtype != F32 or not g2.is_contiguous():
-            g2 = g2.float().contiguous()
-        return ops.l2norm_bwd(g2, y, inv, ctx.dtype).view(ctx.shape)
-
-
-_FUSED_LOSS = os.environ.get("VLM_FUSED_LOSS", "1") != "0"  # A/B switch: 0 = torch's cross_entropy / x / x.norm() graphs
+        return ops.l2norm_bwd(_rows2d(g, y.shape[1], (F32,), contiguous=True), y, inv, ctx.dtype).view(ctx.shape)
 
 
 def l2_normalize(x):
-    if not _FUSED_LOSS or not x.is_cuda or x.dtype not in (BF16, F32):
-        x = x.float()
-        return x / x.norm(dim=-1, keepdim=True)
-    return _L2NormFn.apply(x)
+    if _kernel_rows(x, layout=False):
+        return _L2NormFn.apply(x)
+    x = x.float()
+    return x / x.norm(dim=-1, keepdim=True)
 
 
 class _ContrastiveFn(torch.autograd.Function):
     """(loss, logits_per_image, exp(log_scale)) of the symmetric contrastive cross-entropy on normalised features, forward AND
     gradient in two launches (csrc/lossops.hip vlm_contrastive; reference objectives.py:274-300 / :393-445):
-    all_* = this rank's B rows first, then the other ranks' (no gradient through those, as in the reference).  The loss is a
-    scalar: its upstream gradient scales the stored feature / scale gradients in ONE launch (vlm_scale_by_scalar)."""
+    all_* = gather(.): this rank's B rows first, then the other ranks' (no gradient through those, as in the reference).  The loss
+    is a scalar: its upstream gradient scales the stored feature / scale gradients in ONE launch (vlm_scale_by_scalar)."""
 
     @staticmethod
-    def forward(ctx, img, txt, log_scale, others_img, others_txt):
+    def forward(ctx, img, txt, log_scale, gather):
         B = img.shape[0]
-        all_img = img if others_img is None else torch.cat([img, others_img])
-        all_txt = txt if others_txt is None else torch.cat([txt, others_txt])
+        all_img, all_txt = (img, txt) if gather is None else (gather(img), gather(txt))
         ls = log_scale.detach().reshape(1).float()
         out3, logits, d_img, d_txt = ops.contrastive(all_img.contiguous(), all_txt.contiguous(), B, ls)
         ctx.save_for_backward(out3, d_img, d_txt)
@@ -979,15 +1001,25 @@ class _ContrastiveFn(torch.autograd.Function):
         gs = gs.view(ctx.ls_shape)
         if g_scale is not None:  # somebody differentiates the returned scale itself (d exp(l) / d l = exp(l)): not on the hot path
             gs = gs + (g_scale * out3[2]).view(ctx.ls_shape)
-        return gi, gt, gs, None, None
+        return gi, gt, gs, None
 
 
-def contrastive_loss(img, txt, log_scale, others_img=None, others_txt=None):
-    """loss, logits_per_image [n, n], exp(log_scale): img / txt = this rank's normalised fp32 features [B, D]."""
-    return _ContrastiveFn.apply(img, txt, log_scale, others_img, others_txt)
+_FLOATS = (BF16, F32, torch.float16, torch.float64)
 
 
-_WVEC = {}
+def contrastive_loss(img, txt, log_scale, gather=None):
+    """(loss, logits_per_image [n, n], exp(log_scale)) of the symmetric contrastive cross-entropy on this rank's normalised
+    features img / txt [B, D] (reference objectives.py:274-300).  `gather(t)`: t's rows first, the other ranks' behind them
+    (None: one rank).  CUDA features and ONE log_scale: two launches, forward and gradient; otherwise the reference's torch
+    formulation."""
+    if _kernel_rows(img, _FLOATS, layout=False) and log_scale.numel() == 1:
+        return _ContrastiveFn.apply(img.float(), txt.float(), log_scale, gather)
+    logit_scale = log_scale.exp().mean()
+    all_img, all_txt = (img, txt) if gather is None else (gather(img), gather(txt))
+    li = logit_scale * all_img @ all_txt.t()
+    gt = torch.arange(len(li), device=li.device)
+    loss = (torch.nn.functional.cross_entropy(li.float(), gt) + torch.nn.functional.cross_entropy(li.t().float(), gt)) / 2
+    return loss, li, logit_scale
 
 
 class _WeightedSumFn(torch.autograd.Function):
@@ -1004,13 +1036,7 @@ class _WeightedSumFn(torch.autograd.Function):
         w = ctx.weights
         if all(x == 1.0 for x in w):
             return (None,) + (g,) * len(w)
-        key = (w, str(ctx.dev))
-        wv = _WVEC.get(key)
-        if wv is None:
-            if len(_WVEC) > 64:
-                _WVEC.clear()
-            wv = _WVEC[key] = torch.tensor(w, dtype=F32).to(ctx.dev)
-        gw = g * wv  # one launch for all terms
+        gw = g * const(("weights", w, str(ctx.dev)), lambda: torch.tensor(w, dtype=F32).to(ctx.dev))  # one launch for all terms
         return (None,) + tuple(gw[k] for k in range(len(w)))
 
 
@@ -1019,7 +1045,7 @@ def weighted_sum(terms, weights=None):
     goes through torch."""
     terms = list(terms)
     weights = tuple(float(w) for w in (weights if weights is not None else [1.0] * len(terms)))
-    if (_FUSED_LOSS and 1 <= len(terms) <= 8 and all(torch.is_tensor(t) and t.is_cuda and t.dtype == F32 and t.numel() == 1 for t in terms)):
+    if 1 <= len(terms) <= 8 and all(_kernel_rows(t, (F32,), layout=False) and t.numel() == 1 for t in terms):
         return _WeightedSumFn.apply(weights, *terms)
     out = 0
     for t, w in zip(terms, weights):
@@ -1045,8 +1071,7 @@ class _SmallCrossEntropyFn(torch.autograd.Function):
 
 
 def small_cross_entropy(logits, labels):
-    if (_FUSED_LOSS and logits.is_cuda and logits.dim() == 2 and logits.dtype in (BF16, F32) and logits.stride(1) == 1
-            and logits.shape[1] <= 64 and labels.dtype == torch.int64):
+    if _kernel_rows(logits) and logits.shape[1] <= 64 and labels.dtype == torch.int64:
         return _SmallCrossEntropyFn.apply(logits, labels.contiguous())
     return torch.nn.functional.cross_entropy(logits.float(), labels)
 
@@ -1090,8 +1115,7 @@ class _CrossEntropyFn(torch.autograd.Function):
 def cross_entropy(logits, labels, ignore_index=-100):
     """F.cross_entropy(logits.float(), labels, ignore_index=ignore_index) for 2-D bf16 CUDA logits whose rows are 16-B aligned (the
     MLM head's); anything else goes to torch."""
-    if (_FUSED_LOSS and logits.is_cuda and logits.dtype == BF16 and logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) % 8 == 0
-            and logits.data_ptr() % 16 == 0 and labels.dtype == torch.int64):
+    if _kernel_rows(logits, (BF16,), 8, 16) and labels.dtype == torch.int64:
         return _CrossEntropyFn.apply(logits, labels.contiguous(), ignore_index)
     return torch.nn.functional.cross_entropy(logits.float(), labels, ignore_index=ignore_index)
 
@@ -1115,9 +1139,7 @@ class _LayerNormFn(torch.autograd.Function):
     def backward(ctx, gy):
         x2, st = ctx.saved_tensors
         M, D = x2.shape
-        g2 = gy.reshape(M, D).contiguous()
-        if g2.dtype not in (BF16, F32):
-            g2 = g2.float()
+        g2 = _rows2d(gy, D, contiguous=True)
         dx = torch.empty(M, D, device=x2.device, dtype=F32)
         touch(ctx.weight if ctx.weight.requires_grad else None, ctx.bias if ctx.bias.requires_grad else None)
         ops.layernorm_bwd(g2, x2, st, ctx.weight, dx, dgamma=ctx.weight.grad if ctx.weight.requires_grad else None,
@@ -1127,13 +1149,6 @@ class _LayerNormFn(torch.autograd.Function):
 
 def layer_norm(x, weight, bias, eps, out_f32=False):
     return _LayerNormFn.apply(x, weight, bias, eps, out_f32)
-
-
-def _rows2d(g, D):
-    g2 = g.reshape(-1, D)
-    if g2.dtype not in (BF16, F32):
-        g2 = g2.float()
-    return g2 if g2.stride(1) == 1 else g2.contiguous()
 
 
 class _FeatureViewsFn(torch.autograd.Function):
@@ -1178,7 +1193,7 @@ def feature_views(x, B, T, I):
     _FeatureViewsFn.  Falls back to plain views where the kernel does not apply (CPU, a width that is not a multiple of 4)."""
     D = x.shape[1]
     nt = B * T
-    if x.is_cuda and x.is_contiguous() and x.dtype in (BF16, F32) and D % 4 == 0 and torch.is_grad_enabled() and x.requires_grad:
+    if _kernel_rows(x) and x.is_contiguous() and D % 4 == 0 and torch.is_grad_enabled() and x.requires_grad:
         return _FeatureViewsFn.apply(x, B, T, I)
     text, image = x[:nt].view(B, T, D), x[nt:].view(B, I, D)
     return text, image, text[:, 0], image[:, 0]
@@ -1204,7 +1219,7 @@ class _RowRangeFn(torch.autograd.Function):
 
 def row_range(t, a, b):
     """t[a:b] (first dim); on the GPU with a one-launch backward (objectives.py: `infer["text_feats"][:bsz]`, `cls_feats[bsz:]`)."""
-    if (t.is_cuda and t.dim() >= 2 and t.is_contiguous() and t.dtype in (BF16, F32) and t.shape[-1] % 4 == 0 and torch.is_grad_enabled()
+    if (_kernel_rows(t, layout=False) and t.dim() >= 2 and t.is_contiguous() and t.shape[-1] % 4 == 0 and torch.is_grad_enabled()
             and t.requires_grad):
         return _RowRangeFn.apply(t, a, t.shape[0] if b is None else b)
     return t[a:b]
@@ -1226,10 +1241,8 @@ class _EmbeddingFn(torch.autograd.Function):
         w = ctx.weight
         if w.requires_grad:
             touch(w)
-            g2 = gy.reshape(-1, gy.shape[-1])
-            if g2.dtype != F32 or g2.stride(1) != 1:
-                g2 = g2.float().contiguous()
-            ops.embedding_bwd(g2, ids.reshape(-1).contiguous(), w.grad, -1 if ctx.padding_idx is None else ctx.padding_idx)
+            ops.embedding_bwd(_rows2d(gy, gy.shape[-1], (F32,)), ids.reshape(-1).contiguous(), w.grad,
+                              -1 if ctx.padding_idx is None else ctx.padding_idx)
         return None, None, None
 
 
@@ -1348,8 +1361,7 @@ class _PassRowsFn(torch.autograd.Function):
         stats = saved.pop(0) if ctx.has[1] else None
         weight, bias, cls, tt, text = ctx.weight, ctx.bias, ctx.cls, ctx.tt, ctx.text
         B, rows, Dm, nt, tt_idx = ctx.geom
-        if gx.dtype != F32 or gx.stride(1) != 1:
-            gx = gx.float().contiguous()
+        gx = _rows2d(gx, Dm, (F32,))
         if cols is not None:
             touch(*[p for p in (weight, bias, cls, tt) if p is not None and p.requires_grad])
             g16 = ops.image_rows_bwd(gx[nt:], B, rows, _g(bias), _g(tt)[tt_idx] if _g(tt) is not None else None, _g(cls))

@@ -21,6 +21,48 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+_SCRATCH = {}
+
+
+def _scratch(kind, floats, device):
+    """The fp32 scratch `kind` on `device`, at least `floats` elements, for work issued on torch's current stream: one tensor
+    per (kind, device, stream) -- launches of one stream run in order and may share it, two streams never do -- that only ever
+    grows (the tensor it replaces lives until the launches already reading it are through: the allocator is stream-ordered)."""
+    key = (kind, device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _SCRATCH.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _SCRATCH[key] = torch.empty(floats, device=device, dtype=F32)
+    return ws
+
+
+# the "splitk" scratch: the wgrad GEMM's K slices (vlm_epilogue_t.splitk_ws), fp32 [slice][M][N] tiles, at most 256 CUs / tiles
+# slices of an M x N <= 3072 x 768 weight -- 66 MB at the base width
+SPLITK_WS_BYTES = 96 << 20
+
+
+def _epilogue(N, *, bias=None, col_scale=None, row_scale=None, residual=None, aux=None, act=L.ACT_NONE, alpha=1.0, accumulate=False,
+              col_sum=None):
+    """The vlm_epilogue_t of a GEMM with N output columns, its tensors checked (include/vlm_hip.h has the algebra)."""
+    e = L.Epilogue()
+    e.bias = bias.data_ptr() if bias is not None else 0
+    e.col_scale = col_scale.data_ptr() if col_scale is not None else 0
+    e.row_scale = row_scale.data_ptr() if row_scale is not None else 0
+    e.residual = residual.data_ptr() if residual is not None else 0
+    e.ld_res = _ld(residual) if residual is not None else 0
+    e.aux = aux.data_ptr() if aux is not None else 0
+    e.ld_aux = _ld(aux) if aux is not None else 0
+    e.act = act
+    e.alpha = alpha
+    e.accumulate = 1 if accumulate else 0
+    e.col_sum = col_sum.data_ptr() if col_sum is not None else 0
+    if col_sum is not None and (col_sum.numel() < N or not col_sum.is_contiguous()):
+        raise L.VlmError("gemm: col_sum must be a contiguous f32 vector of at least N elements")
+    for t, dt in ((bias, F32), (col_scale, F32), (row_scale, F32), (residual, F32), (aux, BF16), (col_sum, F32)):
+        if t is not None and t.dtype != dt:
+            raise L.VlmError("gemm epilogue tensor has dtype %s, expected %s" % (t.dtype, dt))
+    return e
+
+
 def gemm(a, b, out, ta=False, tb=False, *, bias=None, act=L.ACT_NONE, aux=None, col_scale=None, row_scale=None,
          residual=None, alpha=1.0, accumulate=False, col_sum=None, col_sum_fold=None):
     """out[M,N] = epilogue(op(a)[M,K] @ op(b)[K,N]); see include/vlm_hip.h for the epilogue algebra.
@@ -37,18 +79,8 @@ def gemm(a, b, out, ta=False, tb=False, *, bias=None, act=L.ACT_NONE, aux=None, 
     kb, nb = (b.shape[0], b.shape[1]) if tb else (b.shape[1], b.shape[0])
     if nb != N or kb != K:
         raise L.VlmError("gemm: B shape %s incompatible with N=%d K=%d" % (tuple(b.shape), N, K))
-    e = L.Epilogue()
-    e.bias = bias.data_ptr() if bias is not None else 0
-    e.col_scale = col_scale.data_ptr() if col_scale is not None else 0
-    e.row_scale = row_scale.data_ptr() if row_scale is not None else 0
-    e.residual = residual.data_ptr() if residual is not None else 0
-    e.ld_res = _ld(residual) if residual is not None else 0
-    e.aux = aux.data_ptr() if aux is not None else 0
-    e.ld_aux = _ld(aux) if aux is not None else 0
-    e.act = act
-    e.alpha = alpha
-    e.accumulate = 1 if accumulate else 0
-    e.col_sum = col_sum.data_ptr() if col_sum is not None else 0
+    e = _epilogue(N, bias=bias, col_scale=col_scale, row_scale=row_scale, residual=residual, aux=aux, act=act, alpha=alpha,
+                  accumulate=accumulate, col_sum=col_sum)
     region = None
     if col_sum is not None and col_sum_fold is not None and not ta and N % 128 == 0 and M >= 128:
         # complete 128-row tiles park their column sums in the fold batch's scratch (plain stores), one
@@ -59,14 +91,9 @@ def gemm(a, b, out, ta=False, tb=False, *, bias=None, act=L.ACT_NONE, aux=None, 
         else:
             region = None
     if ta and tb and out.dtype == F32 and K >= 2048 and bias is None and col_sum is None:
-        ws = _splitk_workspace(out.device)
+        ws = _scratch("splitk", SPLITK_WS_BYTES // 4, out.device)
         e.splitk_ws = ws.data_ptr()
         e.splitk_ws_bytes = ws.numel() * 4
-    if col_sum is not None and (col_sum.numel() < N or not col_sum.is_contiguous()):
-        raise L.VlmError("gemm: col_sum must be a contiguous f32 vector of at least N elements")
-    for t, dt in ((bias, F32), (col_scale, F32), (row_scale, F32), (residual, F32), (aux, BF16), (col_sum, F32)):
-        if t is not None and t.dtype != dt:
-            raise L.VlmError("gemm epilogue tensor has dtype %s, expected %s" % (t.dtype, dt))
     if out.dtype not in (BF16, F32):
         raise L.VlmError("gemm output must be bf16 or f32")
     rc = L.get_lib().vlm_gemm_bf16(int(ta), int(tb), M, N, K, L.ptr(a), _ld(a), L.ptr(b), _ld(b), L.ptr(out), _ld(out),
@@ -91,18 +118,7 @@ def gemm_grouped(a, groups, out, *, act=L.ACT_NONE, aux=None, col_scale=None, ro
     K = a.shape[1]
     if a.shape[0] != M:
         raise L.VlmError("gemm_grouped: A rows %s do not match M=%d" % (tuple(a.shape), M))
-    e = L.Epilogue()
-    e.col_scale = col_scale.data_ptr() if col_scale is not None else 0
-    e.row_scale = row_scale.data_ptr() if row_scale is not None else 0
-    e.residual = residual.data_ptr() if residual is not None else 0
-    e.ld_res = _ld(residual) if residual is not None else 0
-    e.aux = aux.data_ptr() if aux is not None else 0
-    e.ld_aux = _ld(aux) if aux is not None else 0
-    e.act = act
-    e.alpha = alpha
-    for t, dt in ((col_scale, F32), (row_scale, F32), (residual, F32), (aux, BF16)):
-        if t is not None and t.dtype != dt:
-            raise L.VlmError("gemm epilogue tensor has dtype %s, expected %s" % (t.dtype, dt))
+    e = _epilogue(N, col_scale=col_scale, row_scale=row_scale, residual=residual, aux=aux, act=act, alpha=alpha)
     if out.dtype not in (BF16, F32):
         raise L.VlmError("gemm output must be bf16 or f32")
     arr = (L.GemmGroup * len(groups))()
@@ -153,24 +169,10 @@ def gemm_wgrad_grouped(dy, x, groups, accumulate=True):
         ldc = _ld(dW)
         prev = r1
         g.row0, g.rows, g.C, g.accumulate = r0, r1 - r0, dW.data_ptr(), int(bool(accumulate))
-    ws = _splitk_workspace(dy.device)
+    ws = _scratch("splitk", SPLITK_WS_BYTES // 4, dy.device)
     rc = L.get_lib().vlm_gemm_wgrad_grouped(len(groups), arr, M, N, L.ptr(dy), _ld(dy), L.ptr(x), _ld(x), ldc, L.ptr(ws),
                                             ws.numel() * 4, L.stream_ptr())
     L.check(rc, "vlm_gemm_wgrad_grouped")
-
-
-_SPLITK_WS = {}
-SPLITK_WS_BYTES = 96 << 20
-
-
-def _splitk_workspace(device):
-    """Per (device, stream) scratch for the wgrad GEMM's K slices (vlm_epilogue_t.splitk_ws): fp32 [slice][M][N] tiles,
-    at most 256 CUs / tiles slices of an M x N <= 3072 x 768 weight -- 66 MB at the base width."""
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _SPLITK_WS.get(key)
-    if ws is None:
-        ws = _SPLITK_WS[key] = torch.empty(SPLITK_WS_BYTES // 4, device=device, dtype=F32)
-    return ws
 
 
 def layernorm_fwd(x, gamma, beta, eps, out, stats=None):
@@ -182,22 +184,10 @@ def layernorm_fwd(x, gamma, beta, eps, out, stats=None):
     return out
 
 
-_ROW_WS = {}
-
-
 def _row_ws_floats(D):
-    """One partial region, VLM_ROW_WS_BYTES(D) / 4, never below the D = 1024 size: one allocation serves every width."""
+    """One region of the row kernels' per-workgroup column partials, VLM_ROW_WS_BYTES(D) / 4, never below the D = 1024 size: one
+    allocation serves every width."""
     return 1536 * 2 * max(D, 1024)
-
-
-def _row_workspace(device, D, slot=0):
-    """Per-device scratch for the row kernels' per-workgroup column partials; slot 1: the second partial region of a fused
-    call."""
-    key = (device.index, torch.cuda.current_stream().cuda_stream, slot)
-    ws = _ROW_WS.get(key)
-    if ws is None or ws.numel() < _row_ws_floats(D):
-        ws = _ROW_WS[key] = torch.empty(_row_ws_floats(D), device=device, dtype=F32)
-    return ws
 
 
 class FoldBatch:
@@ -208,11 +198,7 @@ class FoldBatch:
 
     def __init__(self, device, D=1024):
         self.region = _row_ws_floats(D)
-        key = ("fold", device.index, torch.cuda.current_stream().cuda_stream)
-        ws = _ROW_WS.get(key)
-        if ws is None or ws.numel() < self.MAX * self.region:
-            ws = _ROW_WS[key] = torch.empty(self.MAX * self.region, device=device, dtype=F32)
-        self.ws = ws
+        self.ws = _scratch("fold", self.MAX * self.region, device)
         self.jobs = []
         self.taken = 0  # regions handed out since the last flush (a region whose job turned out empty stays taken)
 
@@ -247,10 +233,12 @@ class FoldBatch:
 
 def _row_bwd(name, fold, device, D, head, pairs, sc=None):
     """Call the backward row kernel `name`(*head, workspace, bytes[, scale], deferred_blocks, stream) with one partial region
-    per column-sum pair (out0, out1): regions of the batch and a job each when the fold is deferred, else the private
-    scratch and deferred_blocks = NULL (the call folds by itself).  The call reports its grid whenever ANY pair left
-    partials (a frozen LayerNorm, no dgamma / dbeta, still leaves the LayerScale's): only a pair with an output has a job."""
-    ws = fold.next_regions(len(pairs)) if fold is not None else [_row_workspace(device, D, slot=k) for k in range(len(pairs))]
+    per column-sum pair (out0, out1): regions of the batch and a job each when the fold is deferred, else the scratch "row0"
+    ("row1": the second pair of a fused call) and deferred_blocks = NULL (the call folds by itself).  The call reports its grid
+    whenever ANY pair left partials (a frozen LayerNorm, no dgamma / dbeta, still leaves the LayerScale's): only a pair with an
+    output has a job."""
+    ws = (fold.next_regions(len(pairs)) if fold is not None
+          else [_scratch("row%d" % k, _row_ws_floats(D), device) for k in range(len(pairs))])
     nb = ctypes.c_int(0)
     tail = (ctypes.byref(nb) if fold is not None else None, L.stream_ptr())
     if sc is not None:
@@ -372,7 +360,7 @@ def contrastive(all_img, all_txt, B, log_scale):
     out3 = torch.empty(3, device=dev, dtype=F32)
     d_img = torch.empty(B, D, device=dev, dtype=F32)
     d_txt = torch.empty(B, D, device=dev, dtype=F32)
-    ws = torch.empty(max(1, L.get_lib().vlm_contrastive_ws_floats(n)), device=dev, dtype=F32)
+    ws = _scratch("contrastive", max(1, L.get_lib().vlm_contrastive_ws_floats(n)), dev)
     L.check(L.get_lib().vlm_contrastive(L.ptr(all_img), L.ptr(all_txt), n, B, D, L.ptr(log_scale), L.ptr(logits), L.ptr(out3), L.ptr(d_img),
                                         L.ptr(d_txt), L.ptr(ws), L.stream_ptr()), "vlm_contrastive")
     return out3, logits, d_img, d_txt
@@ -416,20 +404,6 @@ def scale_by_scalar(tensors, scalar):
     return outs
 
 
-_FRONT_WS = {}
-
-
-def _front_ws(kind, D, device):
-    """Per-(kind, D, device) scratch of the front-end backward kernels (column partials, folded in the same call)."""
-    key = (kind, D, str(device))
-    ws = _FRONT_WS.get(key)
-    if ws is None:
-        lib = L.get_lib()
-        n = lib.vlm_text_rows_bwd_ws_floats(D) if kind == "text" else lib.vlm_image_rows_bwd_ws_floats(D)
-        ws = _FRONT_WS[key] = torch.empty(max(1, n), device=device, dtype=F32)
-    return ws
-
-
 def _rowvec(t, D, what):
     if t is None:
         return 0
@@ -464,11 +438,12 @@ def text_rows_bwd(g, ids, word, add0, gamma, stats, u, p, scale, d_word, padding
         raise L.VlmError("text_rows_bwd: fp32 gradient rows with unit column stride")
     if d_word is not None and (d_word.dtype != F32 or d_word.shape != word.shape or d_word.stride() != word.stride()):
         raise L.VlmError("text_rows_bwd: d_word has the word table's layout")
+    ws = _scratch("text_rows", max(1, L.get_lib().vlm_text_rows_bwd_ws_floats(D)), g.device)  # column partials, folded in the same call
     L.check(L.get_lib().vlm_text_rows_bwd(L.ptr(g), _ld(g), L.ptr(ids), n, L.ptr(word), _ld(word), _rowvec(add0, D, "add0"),
                                           _rowvec(gamma, D, "gamma"), L.ptr(stats), L.ptr(u) if u is not None else 0, float(p), float(scale), D,
                                           L.ptr(d_word) if d_word is not None else 0, -1 if padding_idx is None else int(padding_idx),
                                           _rowvec(d_add1, D, "d_add1"), _rowvec(d_beta, D, "d_beta"), _rowvec(d_gamma, D, "d_gamma"),
-                                          _rowvec(d_add0, D, "d_add0"), L.ptr(_front_ws("text", D, g.device)), L.stream_ptr()),
+                                          _rowvec(d_add0, D, "d_add0"), L.ptr(ws), L.stream_ptr()),
             "vlm_text_rows_bwd")
 
 
@@ -499,9 +474,10 @@ def image_rows_bwd(g, B, rows, d_bias, d_type_row, d_cls):
     if g.dtype != F32 or g.stride(1) != 1 or n != B * rows:
         raise L.VlmError("image_rows_bwd: fp32 [B * rows, D] gradient rows")
     g16 = torch.empty(n, D, device=g.device, dtype=BF16)
+    ws = _scratch("image_rows", max(1, L.get_lib().vlm_image_rows_bwd_ws_floats(D)), g.device)
     L.check(L.get_lib().vlm_image_rows_bwd(L.ptr(g), _ld(g), B, rows, D, L.ptr(g16), _rowvec(d_bias, D, "d_bias"),
                                            _rowvec(d_type_row, D, "d_type_row"), _rowvec(d_cls.reshape(-1) if d_cls is not None else None, D, "d_cls"),
-                                           L.ptr(_front_ws("image", D, g.device)), L.stream_ptr()), "vlm_image_rows_bwd")
+                                           L.ptr(ws), L.stream_ptr()), "vlm_image_rows_bwd")
     return g16
 
 

@@ -65,51 +65,23 @@ def compute_mlm(pl_module, batch):
             "mlm_labels": mlm_labels, "mlm_ids": infer["text_ids"]}
 
 
-def _others(t):
-    """The other ranks' rows of a feature matrix (no autograd), in rank order without this rank's: what _gather_first_own appends."""
-    world, rank = _world()
-    if world == 1:
-        return None
-    gathered = [torch.zeros_like(t) for _ in range(world)]
-    dist.all_gather(gathered, t.detach().contiguous())
-    return torch.cat(gathered[:rank] + gathered[rank + 1:])
-
-
 def _contrastive_pair(image_features, text_features, log_scale_param):
     """(loss, logits_per_image, logits_per_text, exp(scale)) of the symmetric contrastive cross-entropy (objectives.py:274-300):
-    own features first, the gathered ones behind them without gradient.  GPU: engine.contrastive_loss (two launches, forward
-    and gradient); otherwise the reference's torch formulation."""
-    if image_features.is_cuda and engine._FUSED_LOSS and log_scale_param.numel() == 1:
-        loss, li, scale = engine.contrastive_loss(image_features.float(), text_features.float(), log_scale_param,
-                                                  _others(image_features.float()), _others(text_features.float()))
-        return loss, li, li.t(), scale
-    logit_scale = log_scale_param.exp().mean()
-    all_img = _gather_first_own(image_features)
-    all_txt = _gather_first_own(text_features)
-    li = logit_scale * all_img @ all_txt.t()
-    gt = torch.arange(len(li), device=li.device)
-    return (F.cross_entropy(li.float(), gt) + F.cross_entropy(li.t().float(), gt)) / 2, li, li.t(), logit_scale
+    own features first, the gathered ones behind them without gradient (engine.contrastive_loss)."""
+    loss, li, scale = engine.contrastive_loss(image_features, text_features, log_scale_param, _gather_first_own)
+    return loss, li, li.t(), scale
 
 
 def _itm_labels(bsz, device):
     """(float, int64) labels of the ITM head: B positives then 2B negatives (objectives.py:187-190); built once per batch size."""
-    key = ("itm", bsz, str(device))
-    t = _ARANGE.get(key)
-    if t is None:
+    def build():
         f = torch.cat([torch.ones(bsz, device=device), torch.zeros(2 * bsz, device=device)])
-        t = _ARANGE[key] = (f, f.long())
-    return t
+        return f, f.long()
+    return engine.const(("itm", bsz, str(device)), build)
 
 
 def _labels_arange(n, device):
-    key = (n, str(device))
-    t = _ARANGE.get(key)
-    if t is None:
-        t = _ARANGE[key] = torch.arange(n, device=device)
-    return t
-
-
-_ARANGE = {}
+    return engine.const(("arange", n, str(device)), lambda: torch.arange(n, device=device))
 
 
 def compute_ifm(pl_module, batch, aggregate=True):

@@ -193,10 +193,9 @@ class ViLTransformerSS(nn.Module):
         self.current_tasks = []
         self.fuse_joint_passes = True  # engine option, not a reference config key
         # engine option: image-only + text-only pass of a batch as one block-diagonal pass (infer_unimodal_pair)
-        self.fuse_unimodal_passes = os.environ.get("VLM_FUSE_UNIMODAL", "1") != "0"
+        self.fuse_unimodal_passes = True
         self._flat = None
         self._idx_cache = {}
-        self._ones_cache = {}
         self._grad_hook = None
         self._gram = None
         self.trainer = None
@@ -403,12 +402,10 @@ class ViLTransformerSS(nn.Module):
         I = 1 + pe.num_patches if img.shape[-1] == pe.img_size[1] and img.shape[-2] == pe.img_size[0] \
             else 1 + (img.shape[-2] // pe.patch_size[0]) * (img.shape[-1] // pe.patch_size[1])
         dt = mask_like.dtype if mask_like is not None else torch.float32
-        key = (img.shape[0], I, dt, str(img.device))
-        ones = self._ones_cache.get(key)
-        if ones is None:  # a constant: one fill per geometry instead of one (plus a cast) per pass
-            if len(self._ones_cache) > 16:
-                self._ones_cache.clear()
-            ones = self._ones_cache[key] = torch.ones(img.shape[0], I, device=img.device, dtype=dt)
+        # a constant: one fill per geometry instead of one (plus a cast) per pass.  The key is all the value depends on, so models
+        # that share an entry share the same ones
+        ones = engine.const(("ones", img.shape[0], I, dt, str(img.device)),
+                            lambda: torch.ones(img.shape[0], I, device=img.device, dtype=dt))
         return x, ones, I
 
     def _final_norm(self, x):

@@ -140,6 +140,70 @@ int vlm_ties_plan_upload(const vlm_ties_job_t* jobs_host, int n_jobs, void* work
 int vlm_ties_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DARE merge (drop and rescale; Yu et al. 2023, "Language Models are Super Mario"), csrc/dare.hip.  NO REFERENCE SITE: the
+ * reference has no DARE; the arithmetic below is the specification and is pinned to a numpy restatement of it
+ * (tests/dare_restatement.py), not to the reference.  One job = one output tensor with central tensor c (base), sources
+ * W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), scalars lam and rescale (fp32), keep_below (in [1, 2^32]), seed, stream, mode;
+ * fp32, one rounding per operation, no FMA, source order:
+ *   1. t_m = W_m - c
+ *   2. the draw of element i of source m:  u_m[i] = word (i & 3) of Philox4x32-10 with counter (i >> 2, 0, m, stream) and
+ *      key (seed & 0xffffffff, seed >> 32): multipliers 0xD2511F53 (on counter word 0) and 0xCD9E8D57 (on counter word 2), key
+ *      increments 0x9E3779B9 and 0xBB67AE85, ten rounds, the key bumped after each (csrc/philox.h).  i >> 2 < 2^32 always.
+ *      One Philox call serves one float4 of one source; the ragged end of a tensor uses the same definition.
+ *   3. kept = (uint64) u_m[i] < keep_below;  tt_m = t_m * rescale if kept else +0.0
+ *   4. VLM_DARE_LINEAR: d = ((0 + tt_0) + tt_1) + ...
+ *      VLM_DARE_TIES:   steps 3-4 of the TIES rule above on these tt_m (sign elected by comparison of the sum; d = mean of
+ *                       the agreeing entries, +0.0 if none agrees)
+ *   5. dst = c + lam * d
+ * The mask costs no memory and a draw is a pure function of (seed, stream, m, i): the result does not depend on the grid, the
+ * chunking, the position of the job in a plan or how often the plan runs.
+ * Counters per job (uint64; integer atomics only): kept[0 .. MAX_SRC), then `conflict` = elements whose kept entries hold both a
+ * positive and a negative value (tt_m > 0, tt_m < 0; both modes), then `empty` = elements where no source is kept (LINEAR) or
+ * none agrees (TIES).
+ * The pass is elementwise: dst may be EXACTLY base or EXACTLY one of the job's sources; any other overlap of dst's byte range with
+ * an input's is VLM_ERR_ARG (overlap ACROSS jobs is the caller's to avoid).  Non-finite inputs are outside the contract.
+ */
+#define VLM_DARE_LINEAR 0
+#define VLM_DARE_TIES 1
+
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each */
+  uint64_t keep_below;                  /* step 3: 1 .. 2^32; 2^32 keeps everything */
+  uint64_t seed;
+  uint64_t n_elem;
+  int32_t n_src;
+  int32_t mode;                         /* VLM_DARE_LINEAR | VLM_DARE_TIES */
+  float lam;
+  float rescale;                        /* step 3: the caller's 1 / (1 - p), or 1 */
+  uint32_t stream;                      /* counter word 3: which tensor */
+  uint32_t reserved;
+} vlm_dare_job_t;
+
+/* The workspace of a DARE plan BEGINS with this header (byte offsets from its start); jobs keep their upload order. */
+typedef struct {
+  uint64_t n_jobs, n_chunks;
+  uint64_t jobs_off;      /* vlm_dare_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table */
+  uint64_t counters_off;  /* uint64 [n_jobs][VLM_DARE_COUNTERS]: kept per source, conflict, empty */
+} vlm_dare_header_t;
+#define VLM_DARE_COUNTERS (VLM_MERGE_MAX_SRC + 2)
+
+/* Bytes of device workspace a DARE plan for n_jobs jobs over total_elems elements needs (header, jobs, chunk table, counters).
+ * No reference site. */
+size_t vlm_dare_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (the checks of vlm_ties_plan_upload, except that dst may equal base or a source exactly; plus keep_below in
+ * [1, 2^32] and a valid mode), build the chunk table on the host and copy header + jobs + table into `workspace` (16-byte
+ * aligned).  SYNCHRONISES `stream` before it returns (pageable temporary source); it is the last host synchronisation of a plan.
+ * Implements no step of the rule; no reference site. */
+int vlm_dare_plan_upload(const vlm_dare_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: a tiny launch that zeroes the counters, then ONE streaming launch over all jobs (steps 1-5 and the
+ * counters); no host synchronisation.  May be called again on the same workspace and gives the same bytes and counters.  One run
+ * at a time per workspace.  No reference site. */
+int vlm_dare_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

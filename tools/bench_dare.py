@@ -1,0 +1,83 @@
+#!/usr/bin/env python
+"""Base-size all_moe -> ufo (the inputs tests/test_merge_gpu.py::test_merge_base_size_digests builds): the task-vector merge
+(sum_task_vectors' plan) and the DARE merge over the same inputs in one process, 20 stream-timed runs each after warm-up, medians;
+GB/s for both and t_dare / t_taskvec.  `--mode both` times the linear and the ties plan.  The split by kernel is what
+`rocprofv3 --kernel-trace --stats -- python tools/bench_dare.py` prints.  Prints ONE JSON line.  `--out FILE` also writes it to FILE."""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as ge  # noqa: E402
+
+
+def timed(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return statistics.median(ms), min(ms)
+
+
+def main(argv):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--drop", type=float, default=0.9)
+    ap.add_argument("--seed", type=int, default=20231106)
+    ap.add_argument("--mode", choices=("linear", "ties", "both"), default="both")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    ge.import_package()
+    merge = importlib.import_module("vl_merging_amd.merge")
+    from oracle import synth
+    from oracle.detweights import det_array
+    torch.cuda.set_device(0)
+    sd = {k: torch.from_numpy(det_array(k, s)).cuda() for k, (s, dt) in synth.block_shapes(768, 3072, "all_moe").items()}
+    central = {k: torch.from_numpy(det_array(k, s, 7)).cuda() for k, (s, dt) in synth.block_shapes(768, 3072, "ufo").items()}
+    cfg = dict(vlffn_start_layer_index=10, only_activate_used_experts=False, merge_ratio=0.5, sum_lambda=0.75, loss_names={})
+    tv = []
+    merge.sum_task_vectors(sd, cfg, central_weight=central, plan_out=tv)
+    tv = tv[0]
+    tv_ms, tv_min = timed(tv.run, args.reps)
+    tv_bytes = tv.bytes_read + tv.bytes_written
+    res = {"workload": "base all_moe -> ufo, 156 tensors", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+           "taskvec": {"ms_median": tv_ms, "ms_min": tv_min, "bytes": tv_bytes, "GBps": tv_bytes / tv_ms / 1e6}}
+    for mode in (("linear", "ties") if args.mode == "both" else (args.mode,)):
+        da = []
+        merge.dare_merge(sd, cfg, central_weight=central, drop=args.drop, seed=args.seed, mode=mode, plan_out=da)
+        da = da[0]
+        ms, ms_min = timed(da.run, args.reps)
+        nbytes = da.bytes_read + da.bytes_written
+        rep = da.report()
+        n = sum(r["n"] for r in rep)
+        res["dare_" + mode] = {"drop": args.drop, "seed": args.seed, "launches": 2, "ms_median": ms, "ms_min": ms_min, "bytes": nbytes,
+                               "GBps": nbytes / ms / 1e6, "ms_vs_taskvec": ms / tv_ms,
+                               "kept_fraction": sum(sum(r["kept"]) for r in rep) / sum(r["n"] * len(r["kept"]) for r in rep),
+                               "conflict_fraction": sum(r["conflict"] for r in rep) / n, "empty_fraction": sum(r["empty"] for r in rep) / n}
+        del da
+    # the task-vector plan once more, after the DARE runs: the yardstick did not drift while they ran
+    tv_ms2, _ = timed(tv.run, args.reps)
+    res["taskvec"]["ms_median_after"] = tv_ms2
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

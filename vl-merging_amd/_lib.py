@@ -55,6 +55,33 @@ class TiesState(ctypes.Structure):
     _fields_ = [("key", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("rank", c_u64)]
 
 
+DARE_LINEAR, DARE_TIES = 0, 1
+DARE_COUNTERS = MERGE_MAX_SRC + 2  # VLM_DARE_COUNTERS: kept per source, conflict, empty
+
+
+class DareJob(ctypes.Structure):
+    """vlm_dare_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("keep_below", c_u64),
+        ("seed", c_u64),
+        ("n_elem", c_u64),
+        ("n_src", ctypes.c_int32),
+        ("mode", ctypes.c_int32),
+        ("lam", c_float),
+        ("rescale", c_float),
+        ("stream", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class DareHeader(ctypes.Structure):
+    """vlm_dare_header_t: the first bytes of a DARE plan's workspace."""
+    _fields_ = [(n, c_u64) for n in ("n_jobs", "n_chunks", "jobs_off", "chunks_off", "counters_off")]
+
+
 class ScatterSrc(ctypes.Structure):
     """vlm_scatter_src_t of include/vlm_hip.h."""
     _fields_ = [("g", c_void_p), ("g_is_f32", ctypes.c_int32), ("ld", ctypes.c_int32), ("first_row", ctypes.c_int32),
@@ -144,6 +171,9 @@ SIGNATURES = {
     "vlm_ties_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_ties_plan_upload": (c_int, [ctypes.POINTER(TiesJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_ties_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_dare_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_dare_plan_upload": (c_int, [ctypes.POINTER(DareJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_dare_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_bf16_grouped": (c_int, [c_int, ctypes.POINTER(GemmGroup), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

@@ -17,6 +17,7 @@
 // element; the apply pass also writes 4 B.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
 #include "vlm_common.h"
 #include "chunk_plan.h"
+#include "ties_elem.h"  // steps 3-5, the counters and the chunk runs: shared with dare.hip
 #include <string.h>
 #include <vector>
 
@@ -28,8 +29,6 @@
 #define TIES_SCAN_BLOCKS 1024
 // The three grid sizes above follow from the kernels' resident-workgroup counts (register and LDS use recorded by the build); none of
 // them has been A/B-measured against other values (docs/experiments.md, "TIES merge").
-
-typedef unsigned long long u64_t;
 
 struct ties_unit_t {  // one (job, source) pair
   uint32_t job;
@@ -102,14 +101,6 @@ __device__ __forceinline__ ties_view_t ties_view(unsigned char* ws) {
   v.hist = reinterpret_cast<u64_t*>(ws + v.hdr->hist_off);
   v.counters = reinterpret_cast<u64_t*>(ws + v.hdr->counters_off);
   return v;
-}
-
-// the contiguous run of chunks this workgroup owns
-__device__ __forceinline__ void ties_my_chunks(uint64_t n_chunks, uint64_t* c0, uint64_t* c1) {
-  const uint64_t per = (n_chunks + gridDim.x - 1) / gridDim.x;
-  *c0 = (uint64_t)blockIdx.x * per;
-  uint64_t e = *c0 + per;
-  *c1 = e < n_chunks ? e : n_chunks;
 }
 
 template <int PASS>
@@ -225,39 +216,17 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_scan_kernel(unsigned ch
   }
 }
 
-struct ties_counts_t {
-  uint32_t c[VLM_TIES_COUNTERS];  // kept[0..3], conflict, empty
-};
-
 template <int NSRC>
 __device__ __forceinline__ float ties_elem(float c, const float* wv, const uint32_t* thr, float lam, ties_counts_t& n) {
   float tt[NSRC];
-  float s = 0.0f;
-  bool has_pos = false, has_neg = false;
 #pragma unroll
   for (int m = 0; m < NSRC; ++m) {
     const float t = __fsub_rn(wv[m], c);                                 // step 1
     const bool kept = (__float_as_uint(t) & 0x7fffffffu) >= thr[m];      // step 2
     tt[m] = kept ? t : 0.0f;
     n.c[m] += kept ? 1u : 0u;
-    s = __fadd_rn(s, tt[m]);                                             // step 3
-    has_pos |= tt[m] > 0.0f;
-    has_neg |= tt[m] < 0.0f;
   }
-  float num = 0.0f;
-  int cnt = 0;
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) {                                       // step 4
-    const bool agree = (s > 0.0f && tt[m] > 0.0f) || (s < 0.0f && tt[m] < 0.0f);
-    if (agree) {
-      num = __fadd_rn(num, tt[m]);
-      ++cnt;
-    }
-  }
-  const float d = cnt > 0 ? __fdiv_rn(num, (float)cnt) : 0.0f;
-  n.c[VLM_MERGE_MAX_SRC] += (has_pos && has_neg) ? 1u : 0u;
-  n.c[VLM_MERGE_MAX_SRC + 1] += cnt == 0 ? 1u : 0u;
-  return __fadd_rn(c, __fmul_rn(lam, d));                                // step 5
+  return ties_elect<NSRC>(c, tt, lam, n);                                // steps 3-5 (ties_elem.h)
 }
 
 template <int NSRC>
@@ -303,26 +272,6 @@ __device__ __forceinline__ void ties_apply_tail(const vlm_ties_job_t& j, const u
 #pragma unroll
   for (int m = 0; m < NSRC; ++m) wv[m] = reinterpret_cast<const float*>(j.src[m])[i];
   reinterpret_cast<float*>(j.dst)[i] = ties_elem<NSRC>(reinterpret_cast<const float*>(j.base)[i], wv, thr, j.lam, n);
-}
-
-// in-workgroup reduction of the six counters, then one 64-bit atomic per counter
-__device__ __forceinline__ void ties_flush_counts(ties_counts_t& n, u64_t* red, u64_t* counters) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < VLM_TIES_COUNTERS; ++k) {
-    uint32_t v = n.c[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[wave * VLM_TIES_COUNTERS + k] = v;
-    n.c[k] = 0;
-  }
-  __syncthreads();
-  if (threadIdx.x < VLM_TIES_COUNTERS) {
-    u64_t t = 0;
-    for (int wv = 0; wv < TIES_THREADS / 64; ++wv) t += red[wv * VLM_TIES_COUNTERS + threadIdx.x];
-    if (t) __hip_atomic_fetch_add(&counters[threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
 }
 
 __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_apply_kernel(unsigned char* __restrict__ ws) {

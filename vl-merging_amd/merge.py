@@ -1,4 +1,4 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES.
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
 (reference src/vilt/modules/vilt_module.py:533-638, :640-746, :366-531): same `state_dict -> state_dict`
@@ -8,7 +8,8 @@ launch of the HIP merge kernel (csrc/merge.hip) and is bit-exact with the refere
 
 ties_merge (TIES-merging, Yadav et al. 2023) has NO reference site: the reference has no TIES.  It takes what sum_task_vectors
 takes and follows its dictionary logic; its arithmetic (include/vlm_hip.h, csrc/ties.hip) is pinned to a numpy restatement of
-the rule (tests/ties_restatement.py), not to the reference.
+the rule (tests/ties_restatement.py), not to the reference.  dare_merge (DARE, Yu et al. 2023) likewise: no reference site, the
+rule in include/vlm_hip.h, csrc/dare.hip held to tests/dare_restatement.py.
 """
 import ctypes
 import math
@@ -78,6 +79,8 @@ class _Plan:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise L.VlmError("%s (got device %s)" % (self.GPU_ONLY, device))
+        if self.device.index is None:  # "cuda" names the current device; _dev compares devices, and cuda:0 != cuda would stage a
+            self.device = torch.device("cuda", torch.cuda.current_device())  # copy of every tensor that is already there
         self.jobs = []
         self.keep = []  # keeps staged tensors alive
         self.total = 0
@@ -321,6 +324,142 @@ def ties_merge(state_dict, config, central_weight=None, density=0.2, lam=None, d
             out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
         else:
             out[dst] = plan.add(_tensors(srcs), central[dst], density=density, lam=lam, name=dst)
+    for p in (plan, single):
+        if p.jobs:
+            p.run()
+            if plan_out is not None:
+                plan_out.append(p)
+    if report_out is not None:
+        report_out.extend(plan.report() if plan.jobs else [])
+    return out
+
+
+def dare_keep_below(drop):
+    """keep_below of the DARE rule: a draw u (32 bits) keeps its entry iff u < floor((1 - drop) * 2**32), in python doubles."""
+    if not (0.0 <= drop < 1.0):  # also rejects NaN
+        raise ValueError("DARE drop probability must lie in [0, 1), got %r" % (drop,))
+    kb = math.floor((1.0 - drop) * 2 ** 32)
+    if kb < 1:
+        raise ValueError("DARE drop probability %r keeps nothing" % (drop,))
+    return kb
+
+
+def dare_rescale(drop, rescale=True):
+    """float32(1 / (1 - drop)): computed in double, rounded once; 1.0 without rescaling."""
+    if not rescale:
+        return 1.0
+    return struct.unpack("<f", struct.pack("<f", 1.0 / (1.0 - drop)))[0]
+
+
+_DARE_MODES = {"linear": L.DARE_LINEAR, "ties": L.DARE_TIES, L.DARE_LINEAR: L.DARE_LINEAR, L.DARE_TIES: L.DARE_TIES}
+
+
+def _dare_mode(mode):
+    if isinstance(mode, bool) or mode not in _DARE_MODES:
+        raise L.VlmError("DARE mode must be 'linear' or 'ties', got %r" % (mode,))
+    return _DARE_MODES[mode]
+
+
+class DarePlan(_Plan):
+    """The job table of csrc/dare.hip; run() enqueues the counter reset and the one streaming launch of a DARE merge without a
+    host synchronisation.  The mask is a function of (seed, stream, source, element) and is never stored."""
+
+    GPU_ONLY, JOB = "the DARE kernel runs on the GPU only", L.DareJob
+    BYTES, UPLOAD, RUN = "vlm_dare_plan_bytes", "vlm_dare_plan_upload", "vlm_dare_run"
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.names: List[Optional[str]] = []
+
+    def add(self, srcs, base, drop, lam, seed, stream, mode, rescale=True, out=None, name=None):
+        """One output tensor.  `out` may be `base` or one of `srcs` (the pass is elementwise) or any tensor that meets none of them."""
+        mode = _dare_mode(mode)
+        keep_below = dare_keep_below(drop)
+        if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(stream) < 2 ** 32:
+            raise L.VlmError("DARE seed must fit 64 bits and stream 32 bits, got %r, %r" % (seed, stream))
+        srcs = [self._dev(s) for s in srcs]
+        if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
+            raise L.VlmError("a DARE job takes 1 .. %d sources, got %d" % (L.MERGE_MAX_SRC, len(srcs)))
+        n = srcs[0].numel()
+        b = self._dev(base)
+        self._same_shape(srcs + [b])
+        if out is None:
+            out = torch.empty_like(srcs[0])
+        else:
+            self._same_shape([srcs[0], out])
+            if out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or (out.data_ptr() & 15):
+                raise L.VlmError("a DARE output must be a contiguous, 16-byte aligned float32 tensor on %s" % (self.device,))
+        self.keep.append(out)
+        job = L.DareJob()
+        job.dst = out.data_ptr()
+        job.base = b.data_ptr()
+        for k, s in enumerate(srcs):
+            job.src[k] = s.data_ptr()
+        job.keep_below = keep_below
+        job.seed = int(seed)
+        job.n_elem = n
+        job.n_src = len(srcs)
+        job.mode = mode
+        job.lam = float(lam)
+        job.rescale = dare_rescale(drop, rescale)
+        job.stream = int(stream)
+        self.jobs.append(job)
+        self.names.append(name)
+        self.total += n
+        self.bytes_read += 4 * n * (len(srcs) + 1)  # one pass: every source and the central tensor once; the mask costs nothing
+        self.bytes_written += 4 * n
+        return out
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): how many entries each source kept, the elements whose kept entries
+        disagree in sign, the elements nothing contributes to."""
+        if self.ws is None:
+            raise L.VlmError("DarePlan.report() needs a plan that has run")
+        hdr = L.DareHeader.from_buffer_copy(self.ws[: ctypes.sizeof(L.DareHeader)].cpu().numpy().tobytes())
+        counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * L.DARE_COUNTERS * hdr.n_jobs].cpu().numpy()
+        counters = counters.view("<u8").reshape(-1, L.DARE_COUNTERS)
+        return [{"dst": self.names[i], "n": int(job.n_elem), "keep_below": int(job.keep_below),
+                 "kept": [int(counters[i, m]) for m in range(job.n_src)],
+                 "conflict": int(counters[i, L.MERGE_MAX_SRC]), "empty": int(counters[i, L.MERGE_MAX_SRC + 1])}
+                for i, job in enumerate(self.jobs)]
+
+
+DARE_STREAMS_PER_LAYER = 13  # the tensor names of a layer (_tensor_names)
+
+
+def dare_stream(dst):
+    """The Philox stream of an output tensor: 13 * layer + its position among the layer's names -- a function of the name alone, so
+    a tensor's mask does not depend on which other keys a checkpoint holds."""
+    return _DARE_STREAM[dst]
+
+
+_DARE_STREAM = {dst: DARE_STREAMS_PER_LAYER * i + slot for i in range(NUM_MERGE_LAYERS)
+                for slot, (_, dst) in enumerate(_tensor_names(i))}
+
+
+def dare_merge(state_dict, config, central_weight=None, drop=0.9, lam=None, seed=0, mode="linear", rescale=True, device="cuda",
+               plan_out: Optional[list] = None, report_out: Optional[list] = None):
+    """DARE merge of the modality experts' task vectors `W_m - central` (no reference site; the rule: include/vlm_hip.h): every
+    entry is dropped with probability `drop`, the survivors are scaled by 1 / (1 - drop), then summed (mode "linear") or sign-elected
+    and averaged as in TIES (mode "ties").  Same inputs, keys, pass-through and KeyError behaviour as sum_task_vectors and ties_merge;
+    `lam=None` takes config["sum_lambda"].  A layer with ONE source is not dropped: it is the task-vector job with ratio 1 that
+    sum_task_vectors issues for it.  `plan_out` receives the DarePlan FIRST whenever a layer has several sources, then the MergePlan
+    of the single-source layers if there are any; `report_out` receives DarePlan.report() (reading it back synchronises)."""
+    dare_keep_below(drop)  # ValueError before any device work
+    mode = _dare_mode(mode)
+    if lam is None:
+        lam = config["sum_lambda"]
+    plan = DarePlan(device)
+    single = MergePlan(device)
+    out = _passthrough(state_dict)
+    central = _central(central_weight, config)
+    for dst, mods, srcs, through in _walk(state_dict, config, central):
+        if srcs is None:
+            out[dst] = through
+        elif len(mods) == 1:
+            out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
+        else:
+            out[dst] = plan.add(_tensors(srcs), central[dst], drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst)
     for p in (plan, single):
         if p.jobs:
             p.run()

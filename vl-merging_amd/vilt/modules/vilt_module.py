@@ -279,6 +279,12 @@ class ViLTransformerSS(nn.Module):
         not wired to a config key and not called from __init__."""
         return merge_ops.ties_merge(state_dict, self.hparams.config, density=density, lam=lam, device=self._merge_device())
 
+    def dare_merge(self, state_dict, drop=0.9, lam=None, seed=0, mode="linear", rescale=True):
+        """DARE merge of the experts' task vectors (no reference site; merge.dare_merge).  Same contract as sum_task_vectors;
+        not wired to a config key and not called from __init__."""
+        return merge_ops.dare_merge(state_dict, self.hparams.config, drop=drop, lam=lam, seed=seed, mode=mode, rescale=rescale,
+                                    device=self._merge_device())
+
     def regmean(self, state_dict):
         return regmean_ops.regmean(state_dict, self.hparams.config, device=self._merge_device())
 

@@ -1,13 +1,24 @@
 // Host-only check of csrc/chunk_plan.h (no HIP, no GPU): the chunk table of the merge family for the ragged sizes of
-// tests/test_merge_gpu.py and for the 156 tensor lengths of a base-size all_moe -> ufo merge.  Built with
+// tests/test_merge_gpu.py and for the 156 tensor lengths of a base-size all_moe -> ufo merge, the host image built around it,
+// and the per-job checks under each overlap policy.  Built with
 // -fsanitize=address,undefined and run as a child process by tests/test_chunk_plan_cpu.py; exit status 0 = every check held.
 #include "chunk_plan.h"
 
 #include <stdio.h>
+#include <string.h>
 #include <vector>
 
-struct job_t {
+struct job_t {  // the fields the family's job types share
   uint64_t n_elem;
+  void* dst = nullptr;
+  const void* base = nullptr;
+  const void* src[VLM_MERGE_MAX_SRC] = {};
+  int n_src = 0;
+  job_t(uint64_t n) : n_elem(n) {}
+};
+
+struct header_t {  // a header as the methods' are: the offsets chunk_image reads, then a part of the method's own
+  uint64_t n_jobs, n_chunks, jobs_off, chunks_off, own_off;
 };
 
 static int failures = 0;
@@ -55,6 +66,85 @@ static void check_table(const char* what, const std::vector<job_t>& jobs) {
     CHECK(tail == n % 4, "%s: job %zu (n = %llu): %u tail floats handled", what, i, (unsigned long long)n, tail);
   }
   CHECK(c == want, "%s: %llu records belong to no job", what, (unsigned long long)(want - c));
+
+  // the host image around that table: 256-byte aligned parts in the order taken, nothing written outside them
+  header_t h;
+  chunk_layout_t at;
+  CHECK(at.take(sizeof(h)) == 0, "%s: the header is not at 0", what);
+  h.n_jobs = jobs.size();
+  h.n_chunks = want;
+  h.jobs_off = at.take(jobs.size() * sizeof(job_t));
+  h.chunks_off = at.take(want * sizeof(chunk_t));
+  h.own_off = at.take(100);  // what a method appends (TIES: unit0, units): left zero by the builder
+  CHECK(h.jobs_off == 256 && h.chunks_off == h.jobs_off + chunk_align_up(jobs.size() * sizeof(job_t), 256) &&
+            h.own_off == h.chunks_off + chunk_align_up(want * sizeof(chunk_t), 256) && at.off == h.own_off + 256,
+        "%s: layout offsets", what);
+  const std::vector<unsigned char> img = chunk_image(h, jobs.data(), (int)jobs.size(), at.off);
+  CHECK(img.size() == at.off, "%s: image of %zu bytes, expected %zu", what, img.size(), at.off);
+  CHECK(!memcmp(img.data(), &h, sizeof(h)), "%s: header bytes", what);
+  CHECK(!memcmp(img.data() + h.jobs_off, jobs.data(), jobs.size() * sizeof(job_t)), "%s: job bytes", what);
+  CHECK(!memcmp(img.data() + h.chunks_off, ck.data(), want * sizeof(chunk_t)), "%s: chunk table bytes", what);
+  size_t stray = 0;
+  for (size_t i = sizeof(h); i < h.jobs_off; ++i) stray += img[i] != 0;
+  for (size_t i = h.jobs_off + jobs.size() * sizeof(job_t); i < h.chunks_off; ++i) stray += img[i] != 0;
+  for (size_t i = h.chunks_off + want * sizeof(chunk_t); i < img.size(); ++i) stray += img[i] != 0;
+  CHECK(stray == 0, "%s: %zu non-zero bytes between the parts", what, stray);
+}
+
+// chunk_job_check under the three overlap policies (plain merge: unchecked, TIES: no meeting, DARE: exact alias allowed)
+static void check_job_checks() {
+  alignas(16) static float buf[64];  // dst at buf, inputs of n = 8 floats relative to it
+  const chunk_overlap_t policies[] = {CHUNK_OVERLAP_UNCHECKED, CHUNK_OVERLAP_NONE, CHUNK_OVERLAP_EXACT};
+  for (chunk_overlap_t pol : policies) {
+    const bool checked = pol != CHUNK_OVERLAP_UNCHECKED;
+    auto job = [&](const void* base, const void* s0, const void* s1) {
+      job_t j(8);
+      j.dst = buf;
+      j.base = base;
+      j.src[0] = s0;
+      j.src[1] = s1;
+      j.n_src = 2;
+      return j;
+    };
+    auto rc = [&](const job_t& j, bool need_base = true) { return chunk_job_check(j, pol, need_base); };
+    CHECK(rc(job(buf + 8, buf + 16, buf + 24)) == VLM_OK, "policy %d: disjoint ranges", (int)pol);
+    // equal ranges: only where exact alias is allowed (or nothing is compared)
+    CHECK(rc(job(buf, buf + 16, buf + 24)) == (pol == CHUNK_OVERLAP_NONE ? VLM_ERR_ARG : VLM_OK), "policy %d: dst == base", (int)pol);
+    CHECK(rc(job(buf + 8, buf + 16, buf)) == (pol == CHUNK_OVERLAP_NONE ? VLM_ERR_ARG : VLM_OK), "policy %d: dst == src[1]", (int)pol);
+    // offset by 16 B either way: refused under both policies that compare
+    CHECK(rc(job(buf + 4, buf + 16, buf + 24)) == (checked ? VLM_ERR_ARG : VLM_OK), "policy %d: base 16 B above dst", (int)pol);
+    CHECK(rc(job(buf + 8, buf + 4, buf + 24)) == (checked ? VLM_ERR_ARG : VLM_OK), "policy %d: src[0] 16 B above dst", (int)pol);
+    job_t below = job(buf + 16, buf + 24, buf);
+    below.dst = buf + 4;
+    CHECK(rc(below) == (checked ? VLM_ERR_ARG : VLM_OK), "policy %d: src[1] 16 B below dst", (int)pol);
+    job_t touch = job(buf + 8, buf + 16, buf + 24);  // ranges that end where the next begins do not meet
+    CHECK(rc(touch) == VLM_OK, "policy %d: adjacent ranges", (int)pol);
+    // misaligned and null pointers
+    CHECK(rc(job(buf + 9, buf + 16, buf + 24)) == VLM_ERR_ARG, "policy %d: misaligned base", (int)pol);
+    CHECK(rc(job(buf + 8, buf + 17, buf + 24)) == VLM_ERR_ARG, "policy %d: misaligned src[0]", (int)pol);
+    CHECK(rc(job(buf + 8, buf + 16, nullptr)) == VLM_ERR_ARG, "policy %d: null src[1]", (int)pol);
+    CHECK(rc(job(nullptr, buf + 16, buf + 24)) == VLM_ERR_ARG, "policy %d: null base where one is needed", (int)pol);
+    CHECK(rc(job(nullptr, buf + 16, buf + 24), false) == VLM_OK, "policy %d: null base where none is needed", (int)pol);
+    job_t bad = job(buf + 8, buf + 16, buf + 24);
+    bad.dst = nullptr;
+    CHECK(rc(bad) == VLM_ERR_ARG, "policy %d: null dst", (int)pol);
+    bad = job(buf + 8, buf + 16, buf + 24);
+    bad.dst = buf + 1;
+    CHECK(rc(bad) == VLM_ERR_ARG, "policy %d: misaligned dst", (int)pol);
+    for (int n_src : {0, VLM_MERGE_MAX_SRC + 1}) {
+      bad = job(buf + 8, buf + 16, buf + 24);
+      bad.n_src = n_src;
+      CHECK(rc(bad) == VLM_ERR_ARG, "policy %d: n_src = %d", (int)pol, n_src);
+    }
+    // the length limit; with a misaligned pointer as well, the policies that form byte ranges answer for the length first
+    job_t far = job(buf + 32, buf + 40, buf + 48);  // far apart: no byte range below is formed from these lengths
+    far.n_elem = (1ull << 34) - 1;
+    CHECK(rc(far) == (checked ? VLM_ERR_ARG : VLM_OK), "policy %d: the longest length (its ranges meet)", (int)pol);
+    far.n_elem = 1ull << 34;
+    CHECK(rc(far) == VLM_ERR_UNSUPPORTED, "policy %d: one past the longest length", (int)pol);
+    far.src[0] = buf + 41;
+    CHECK(rc(far) == (checked ? VLM_ERR_UNSUPPORTED : VLM_ERR_ARG), "policy %d: too long and misaligned", (int)pol);
+  }
 }
 
 int main() {
@@ -69,6 +159,8 @@ int main() {
     for (uint64_t n : {3 * D * D, D * D, D, D, D, F * D, F, D * F, D, D, D, D, D}) base.push_back({n});
   CHECK(base.size() == 156, "base table has %zu jobs", base.size());
   check_table("base", base);
+
+  check_job_checks();
 
   // the common checks
   alignas(16) static char buf[32];

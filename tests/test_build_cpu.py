@@ -153,3 +153,25 @@ def test_f64_block_entry_points_and_switch_are_retired(resources):
 def test_one_fold_kernel(resources):
     assert [k for k in resources if "colreduce_batch_kernel" in k]
     assert not [k for k in resources if "colreduce_kernel" in k]
+
+
+def test_merge_family_keeps_the_occupancy_its_grids_count_on(resources):
+    """The chunk walkers of merge.hip, ties.hip and dare.hip are one template (csrc/chunk_walk.h) around each method's rule; the
+    grids are sized from resident workgroups (one wave per SIMD each).  TIES_HIST_BLOCKS_PER_CU = 4 counts on exactly four
+    histogram workgroups per CU (registers allow four, and four times 32 KiB of LDS fit); TIES_APPLY_BLOCKS_PER_CU =
+    DARE_APPLY_BLOCKS_PER_CU = 12 is four rounds of three; vlm_merge_run's 96 per CU strides the table with at least five
+    resident.  None of them may spill: the kernels are HBM-bound streams."""
+    def only(name):
+        r = [v for k, v in resources.items() if name in k]
+        assert len(r) == 1, (name, sorted(k for k in resources if name in k))
+        return r[0]
+
+    hist = {k: v for k, v in resources.items() if "vlm_ties_hist_kernel" in k}
+    assert len(hist) == 3, sorted(hist)  # PASS 0 / 1 / 2
+    for name, r in hist.items():
+        assert r["Occupancy"] == 4 and r["LDS Size"] == 32768, (name, r)
+    apply_ties, apply_dare, plain = only("vlm_ties_apply_kernel"), only("vlm_dare_apply_kernel"), only("vlm_merge_kernel")
+    assert apply_ties["Occupancy"] >= 3 and apply_dare["Occupancy"] >= 3, (apply_ties, apply_dare)
+    assert plain["Occupancy"] >= 5, plain
+    for r in list(hist.values()) + [apply_ties, apply_dare, plain]:
+        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, r

@@ -1,4 +1,4 @@
-"""The host part of csrc/chunk_plan.h, the chunk plan merge.hip and ties.hip share, checked without HIP and without a GPU:
+"""The host part of csrc/chunk_plan.h, the chunk plan merge.hip, ties.hip and dare.hip share, checked without HIP and without a GPU:
 tests/helpers/chunk_plan_check.cpp is compiled with the host compiler under AddressSanitizer + UBSan and run as a child process."""
 import os
 import shutil
@@ -9,7 +9,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_chunk_table_count_cover_and_tail_owner(tmp_path):
     """For the ragged sizes {1, 3, 5, 4095, 4096, 4097, 8195, 12289} and for the 156 tensor lengths of a base-size merge: the
-    chunk count, every (job, start4), the chunks of a job cover [0, n4) exactly once, exactly one chunk per job owns the tail."""
+    chunk count, every (job, start4), the chunks of a job cover [0, n4) exactly once, exactly one chunk per job owns the tail,
+    and the offsets and bytes of the host image built around the table.  The per-job checks under each overlap policy: equal,
+    16-byte offset, adjacent and disjoint ranges, misaligned and null pointers, the length limit and its precedence."""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
     assert cxx, "no host C++ compiler"
     exe = os.path.join(str(tmp_path), "chunk_plan_check")

@@ -12,11 +12,12 @@ import pytest
 import torch
 
 from oracle import merge_oracle as mo
-from oracle import synth
-from oracle.detweights import det_array
 from test_oracle_merge import merge_cfg, tiny_state
 from test_ties_gpu import CASES, is_block, planted, to_dev
 from dare_restatement import LINEAR, TIES, dare, keep_below
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from merge_inputs import base_size_state, one_buffer, tiny_jobs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -90,6 +91,28 @@ def test_dare_a_dozen_jobs_in_one_plan(merge):
     outs, rows, _ = run_plan(merge, jobs)
     check_jobs(jobs, outs, rows)
     assert sum(r["conflict"] for r in rows) > 0 and sum(r["empty"] for r in rows) > 0
+
+
+def test_dare_runs_of_chunks_cross_job_boundaries(merge):
+    """2 x 12 x CUs + 7 one-chunk jobs (lengths cycled through 5, 1, 4097, 3, 2, 4099; 1 .. 4 sources; both modes; drop, lambda,
+    seed, stream and rescale cycled as above), every input a 16-byte aligned view into one device buffer: each of the 12
+    workgroups per CU owns three chunks, every one of another job -- so a run leaves a job, flushes its counters and loads the
+    next job's scalars at every step, which plans below the grid size (one chunk per workgroup) never do.  Outputs and every
+    counter against the restatement."""
+    jobs = [job(c, srcs, [0.9, 0.5, 0.0, 0.25, 0.99][i % 5], lam=[1, 0.75, 0.3][i % 3], seed=[SEED, 0, 2 ** 64 - 1, 2 ** 32 + 7][i % 4],
+                stream=[0, 5, 155, 2 ** 32 - 1][(i // 2) % 4], mode=["linear", "ties"][i % 2], rescale=i % 7 != 3)
+            for i, (c, srcs) in enumerate(tiny_jobs(torch.cuda.get_device_properties(0).multi_processor_count, planted))]
+    views = iter(one_buffer([a for j in jobs for a in [j["c"]] + j["srcs"]]))
+    plan = merge.DarePlan("cuda")
+    outs = []
+    for i, j in enumerate(jobs):
+        base = next(views)
+        outs.append(plan.add([next(views) for _ in j["srcs"]], base, j["drop"], j["lam"], j["seed"], j["stream"], j["mode"],
+                             rescale=j["rescale"], name=str(i)))
+        assert plan.jobs[-1].base == base.data_ptr()  # the view itself, not a staged copy
+    plan.run()
+    torch.cuda.synchronize()
+    check_jobs(jobs, outs, plan.report())
 
 
 def test_dare_coordinates_not_position_decide_the_mask(merge):
@@ -275,10 +298,7 @@ def test_dare_base_size(merge):
     """Base size (the inputs of test_ties_base_size), drop 0.9: layers 0 (two sources) and 11 (three) against the restatement bit
     for bit, every other output finite; the plan's byte counts; and run() returns while its launches are still queued."""
     L = importlib.import_module("vl_merging_amd._lib")
-    shapes = synth.block_shapes(768, 3072, "all_moe")
-    sd_np = {k: det_array(k, s) for k, (s, dt) in shapes.items()}
-    cshapes = synth.block_shapes(768, 3072, "ufo")
-    central_np = {k: det_array(k, s, 7) for k, (s, dt) in cshapes.items()}
+    sd_np, central_np = base_size_state()
     sd, central = to_dev(sd_np), to_dev(central_np)
     cfg = merge_cfg(sum_lambda=0.75)
     plans, rows = [], []

@@ -3,15 +3,17 @@ import hashlib
 import importlib
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import merge_oracle as mo
-from oracle import synth
-from oracle.detweights import det_array
 from test_oracle_merge import CASES, merge_cfg, tiny_state
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from merge_inputs import base_size_state  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -112,8 +114,8 @@ def test_merge_mixed_jobs_in_one_plan(merge):
 def test_merge_base_size_digests(merge, golden_dir):
     """BASELINE config 4: base-size all_moe -> ufo (1 077 239 808 algorithmic bytes), sha256 == reference."""
     dig = json.load(open(os.path.join(golden_dir, "merge_base_digests.json")))
-    shapes = synth.block_shapes(768, 3072, "all_moe")
-    sd = {k: torch.from_numpy(det_array(k, s)).cuda() for k, (s, dt) in shapes.items()}
+    sd_np, central_np = base_size_state()
+    sd, central = to_dev(sd_np), to_dev(central_np)
     for name, ratio in (("interp_r0.5", 0.5), ("interp_r0.3", 0.3)):
         plans = []
         res = merge.merge_weights(sd, merge_cfg(merge_ratio=ratio), plan_out=plans)
@@ -121,8 +123,6 @@ def test_merge_base_size_digests(merge, golden_dir):
         assert plans[0].bytes_read + plans[0].bytes_written == 1077239808
         bad = [k for k, d in dig[name].items() if hashlib.sha256(res[k].cpu().numpy().tobytes()).hexdigest() != d]
         assert not bad, bad[:5]
-    cshapes = synth.block_shapes(768, 3072, "ufo")
-    central = {k: torch.from_numpy(det_array(k, s, 7)).cuda() for k, (s, dt) in cshapes.items()}
     res = merge.sum_task_vectors(sd, merge_cfg(sum_lambda=0.75), central_weight=central)
     torch.cuda.synchronize()
     bad = [k for k, d in dig["taskvec_l0.75"].items()

@@ -12,10 +12,11 @@ import pytest
 import torch
 
 from oracle import merge_oracle as mo
-from oracle import synth
-from oracle.detweights import det_array
 from test_oracle_merge import merge_cfg, tiny_state
 from ties_restatement import keep_count, ties
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from merge_inputs import base_size_state, one_buffer, tiny_jobs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -186,6 +187,26 @@ def test_ties_several_jobs_in_one_plan_and_ties_at_the_threshold(merge):
     assert rows[-1]["conflict"] > 0 and rows[-1]["empty"] > 0
 
 
+def test_ties_runs_of_chunks_cross_job_boundaries(merge):
+    """2 x 12 x CUs + 7 one-chunk jobs (lengths cycled through 5, 1, 4097, 3, 2, 4099; 1 .. 4 sources; density and lambda
+    cycled as above), every input a 16-byte aligned view into one device buffer: each workgroup of a histogram pass (4 per CU)
+    owns about seven chunks and each of the apply pass (12 per CU) three, every one of another job -- so a run leaves a job,
+    flushes and loads the next job's prefixes or thresholds at every step, which plans below the grid size (one chunk per
+    workgroup) never do.  Outputs, thresholds and every counter against the restatement."""
+    jobs = [(c, srcs, [0.2, 0.05, 1.0][i % 3], [1, 0.75][i % 2])
+            for i, (c, srcs) in enumerate(tiny_jobs(torch.cuda.get_device_properties(0).multi_processor_count, planted))]
+    views = iter(one_buffer([a for c, srcs, _, _ in jobs for a in [c] + srcs]))
+    plan = merge.TiesPlan("cuda")
+    outs = []
+    for i, (c, srcs, density, lam) in enumerate(jobs):
+        base = next(views)
+        outs.append(plan.add([next(views) for _ in srcs], base, density=density, lam=lam, name=str(i)))
+        assert plan.jobs[-1].base == base.data_ptr()  # the view itself, not a staged copy
+    plan.run()
+    torch.cuda.synchronize()
+    check_jobs(jobs, outs, plan.report())
+
+
 def test_ties_constant_and_all_zero_task_vectors(merge):
     n = 5000
     c = np.linspace(-1, 1, n).astype(F)
@@ -241,10 +262,7 @@ def test_ties_base_size(merge):
     """Base size (the inputs of test_merge_base_size_digests), density 0.2: layers 0 (two sources) and 11 (three) against the
     restatement bit for bit, every other output finite; and run() returns while its launches are still queued."""
     L = importlib.import_module("vl_merging_amd._lib")
-    shapes = synth.block_shapes(768, 3072, "all_moe")
-    sd_np = {k: det_array(k, s) for k, (s, dt) in shapes.items()}
-    cshapes = synth.block_shapes(768, 3072, "ufo")
-    central_np = {k: det_array(k, s, 7) for k, (s, dt) in cshapes.items()}
+    sd_np, central_np = base_size_state()
     sd, central = to_dev(sd_np), to_dev(central_np)
     cfg = merge_cfg(sum_lambda=0.75)
     plans, rows = [], []

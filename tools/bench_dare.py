@@ -7,7 +7,6 @@ import argparse
 import importlib
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -15,21 +14,6 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
-
-
-def timed(fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms), min(ms)
 
 
 def main(argv):
@@ -42,16 +26,13 @@ def main(argv):
     args = ap.parse_args(argv)
     ge.import_package()
     merge = importlib.import_module("vl_merging_amd.merge")
-    from oracle import synth
-    from oracle.detweights import det_array
+    bm = importlib.import_module("vl_merging_amd.bench_merge")
     torch.cuda.set_device(0)
-    sd = {k: torch.from_numpy(det_array(k, s)).cuda() for k, (s, dt) in synth.block_shapes(768, 3072, "all_moe").items()}
-    central = {k: torch.from_numpy(det_array(k, s, 7)).cuda() for k, (s, dt) in synth.block_shapes(768, 3072, "ufo").items()}
-    cfg = dict(vlffn_start_layer_index=10, only_activate_used_experts=False, merge_ratio=0.5, sum_lambda=0.75, loss_names={})
+    sd, central, cfg = bm.base_size_task_vector_inputs()
     tv = []
     merge.sum_task_vectors(sd, cfg, central_weight=central, plan_out=tv)
     tv = tv[0]
-    tv_ms, tv_min = timed(tv.run, args.reps)
+    tv_ms, tv_min = bm.timed(tv.run, args.reps)
     tv_bytes = tv.bytes_read + tv.bytes_written
     res = {"workload": "base all_moe -> ufo, 156 tensors", "device": torch.cuda.get_device_name(0), "reps": args.reps,
            "taskvec": {"ms_median": tv_ms, "ms_min": tv_min, "bytes": tv_bytes, "GBps": tv_bytes / tv_ms / 1e6}}
@@ -59,17 +40,14 @@ def main(argv):
         da = []
         merge.dare_merge(sd, cfg, central_weight=central, drop=args.drop, seed=args.seed, mode=mode, plan_out=da)
         da = da[0]
-        ms, ms_min = timed(da.run, args.reps)
+        ms, ms_min = bm.timed(da.run, args.reps)
         nbytes = da.bytes_read + da.bytes_written
-        rep = da.report()
-        n = sum(r["n"] for r in rep)
         res["dare_" + mode] = {"drop": args.drop, "seed": args.seed, "launches": 2, "ms_median": ms, "ms_min": ms_min, "bytes": nbytes,
                                "GBps": nbytes / ms / 1e6, "ms_vs_taskvec": ms / tv_ms,
-                               "kept_fraction": sum(sum(r["kept"]) for r in rep) / sum(r["n"] * len(r["kept"]) for r in rep),
-                               "conflict_fraction": sum(r["conflict"] for r in rep) / n, "empty_fraction": sum(r["empty"] for r in rep) / n}
+                               **bm.report_fractions(da.report())}
         del da
     # the task-vector plan once more, after the DARE runs: the yardstick did not drift while they ran
-    tv_ms2, _ = timed(tv.run, args.reps)
+    tv_ms2, _ = bm.timed(tv.run, args.reps)
     res["taskvec"]["ms_median_after"] = tv_ms2
     line = json.dumps(res)
     print(line)

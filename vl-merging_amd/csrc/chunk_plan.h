@@ -1,10 +1,16 @@
-// The chunk plan of the merge family (merge.hip, ties.hip): every job (one output tensor) is cut into 16-KiB chunks listed in a
-// device-resident table, so that ONE grid covers all tensors of a plan.  A chunk is what one 256-thread workgroup moves as
-// 4 float4 per thread; a job's ragged end (n_elem % 4 floats) rides with exactly one of its chunks.
-// Everything but the upload compiles without HIP (tests/helpers/chunk_plan_check.cpp does so).
+// The chunk plan of the merge family (merge.hip, ties.hip, dare.hip): every job (one output tensor) is cut into 16-KiB chunks
+// listed in a device-resident table, so that ONE grid covers all tensors of a plan.  A chunk is what one 256-thread workgroup
+// moves as 4 float4 per thread; a job's ragged end (n_elem % 4 floats) rides with exactly one of its chunks.
+// This is the family's host side, stated once: the chunk table, the checks every job passes (chunk_job_check), the host image
+// "header, jobs, chunk table" (chunk_layout_t, chunk_image), its upload and the grid rule.  The device side -- the chunk walker,
+// a workgroup's run loop, the source-count dispatch -- is chunk_walk.h.
+// Everything but the upload and the grid compiles without HIP (tests/helpers/chunk_plan_check.cpp does so).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
+#include <vector>
+#include "../../include/vlm_hip.h"
 
 #define CHUNK_FLOATS 4096u  // floats per chunk: 256 threads x 4 float4
 #define CHUNK_THREADS 256
@@ -33,6 +39,38 @@ static inline bool chunk_ptr_ok(const void* p) { return p && !((uintptr_t)p & 15
 static inline bool chunk_len_ok(uint64_t n_elem) { return (n_elem >> 2) < (1ull << 32); }
 static inline bool chunk_count_ok(uint64_t n_chunks) { return n_chunks < (1ull << 32); }
 
+// dst against an input of the same job (overlap ACROSS jobs is the caller's to avoid)
+enum chunk_overlap_t {
+  CHUNK_OVERLAP_UNCHECKED,  // plain merge: the caller's to avoid
+  CHUNK_OVERLAP_NONE,       // TIES: dst may not meet an input (the selection passes re-read the inputs)
+  CHUNK_OVERLAP_EXACT       // DARE: dst may be an input exactly (the pass is elementwise), any other meeting is refused
+};
+
+// do the byte ranges [a, a + 4 n) and [b, b + 4 n) meet?
+static inline bool chunk_ranges_meet(const void* a, const void* b, uint64_t n_elem) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  const uint64_t bytes = n_elem * 4;
+  return x < y ? (y - x) < bytes : (x - y) < bytes;
+}
+
+static inline bool chunk_input_ok(chunk_overlap_t overlap, const void* dst, const void* in, uint64_t n_elem) {
+  if (!chunk_ptr_ok(in)) return false;
+  if (overlap == CHUNK_OVERLAP_UNCHECKED || (overlap == CHUNK_OVERLAP_EXACT && dst == in)) return true;
+  return !chunk_ranges_meet(dst, in, n_elem);
+}
+
+// The checks on a job's fields dst, base, src, n_src and n_elem, in the family's order of precedence.  `need_base`: a NULL base
+// is VLM_ERR_ARG (otherwise it is skipped).  Where byte ranges are compared, the length is checked before they are formed.
+template <class Job>
+static inline int chunk_job_check(const Job& j, chunk_overlap_t overlap, bool need_base) {
+  if (j.n_src < 1 || j.n_src > VLM_MERGE_MAX_SRC || !j.dst || (need_base && !j.base)) return VLM_ERR_ARG;
+  if (overlap != CHUNK_OVERLAP_UNCHECKED && !chunk_len_ok(j.n_elem)) return VLM_ERR_UNSUPPORTED;
+  if (!chunk_ptr_ok(j.dst) || (j.base && !chunk_input_ok(overlap, j.dst, j.base, j.n_elem))) return VLM_ERR_ARG;
+  for (int m = 0; m < j.n_src; ++m)
+    if (!chunk_input_ok(overlap, j.dst, j.src[m], j.n_elem)) return VLM_ERR_ARG;
+  return chunk_len_ok(j.n_elem) ? VLM_OK : VLM_ERR_UNSUPPORTED;
+}
+
 // `ck` receives sum_i chunks_of(jobs[i].n_elem) records.  Plain job order: a workgroup's stream of chunks stays contiguous.
 template <class Job>
 static inline uint64_t chunk_table_fill(chunk_t* ck, const Job* jobs, int n_jobs) {
@@ -46,6 +84,27 @@ static inline uint64_t chunk_table_fill(chunk_t* ck, const Job* jobs, int n_jobs
     }
   }
   return c;
+}
+
+// A workspace is laid out as 256-byte aligned parts, the header first: take() gives the next part's offset.
+struct chunk_layout_t {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t at = off;
+    off += chunk_align_up(bytes, 256);
+    return at;
+  }
+};
+
+// The host image of a plan: `hdr` at 0, the jobs at hdr.jobs_off, their chunk table at hdr.chunks_off, zeros up to img_bytes
+// (where a method appends tables of its own).  What lies behind img_bytes in the workspace is device-made.
+template <class Hdr, class Job>
+static inline std::vector<unsigned char> chunk_image(const Hdr& hdr, const Job* jobs, int n_jobs, size_t img_bytes) {
+  std::vector<unsigned char> img(img_bytes, 0);
+  memcpy(img.data(), &hdr, sizeof(hdr));
+  memcpy(img.data() + hdr.jobs_off, jobs, (size_t)n_jobs * sizeof(Job));
+  chunk_table_fill(reinterpret_cast<chunk_t*>(img.data() + hdr.chunks_off), jobs, n_jobs);
+  return img;
 }
 
 #ifdef __HIPCC__
@@ -63,11 +122,19 @@ CHUNK_HD uint32_t chunk_tail_len(uint64_t start4, uint64_t n_elem) {
 }
 
 #ifdef __HIPCC__
-// Host image -> device.  `img` is a pageable temporary, so the copy is waited for before the caller lets it die: the upload
-// entry points synchronise the stream (include/vlm_hip.h says so).
-static inline int chunk_upload(void* dst, const void* img, size_t bytes, hipStream_t s) {
-  if (hipMemcpyAsync(dst, img, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return VLM_ERR_LAUNCH;
+// Host image -> device, after `zero_bytes` behind it are zeroed (TIES: its histograms start at zero).  `img` is a pageable
+// temporary, so the copy is waited for before the caller lets it die: the upload entry points synchronise the stream
+// (include/vlm_hip.h says so).
+static inline int chunk_upload(void* dst, const std::vector<unsigned char>& img, size_t zero_bytes, hipStream_t s) {
+  if (zero_bytes && hipMemsetAsync((unsigned char*)dst + img.size(), 0, zero_bytes, s) != hipSuccess) return VLM_ERR_LAUNCH;
+  if (hipMemcpyAsync(dst, img.data(), img.size(), hipMemcpyHostToDevice, s) != hipSuccess) return VLM_ERR_LAUNCH;
   if (hipStreamSynchronize(s) != hipSuccess) return VLM_ERR_LAUNCH;
   return VLM_OK;
+}
+
+// `per_cu` workgroups per CU (256 CUs when the device does not say)
+static inline dim3 chunk_grid(int per_cu) {
+  const int cus = vlm_device_cus();
+  return dim3((cus <= 0 ? 256 : cus) * per_cu);
 }
 #endif

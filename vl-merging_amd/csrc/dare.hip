@@ -9,20 +9,18 @@
 //   vlm_dare_apply_kernel   one launch over the plan's 16-KiB chunk table (chunk_plan.h), the shape of vlm_ties_apply_kernel:
 //                           a workgroup owns a CONTIGUOUS run of chunks, 16-B non-temporal loads and stores, steps 1-5 of the
 //                           rule, and the per-job counters flushed (64-bit integer atomics) when the run leaves a job.
-// Steps 3-5 of VLM_DARE_TIES are ties_elem.h's, shared with ties.hip.  Integer counters only, so nothing depends on the order
+// Steps 3-5 of VLM_DARE_TIES are chunk_walk.h's, shared with ties.hip.  Integer counters only, so nothing depends on the order
 // workgroups run in.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
+// This file holds the rule (dare_elem, the draws) and the workspace layout; the walker, the run loop and the host checks are
+// chunk_walk.h's and chunk_plan.h's, as in ties.hip.
 #include "vlm_common.h"
-#include "chunk_plan.h"
 #include "philox.h"
-#include "ties_elem.h"
-#include <string.h>
-#include <vector>
+#include "chunk_walk.h"  // the chunk walker, the run loop, steps 3-5 and the counters: shared with ties.hip (and merge.hip)
 
 #define DARE_THREADS CHUNK_THREADS
-#define DARE_FLUSH_CHUNKS (1u << 19)  // a thread counts at most 16 per chunk: 2^23 per thread, 2^29 in the 64-lane wave sum, between flushes (32-bit)
 #define DARE_APPLY_BLOCKS_PER_CU 12   // vlm_ties_apply_kernel's rule; not A/B-measured against other values (docs/experiments.md, "DARE merge")
 
-static_assert(VLM_DARE_COUNTERS == VLM_TIES_COUNTERS, "dare.hip flushes its counters with ties_elem.h's ties_flush_counts");
+static_assert(VLM_DARE_COUNTERS == VLM_TIES_COUNTERS, "dare.hip flushes its counters with chunk_walk.h's ties_flush_counts");
 
 struct dare_view_t {
   const vlm_dare_header_t* hdr;
@@ -62,7 +60,7 @@ __device__ __forceinline__ float dare_elem(float c, const float* wv, const uint3
     n.c[m] += kept ? 1u : 0u;
     any += kept ? 1 : 0;
   }
-  if (MODE == VLM_DARE_TIES) return ties_elect<NSRC>(c, tt, p.lam, n);   // steps 4-5: the TIES rule's 3-5 (ties_elem.h)
+  if (MODE == VLM_DARE_TIES) return ties_elect<NSRC>(c, tt, p.lam, n);   // steps 4-5: the TIES rule's 3-5 (chunk_walk.h)
   float d = 0.0f;
   bool has_pos = false, has_neg = false;
 #pragma unroll
@@ -76,73 +74,28 @@ __device__ __forceinline__ float dare_elem(float c, const float* wv, const uint3
   return __fadd_rn(c, __fmul_rn(p.lam, d));                              // step 5
 }
 
+// The rule as chunk_stream's rule (chunk_walk.h).  Step 2: prep draws one Philox block per source for float4 idx4, and element c
+// of that float4 takes word c -- so the ragged tail's element 4 n4 + t takes word t of the block of float4 n4.
 template <int NSRC, int MODE>
-__device__ __forceinline__ void dare_apply_vec(const vlm_dare_job_t& j, const dare_param_t& p, uint64_t start4, uint64_t n4,
-                                               ties_counts_t& n) {
-  // no __restrict__: dst may be base or a source exactly.  Every load of a float4 precedes its store in program order.
-  f32x4* dst = reinterpret_cast<f32x4*>(j.dst);
-  const f32x4* base = reinterpret_cast<const f32x4*>(j.base);
-  const f32x4* s[NSRC];
+struct dare_rule {
+  struct draw_t {
+    philox4_t r[NSRC];
+  };
+  const dare_param_t& p;
+  ties_counts_t& n;
+  __device__ __forceinline__ draw_t prep(uint64_t idx4) const {
+    draw_t d;
 #pragma unroll
-  for (int m = 0; m < NSRC; ++m) s[m] = reinterpret_cast<const f32x4*>(j.src[m]);
-  f32x4 v[4][NSRC];
-  f32x4 b[4];
-  uint64_t idx[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    idx[u] = start4 + threadIdx.x + u * DARE_THREADS;
-    if (idx[u] < n4) {
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m) v[u][m] = __builtin_nontemporal_load(&s[m][idx[u]]);
-      b[u] = __builtin_nontemporal_load(&base[idx[u]]);
-    }
+    for (int m = 0; m < NSRC; ++m) d.r[m] = dare_draw4(p.seed, p.stream, (uint32_t)m, (uint32_t)idx4);
+    return d;
   }
+  __device__ __forceinline__ float elem(const draw_t& d, int c, float base, const float* wv) const {
+    uint32_t uu[NSRC];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    if (idx[u] < n4) {
-      philox4_t r[NSRC];  // step 2: one block per float4 and source, computed while the loads are in flight
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m) r[m] = dare_draw4(p.seed, p.stream, (uint32_t)m, (uint32_t)idx[u]);
-      f32x4 o;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float wv[NSRC];
-        uint32_t uu[NSRC];
-#pragma unroll
-        for (int m = 0; m < NSRC; ++m) {
-          wv[m] = v[u][m][c];
-          uu[m] = r[m].w[c];
-        }
-        o[c] = dare_elem<NSRC, MODE>(b[u][c], wv, uu, p, n);
-      }
-      __builtin_nontemporal_store(o, &dst[idx[u]]);
-    }
+    for (int m = 0; m < NSRC; ++m) uu[m] = c == 0 ? d.r[m].w[0] : (c == 1 ? d.r[m].w[1] : (c == 2 ? d.r[m].w[2] : d.r[m].w[3]));
+    return dare_elem<NSRC, MODE>(base, wv, uu, p, n);
   }
-}
-
-// element i = 4 n4 + t of the ragged end: word t of the block of float4 n4
-template <int NSRC, int MODE>
-__device__ __forceinline__ void dare_apply_tail(const vlm_dare_job_t& j, const dare_param_t& p, uint64_t n4, uint32_t t,
-                                                ties_counts_t& n) {
-  const uint64_t i = (n4 << 2) + t;
-  float wv[NSRC];
-  uint32_t uu[NSRC];
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) {
-    wv[m] = reinterpret_cast<const float*>(j.src[m])[i];
-    const philox4_t r = dare_draw4(p.seed, p.stream, (uint32_t)m, (uint32_t)n4);
-    uu[m] = t == 0 ? r.w[0] : (t == 1 ? r.w[1] : r.w[2]);  // t < 4 and t < n_elem % 4 <= 3
-  }
-  const float c = reinterpret_cast<const float*>(j.base)[i];
-  reinterpret_cast<float*>(j.dst)[i] = dare_elem<NSRC, MODE>(c, wv, uu, p, n);
-}
-
-template <int NSRC, int MODE>
-__device__ __forceinline__ void dare_chunk(const vlm_dare_job_t& j, const dare_param_t& p, uint64_t start4, ties_counts_t& n) {
-  const uint64_t n4 = j.n_elem >> 2;
-  dare_apply_vec<NSRC, MODE>(j, p, start4, n4, n);
-  if (threadIdx.x < chunk_tail_len(start4, j.n_elem)) dare_apply_tail<NSRC, MODE>(j, p, n4, threadIdx.x, n);
-}
+};
 
 __global__ __launch_bounds__(DARE_THREADS) void vlm_dare_clear_kernel(unsigned char* __restrict__ ws) {
   const dare_view_t w = dare_view(ws);
@@ -155,58 +108,46 @@ __global__ __launch_bounds__(DARE_THREADS) void vlm_dare_apply_kernel(unsigned c
   __shared__ u64_t red[(DARE_THREADS / 64) * VLM_DARE_COUNTERS];
   const dare_view_t w = dare_view(ws);
   uint64_t c0, c1;
-  ties_my_chunks(w.hdr->n_chunks, &c0, &c1);
-  if (c0 >= c1) return;
+  if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
   ties_counts_t n;
 #pragma unroll
   for (int k = 0; k < VLM_DARE_COUNTERS; ++k) n.c[k] = 0;
-  uint32_t cur = 0xffffffffu, since = 0;
   dare_param_t p = {0, 0, 0, false, 1.0f, 0.0f};
-  for (uint64_t c = c0; c < c1; ++c) {
-    const chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
-    if (ck.job != cur || since >= DARE_FLUSH_CHUNKS) {
-      if (cur != 0xffffffffu) ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_DARE_COUNTERS);
-      cur = ck.job;
-      since = 0;
-      const vlm_dare_job_t& jn = w.jobs[cur];
-      p.seed = jn.seed;
-      p.stream = jn.stream;
-      p.below = (uint32_t)jn.keep_below;
-      p.keep_all = (jn.keep_below >> 32) != 0;
-      p.rescale = jn.rescale;
-      p.lam = jn.lam;
-    }
-    ++since;
-    const vlm_dare_job_t& j = w.jobs[cur];
-    const uint64_t start4 = ck.start4;
-    if (j.mode == VLM_DARE_TIES) {
-      switch (j.n_src) {
-        case 1: dare_chunk<1, VLM_DARE_TIES>(j, p, start4, n); break;
-        case 2: dare_chunk<2, VLM_DARE_TIES>(j, p, start4, n); break;
-        case 3: dare_chunk<3, VLM_DARE_TIES>(j, p, start4, n); break;
-        default: dare_chunk<4, VLM_DARE_TIES>(j, p, start4, n); break;
-      }
-    } else {
-      switch (j.n_src) {
-        case 1: dare_chunk<1, VLM_DARE_LINEAR>(j, p, start4, n); break;
-        case 2: dare_chunk<2, VLM_DARE_LINEAR>(j, p, start4, n); break;
-        case 3: dare_chunk<3, VLM_DARE_LINEAR>(j, p, start4, n); break;
-        default: dare_chunk<4, VLM_DARE_LINEAR>(j, p, start4, n); break;
-      }
-    }
-  }
-  ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_DARE_COUNTERS);
+  chunk_run(
+      w.chunks, w.jobs, c0, c1,
+      [&](uint32_t cur) {
+        const vlm_dare_job_t& jn = w.jobs[cur];
+        p.seed = jn.seed;
+        p.stream = jn.stream;
+        p.below = (uint32_t)jn.keep_below;
+        p.keep_all = (jn.keep_below >> 32) != 0;
+        p.rescale = jn.rescale;
+        p.lam = jn.lam;
+      },
+      [&](const vlm_dare_job_t& j, uint64_t start4) {
+        with_nsrc(j.n_src, [&](auto S) {
+          if (j.mode == VLM_DARE_TIES) {
+            dare_rule<S(), VLM_DARE_TIES> rule{p, n};
+            chunk_stream<S(), true, true>(j, start4, rule);
+          } else {
+            dare_rule<S(), VLM_DARE_LINEAR> rule{p, n};
+            chunk_stream<S(), true, true>(j, start4, rule);
+          }
+        });
+      },
+      [&](uint32_t cur) { ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_DARE_COUNTERS); });
 }
 
 // fills every offset of `h` for n_jobs jobs and n_chunks chunks; returns the total size
 static size_t dare_layout(vlm_dare_header_t* h, uint64_t n_jobs, uint64_t n_chunks) {
+  chunk_layout_t at;
+  at.take(sizeof(vlm_dare_header_t));
   h->n_jobs = n_jobs;
   h->n_chunks = n_chunks;
-  size_t off = chunk_align_up(sizeof(vlm_dare_header_t), 256);
-  h->jobs_off = off;     off += chunk_align_up(n_jobs * sizeof(vlm_dare_job_t), 256);
-  h->chunks_off = off;   off += chunk_align_up(n_chunks * sizeof(chunk_t), 256);
-  h->counters_off = off; off += chunk_align_up(n_jobs * VLM_DARE_COUNTERS * sizeof(uint64_t), 256);
-  return off;
+  h->jobs_off = at.take(n_jobs * sizeof(vlm_dare_job_t));
+  h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
+  h->counters_off = at.take(n_jobs * VLM_DARE_COUNTERS * sizeof(uint64_t));
+  return at.off;
 }
 
 extern "C" size_t vlm_dare_plan_bytes(int n_jobs, uint64_t total_elems) {
@@ -215,28 +156,16 @@ extern "C" size_t vlm_dare_plan_bytes(int n_jobs, uint64_t total_elems) {
   return dare_layout(&h, (uint64_t)n_jobs, chunks_bound(n_jobs, total_elems));
 }
 
-// dst against one input: exactly the same range is fine (the pass is elementwise), any other meeting of the byte ranges
-// [a, a + 4 n) and [b, b + 4 n) is not
-static bool dare_partial_overlap(const void* a, const void* b, uint64_t n_elem) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  if (x == y) return false;
-  const uint64_t bytes = n_elem * 4;
-  return x < y ? (y - x) < bytes : (x - y) < bytes;
-}
-
 extern "C" int vlm_dare_plan_upload(const vlm_dare_job_t* jobs, int n_jobs, void* workspace, size_t workspace_bytes,
                                     void* stream) {
   if (!jobs || n_jobs <= 0 || !chunk_ptr_ok(workspace)) return VLM_ERR_ARG;
   uint64_t n_chunks = 0;
   for (int i = 0; i < n_jobs; ++i) {
     const vlm_dare_job_t& j = jobs[i];
-    if (j.n_src < 1 || j.n_src > VLM_MERGE_MAX_SRC || !j.dst || !j.base || j.n_elem == 0) return VLM_ERR_ARG;
-    if (j.mode != VLM_DARE_LINEAR && j.mode != VLM_DARE_TIES) return VLM_ERR_ARG;
+    if (j.n_elem == 0 || (j.mode != VLM_DARE_LINEAR && j.mode != VLM_DARE_TIES)) return VLM_ERR_ARG;
     if (j.keep_below < 1 || j.keep_below > (1ull << 32)) return VLM_ERR_ARG;
-    if (!chunk_len_ok(j.n_elem)) return VLM_ERR_UNSUPPORTED;  // before the byte ranges are formed
-    if (!chunk_ptr_ok(j.dst) || !chunk_ptr_ok(j.base) || dare_partial_overlap(j.dst, j.base, j.n_elem)) return VLM_ERR_ARG;
-    for (int m = 0; m < j.n_src; ++m)
-      if (!chunk_ptr_ok(j.src[m]) || dare_partial_overlap(j.dst, j.src[m], j.n_elem)) return VLM_ERR_ARG;
+    const int rc = chunk_job_check(j, CHUNK_OVERLAP_EXACT, true);
+    if (rc != VLM_OK) return rc;
     n_chunks += chunks_of(j.n_elem);
   }
   if (!chunk_count_ok(n_chunks)) return VLM_ERR_UNSUPPORTED;
@@ -244,23 +173,16 @@ extern "C" int vlm_dare_plan_upload(const vlm_dare_job_t* jobs, int n_jobs, void
   const size_t total = dare_layout(&hdr, (uint64_t)n_jobs, n_chunks);
   if (total > workspace_bytes) return VLM_ERR_WORKSPACE;
   // the host image ends where the counters begin: they are device-made (every run zeroes them first)
-  const size_t img_bytes = hdr.counters_off;
-  std::vector<unsigned char> img(img_bytes, 0);
-  memcpy(img.data(), &hdr, sizeof(hdr));
-  memcpy(img.data() + hdr.jobs_off, jobs, (size_t)n_jobs * sizeof(vlm_dare_job_t));
-  chunk_table_fill(reinterpret_cast<chunk_t*>(img.data() + hdr.chunks_off), jobs, n_jobs);
-  return chunk_upload(workspace, img.data(), img_bytes, (hipStream_t)stream);
+  return chunk_upload(workspace, chunk_image(hdr, jobs, n_jobs, hdr.counters_off), 0, (hipStream_t)stream);
 }
 
 extern "C" int vlm_dare_run(void* workspace, void* stream) {
   if (!workspace) return VLM_ERR_ARG;
-  int cus = vlm_device_cus();
-  if (cus <= 0) cus = 256;
   unsigned char* ws = (unsigned char*)workspace;
   hipStream_t s = (hipStream_t)stream;
   // two launches, stream-ordered, no host synchronisation: the sizes of the plan live in the workspace header
   hipLaunchKernelGGL(vlm_dare_clear_kernel, dim3(64), dim3(DARE_THREADS), 0, s, ws);
-  hipLaunchKernelGGL(vlm_dare_apply_kernel, dim3(cus * DARE_APPLY_BLOCKS_PER_CU), dim3(DARE_THREADS), 0, s, ws);
+  hipLaunchKernelGGL(vlm_dare_apply_kernel, chunk_grid(DARE_APPLY_BLOCKS_PER_CU), dim3(DARE_THREADS), 0, s, ws);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }

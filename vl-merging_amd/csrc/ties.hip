@@ -15,16 +15,15 @@
 //   vlm_ties_apply_kernel       steps 1-5 of the rule with the thresholds read from the workspace, and the per-job counters.
 // Integer counters only, so nothing depends on the order workgroups run in.  HBM-bound: every pass streams 4 (S + 1) B per
 // element; the apply pass also writes 4 B.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
+// This file holds the rules (ties_key, ties_bin, ties_elem), the scan kernel and the workspace layout.  The streaming body of a
+// chunk, a workgroup's run loop with its flush cap, the source-count dispatch, steps 3-5 and the counters are chunk_walk.h's; the
+// chunk table, the per-job checks, the host image, the upload and the grid rule are chunk_plan.h's.
 #include "vlm_common.h"
-#include "chunk_plan.h"
-#include "ties_elem.h"  // steps 3-5, the counters and the chunk runs: shared with dare.hip
-#include <string.h>
-#include <vector>
+#include "chunk_walk.h"  // the chunk walker, the run loop, steps 3-5 and the counters: shared with dare.hip (and merge.hip)
 
 #define TIES_THREADS CHUNK_THREADS  // the chunk walkers need the chunk's 256; the scan kernel uses the same block
 #define TIES_BINS 2048u           // bins per source in LDS and in global memory (pass 0 uses all, passes 1 and 2 use 1024)
-#define TIES_FLUSH_CHUNKS (1u << 19)  // 2^19 chunks x 4096 keys < 2^32: the 32-bit LDS bins cannot wrap between flushes
-#define TIES_HIST_BLOCKS_PER_CU 4  // 110 VGPRs: four workgroups (one wave per SIMD each) are resident per CU; 32 KiB LDS each
+#define TIES_HIST_BLOCKS_PER_CU 4  // under 128 VGPRs: four workgroups (one wave per SIMD each) are resident per CU; 32 KiB LDS each
 #define TIES_APPLY_BLOCKS_PER_CU 12  // three resident per CU (145 VGPRs): four even rounds
 #define TIES_SCAN_BLOCKS 1024
 // The three grid sizes above follow from the kernels' resident-workgroup counts (register and LDS use recorded by the build); none of
@@ -49,35 +48,18 @@ __device__ __forceinline__ void ties_bin(uint32_t key, uint32_t prefix, uint32_t
   else { if ((key >> 10) == (prefix >> 10)) atomicAdd(&h[key & 1023u], 1u); }
 }
 
+// a histogram pass as chunk_stream's rule (chunk_walk.h): stores nothing, bins every source of an element
 template <int PASS, int NSRC>
-__device__ __forceinline__ void ties_hist_vec(const vlm_ties_job_t& j, const uint32_t* prefix, uint64_t start4, uint64_t n4,
-                                              uint32_t* lds) {
-  const f32x4* __restrict__ base = reinterpret_cast<const f32x4*>(j.base);
-  const f32x4* __restrict__ s[NSRC];
+struct ties_hist_rule {
+  const uint32_t* prefix;
+  uint32_t* lds;
+  __device__ __forceinline__ chunk_no_prep prep(uint64_t) const { return {}; }
+  __device__ __forceinline__ float elem(chunk_no_prep, int, float c, const float* wv) const {
 #pragma unroll
-  for (int m = 0; m < NSRC; ++m) s[m] = reinterpret_cast<const f32x4*>(j.src[m]);
-  f32x4 v[4][NSRC];
-  f32x4 b[4];
-  uint64_t idx[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    idx[u] = start4 + threadIdx.x + u * TIES_THREADS;
-    if (idx[u] < n4) {
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m) v[u][m] = __builtin_nontemporal_load(&s[m][idx[u]]);
-      b[u] = __builtin_nontemporal_load(&base[idx[u]]);
-    }
+    for (int m = 0; m < NSRC; ++m) ties_bin<PASS>(ties_key(wv[m], c), prefix[m], lds + m * TIES_BINS);
+    return 0.0f;
   }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    if (idx[u] < n4) {
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ties_bin<PASS>(ties_key(v[u][m][c], b[u][c]), prefix[m], lds + m * TIES_BINS);
-    }
-  }
-}
+};
 
 struct ties_view_t {
   const vlm_ties_header_t* hdr;
@@ -122,42 +104,26 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_hist_kernel(unsigned ch
   __shared__ uint32_t lds[VLM_MERGE_MAX_SRC * TIES_BINS];
   const ties_view_t w = ties_view(ws);
   uint64_t c0, c1;
-  ties_my_chunks(w.hdr->n_chunks, &c0, &c1);
-  if (c0 >= c1) return;
+  if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
   for (uint32_t i = threadIdx.x; i < VLM_MERGE_MAX_SRC * TIES_BINS; i += TIES_THREADS) lds[i] = 0;
   __syncthreads();
-  uint32_t cur = 0xffffffffu, since = 0;
   uint32_t prefix[VLM_MERGE_MAX_SRC] = {0, 0, 0, 0};
-  for (uint64_t c = c0; c < c1; ++c) {
-    const chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
-    if (ck.job != cur || since >= TIES_FLUSH_CHUNKS) {
-      if (cur != 0xffffffffu) ties_flush<PASS>(lds, w.hist + (uint64_t)w.unit0[cur] * TIES_BINS, w.jobs[cur].n_src);
-      cur = ck.job;
-      since = 0;
-      if (PASS > 0) {
+  chunk_run(
+      w.chunks, w.jobs, c0, c1,
+      [&](uint32_t cur) {
+        if (PASS > 0) {
 #pragma unroll
-        for (int m = 0; m < VLM_MERGE_MAX_SRC; ++m)
-          if (m < w.jobs[cur].n_src) prefix[m] = w.state[w.unit0[cur] + m].key;
-      }
-    }
-    ++since;
-    const vlm_ties_job_t& j = w.jobs[cur];
-    const uint64_t n4 = j.n_elem >> 2;
-    const uint64_t start4 = ck.start4;
-    switch (j.n_src) {
-      case 1: ties_hist_vec<PASS, 1>(j, prefix, start4, n4, lds); break;
-      case 2: ties_hist_vec<PASS, 2>(j, prefix, start4, n4, lds); break;
-      case 3: ties_hist_vec<PASS, 3>(j, prefix, start4, n4, lds); break;
-      default: ties_hist_vec<PASS, 4>(j, prefix, start4, n4, lds); break;
-    }
-    if (threadIdx.x < chunk_tail_len(start4, j.n_elem)) {
-      const uint64_t i = (n4 << 2) + threadIdx.x;
-      const float b = reinterpret_cast<const float*>(j.base)[i];
-      for (int m = 0; m < j.n_src; ++m)
-        ties_bin<PASS>(ties_key(reinterpret_cast<const float*>(j.src[m])[i], b), prefix[m], lds + m * TIES_BINS);
-    }
-  }
-  ties_flush<PASS>(lds, w.hist + (uint64_t)w.unit0[cur] * TIES_BINS, w.jobs[cur].n_src);
+          for (int m = 0; m < VLM_MERGE_MAX_SRC; ++m)
+            if (m < w.jobs[cur].n_src) prefix[m] = w.state[w.unit0[cur] + m].key;
+        }
+      },
+      [&](const vlm_ties_job_t& j, uint64_t start4) {
+        with_nsrc(j.n_src, [&](auto S) {
+          ties_hist_rule<PASS, S()> rule{prefix, lds};
+          chunk_stream<S(), true, false>(j, start4, rule);
+        });
+      },
+      [&](uint32_t cur) { ties_flush<PASS>(lds, w.hist + (uint64_t)w.unit0[cur] * TIES_BINS, w.jobs[cur].n_src); });
 }
 
 // One workgroup per (job, source): find the bin that holds the rank-th largest key, walking down from the top bin.
@@ -226,105 +192,61 @@ __device__ __forceinline__ float ties_elem(float c, const float* wv, const uint3
     tt[m] = kept ? t : 0.0f;
     n.c[m] += kept ? 1u : 0u;
   }
-  return ties_elect<NSRC>(c, tt, lam, n);                                // steps 3-5 (ties_elem.h)
+  return ties_elect<NSRC>(c, tt, lam, n);                                // steps 3-5 (chunk_walk.h)
 }
 
+// steps 1-5 as chunk_stream's rule
 template <int NSRC>
-__device__ __forceinline__ void ties_apply_vec(const vlm_ties_job_t& j, const uint32_t* thr, uint64_t start4, uint64_t n4,
-                                               ties_counts_t& n) {
-  f32x4* __restrict__ dst = reinterpret_cast<f32x4*>(j.dst);
-  const f32x4* __restrict__ base = reinterpret_cast<const f32x4*>(j.base);
-  const f32x4* __restrict__ s[NSRC];
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) s[m] = reinterpret_cast<const f32x4*>(j.src[m]);
-  const float lam = j.lam;
-  f32x4 v[4][NSRC];
-  f32x4 b[4];
-  uint64_t idx[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    idx[u] = start4 + threadIdx.x + u * TIES_THREADS;
-    if (idx[u] < n4) {
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m) v[u][m] = __builtin_nontemporal_load(&s[m][idx[u]]);
-      b[u] = __builtin_nontemporal_load(&base[idx[u]]);
-    }
+struct ties_apply_rule {
+  const uint32_t* thr;
+  float lam;
+  ties_counts_t& n;
+  __device__ __forceinline__ chunk_no_prep prep(uint64_t) const { return {}; }
+  __device__ __forceinline__ float elem(chunk_no_prep, int, float c, const float* wv) const {
+    return ties_elem<NSRC>(c, wv, thr, lam, n);
   }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    if (idx[u] < n4) {
-      f32x4 o;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float wv[NSRC];
-#pragma unroll
-        for (int m = 0; m < NSRC; ++m) wv[m] = v[u][m][c];
-        o[c] = ties_elem<NSRC>(b[u][c], wv, thr, lam, n);
-      }
-      __builtin_nontemporal_store(o, &dst[idx[u]]);
-    }
-  }
-}
-
-template <int NSRC>
-__device__ __forceinline__ void ties_apply_tail(const vlm_ties_job_t& j, const uint32_t* thr, uint64_t i, ties_counts_t& n) {
-  float wv[NSRC];
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) wv[m] = reinterpret_cast<const float*>(j.src[m])[i];
-  reinterpret_cast<float*>(j.dst)[i] = ties_elem<NSRC>(reinterpret_cast<const float*>(j.base)[i], wv, thr, j.lam, n);
-}
+};
 
 __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_apply_kernel(unsigned char* __restrict__ ws) {
   __shared__ u64_t red[(TIES_THREADS / 64) * VLM_TIES_COUNTERS];
   const ties_view_t w = ties_view(ws);
   uint64_t c0, c1;
-  ties_my_chunks(w.hdr->n_chunks, &c0, &c1);
-  if (c0 >= c1) return;
+  if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
   ties_counts_t n;
 #pragma unroll
   for (int k = 0; k < VLM_TIES_COUNTERS; ++k) n.c[k] = 0;
-  uint32_t cur = 0xffffffffu, since = 0;
   uint32_t thr[VLM_MERGE_MAX_SRC] = {0, 0, 0, 0};
-  for (uint64_t c = c0; c < c1; ++c) {
-    const chunk_t ck = w.chunks[c];  // block-uniform => scalar loads
-    if (ck.job != cur || since >= TIES_FLUSH_CHUNKS) {
-      if (cur != 0xffffffffu) ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS);
-      cur = ck.job;
-      since = 0;
+  chunk_run(
+      w.chunks, w.jobs, c0, c1,
+      [&](uint32_t cur) {
 #pragma unroll
-      for (int m = 0; m < VLM_MERGE_MAX_SRC; ++m)
-        if (m < w.jobs[cur].n_src) thr[m] = w.state[w.unit0[cur] + m].key;
-    }
-    ++since;
-    const vlm_ties_job_t& j = w.jobs[cur];
-    const uint64_t n4 = j.n_elem >> 2;
-    const uint64_t start4 = ck.start4;
-    const bool tail = threadIdx.x < chunk_tail_len(start4, j.n_elem);
-    const uint64_t ti = (n4 << 2) + threadIdx.x;
-    switch (j.n_src) {
-      case 1: ties_apply_vec<1>(j, thr, start4, n4, n); if (tail) ties_apply_tail<1>(j, thr, ti, n); break;
-      case 2: ties_apply_vec<2>(j, thr, start4, n4, n); if (tail) ties_apply_tail<2>(j, thr, ti, n); break;
-      case 3: ties_apply_vec<3>(j, thr, start4, n4, n); if (tail) ties_apply_tail<3>(j, thr, ti, n); break;
-      default: ties_apply_vec<4>(j, thr, start4, n4, n); if (tail) ties_apply_tail<4>(j, thr, ti, n); break;
-    }
-  }
-  ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS);
+        for (int m = 0; m < VLM_MERGE_MAX_SRC; ++m)
+          if (m < w.jobs[cur].n_src) thr[m] = w.state[w.unit0[cur] + m].key;
+      },
+      [&](const vlm_ties_job_t& j, uint64_t start4) {
+        with_nsrc(j.n_src, [&](auto S) {
+          ties_apply_rule<S()> rule{thr, j.lam, n};
+          chunk_stream<S(), true, true>(j, start4, rule);
+        });
+      },
+      [&](uint32_t cur) { ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS); });
 }
 
 // fills every offset of `h` for n_jobs jobs, n_units (job, source) pairs and n_chunks chunks; returns the total size
 static size_t ties_layout(vlm_ties_header_t* h, uint64_t n_jobs, uint64_t n_units, uint64_t n_chunks) {
+  chunk_layout_t at;
+  at.take(sizeof(vlm_ties_header_t));
   h->n_jobs = n_jobs;
   h->n_units = n_units;
   h->n_chunks = n_chunks;
-  size_t off = chunk_align_up(sizeof(vlm_ties_header_t), 256);
-  h->jobs_off = off;     off += chunk_align_up(n_jobs * sizeof(vlm_ties_job_t), 256);
-  h->chunks_off = off;   off += chunk_align_up(n_chunks * sizeof(chunk_t), 256);
-  h->unit0_off = off;    off += chunk_align_up(n_jobs * sizeof(uint32_t), 256);
-  h->units_off = off;    off += chunk_align_up(n_units * sizeof(ties_unit_t), 256);
-  h->state_off = off;    off += chunk_align_up(n_units * sizeof(vlm_ties_state_t), 256);
-  h->counters_off = off; off += chunk_align_up(n_jobs * VLM_TIES_COUNTERS * sizeof(uint64_t), 256);
-  h->hist_off = off;     off += chunk_align_up(n_units * TIES_BINS * sizeof(uint64_t), 256);
-  return off;
+  h->jobs_off = at.take(n_jobs * sizeof(vlm_ties_job_t));
+  h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
+  h->unit0_off = at.take(n_jobs * sizeof(uint32_t));
+  h->units_off = at.take(n_units * sizeof(ties_unit_t));
+  h->state_off = at.take(n_units * sizeof(vlm_ties_state_t));
+  h->counters_off = at.take(n_jobs * VLM_TIES_COUNTERS * sizeof(uint64_t));
+  h->hist_off = at.take(n_units * TIES_BINS * sizeof(uint64_t));
+  return at.off;
 }
 
 extern "C" size_t vlm_ties_plan_bytes(int n_jobs, uint64_t total_elems) {
@@ -334,26 +256,17 @@ extern "C" size_t vlm_ties_plan_bytes(int n_jobs, uint64_t total_elems) {
   return ties_layout(&h, (uint64_t)n_jobs, (uint64_t)n_jobs * VLM_MERGE_MAX_SRC, chunks_bound(n_jobs, total_elems));
 }
 
-// do the byte ranges [a, a + 4 n) and [b, b + 4 n) meet?  (dst may not overlap an input: the selection passes re-read the inputs)
-static bool ties_overlap(const void* a, const void* b, uint64_t n_elem) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  const uint64_t bytes = n_elem * 4;
-  return x < y ? (y - x) < bytes : (x - y) < bytes;
-}
-
 extern "C" int vlm_ties_plan_upload(const vlm_ties_job_t* jobs, int n_jobs, void* workspace, size_t workspace_bytes,
                                     void* stream) {
   if (!jobs || n_jobs <= 0 || !chunk_ptr_ok(workspace)) return VLM_ERR_ARG;
   uint64_t n_chunks = 0, n_units = 0;
   for (int i = 0; i < n_jobs; ++i) {
     const vlm_ties_job_t& j = jobs[i];
-    if (j.n_src < 1 || j.n_src > VLM_MERGE_MAX_SRC || !j.dst || !j.base || j.n_elem == 0) return VLM_ERR_ARG;
-    if (!chunk_len_ok(j.n_elem)) return VLM_ERR_UNSUPPORTED;  // before the byte ranges are formed
-    if (!chunk_ptr_ok(j.dst) || !chunk_ptr_ok(j.base) || ties_overlap(j.dst, j.base, j.n_elem)) return VLM_ERR_ARG;
-    for (int m = 0; m < j.n_src; ++m) {
-      if (!chunk_ptr_ok(j.src[m]) || ties_overlap(j.dst, j.src[m], j.n_elem)) return VLM_ERR_ARG;
+    if (j.n_elem == 0) return VLM_ERR_ARG;
+    const int rc = chunk_job_check(j, CHUNK_OVERLAP_NONE, true);
+    if (rc != VLM_OK) return rc;
+    for (int m = 0; m < j.n_src; ++m)
       if (j.k[m] < 1 || j.k[m] > j.n_elem) return VLM_ERR_ARG;
-    }
     n_chunks += chunks_of(j.n_elem);
     n_units += (uint64_t)j.n_src;
   }
@@ -362,11 +275,7 @@ extern "C" int vlm_ties_plan_upload(const vlm_ties_job_t* jobs, int n_jobs, void
   const size_t total = ties_layout(&hdr, (uint64_t)n_jobs, n_units, n_chunks);
   if (total > workspace_bytes) return VLM_ERR_WORKSPACE;
   // the host image ends where the state begins: state, counters and histograms are device-made
-  const size_t img_bytes = hdr.state_off;
-  std::vector<unsigned char> img(img_bytes, 0);
-  memcpy(img.data(), &hdr, sizeof(hdr));
-  memcpy(img.data() + hdr.jobs_off, jobs, (size_t)n_jobs * sizeof(vlm_ties_job_t));
-  chunk_table_fill(reinterpret_cast<chunk_t*>(img.data() + hdr.chunks_off), jobs, n_jobs);
+  std::vector<unsigned char> img = chunk_image(hdr, jobs, n_jobs, hdr.state_off);
   uint32_t* unit0 = reinterpret_cast<uint32_t*>(img.data() + hdr.unit0_off);
   ties_unit_t* units = reinterpret_cast<ties_unit_t*>(img.data() + hdr.units_off);
   uint64_t u = 0;
@@ -378,21 +287,16 @@ extern "C" int vlm_ties_plan_upload(const vlm_ties_job_t* jobs, int n_jobs, void
       ++u;
     }
   }
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* ws = (unsigned char*)workspace;
   // the histograms start at zero; every scan launch leaves them at zero again
-  if (hipMemsetAsync(ws + hdr.state_off, 0, total - hdr.state_off, s) != hipSuccess) return VLM_ERR_LAUNCH;
-  return chunk_upload(ws, img.data(), img_bytes, s);
+  return chunk_upload(workspace, img, total - hdr.state_off, (hipStream_t)stream);
 }
 
 extern "C" int vlm_ties_run(void* workspace, void* stream) {
   if (!workspace) return VLM_ERR_ARG;
-  int cus = vlm_device_cus();
-  if (cus <= 0) cus = 256;
   unsigned char* ws = (unsigned char*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 block(TIES_THREADS), hist_grid(cus * TIES_HIST_BLOCKS_PER_CU), scan_grid(TIES_SCAN_BLOCKS),
-      apply_grid(cus * TIES_APPLY_BLOCKS_PER_CU);
+  const dim3 block(TIES_THREADS), hist_grid = chunk_grid(TIES_HIST_BLOCKS_PER_CU), scan_grid(TIES_SCAN_BLOCKS),
+             apply_grid = chunk_grid(TIES_APPLY_BLOCKS_PER_CU);
   // seven launches, stream-ordered, no host synchronisation: the sizes of the plan live in the workspace header
   hipLaunchKernelGGL((vlm_ties_hist_kernel<0>), hist_grid, block, 0, s, ws);
   hipLaunchKernelGGL((vlm_ties_scan_kernel<0>), scan_grid, block, 0, s, ws);

@@ -71,9 +71,11 @@ def interpolation_ratios(modalities, merge_ratio):
 
 class _Plan:
     """A device-resident job table of the merge family (csrc/chunk_plan.h): build with add(), upload once, run() enqueues the
-    kernels.  A subclass gives its ctypes job type and its three entry points, and writes add()."""
+    kernels.  A subclass gives its ctypes job type, its three entry points and how often a run streams the inputs, and writes
+    an add() that hands _add() a `fill(job)` for the fields of its own."""
 
-    GPU_ONLY = JOB = BYTES = UPLOAD = RUN = None
+    KIND = GPU_ONLY = JOB = BYTES = UPLOAD = RUN = COUNTERS = None
+    PASSES = 1  # how often a run reads every source and the base
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -82,6 +84,7 @@ class _Plan:
         if self.device.index is None:  # "cuda" names the current device; _dev compares devices, and cuda:0 != cuda would stage a
             self.device = torch.device("cuda", torch.cuda.current_device())  # copy of every tensor that is already there
         self.jobs = []
+        self.names: List[Optional[str]] = []
         self.keep = []  # keeps staged tensors alive
         self.total = 0
         self.bytes_read = 0
@@ -102,6 +105,40 @@ class _Plan:
             if t.shape != tensors[0].shape:
                 raise L.VlmError("merge sources disagree in shape: %s vs %s" % (t.shape, tensors[0].shape))
 
+    def _add(self, fill, srcs, base=None, out=None, name=None):
+        """The part of add() every method shares: stages the sources and the base, checks their count and shapes, allocates
+        `out` or checks the one given, fills the job's dst / base / src / n_src / n_elem, has `fill(job)` set the method's own
+        fields (if it raises, the plan has no new job) and appends the job.  Returns `out`."""
+        srcs = [self._dev(s) for s in srcs]
+        if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
+            raise L.VlmError("a %s job takes 1 .. %d sources, got %d" % (self.KIND, L.MERGE_MAX_SRC, len(srcs)))
+        ins = srcs if base is None else srcs + [self._dev(base)]
+        self._same_shape(ins)
+        if out is None:
+            out = torch.empty_like(srcs[0])
+        else:
+            self._same_shape([srcs[0], out])
+            if out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or (out.data_ptr() & 15):
+                raise L.VlmError("a %s output must be a contiguous, 16-byte aligned float32 tensor on %s" % (self.KIND, self.device))
+        self.keep.append(out)
+        n = srcs[0].numel()
+        job = self.JOB()
+        job.dst = out.data_ptr()
+        job.base = 0 if base is None else ins[-1].data_ptr()
+        for k, s in enumerate(srcs):
+            job.src[k] = s.data_ptr()
+        job.n_src = len(srcs)
+        job.n_elem = n
+        fill(job)
+        self.jobs.append(job)
+        self.names.append(name)
+        self.total += n
+        # what the passes move: each reads every source and the base once (TIES never stores the task vectors; its histograms,
+        # thresholds and counters, 16 KiB per source and tensor, are not counted; DARE's mask costs nothing)
+        self.bytes_read += self.PASSES * 4 * n * len(ins)
+        self.bytes_written += 4 * n
+        return out
+
     def upload(self):
         lib = L.get_lib()
         n = len(self.jobs)
@@ -118,38 +155,34 @@ class _Plan:
         with torch.cuda.device(self.device):
             L.check(getattr(L.get_lib(), self.RUN)(L.ptr(self.ws), L.stream_ptr()), self.RUN)
 
+    def _read(self, header_type):
+        """The workspace header after a run (this synchronises) and, per job, the start of its report row and the counters TIES
+        and DARE share: how many entries each source kept, the elements whose kept entries disagree in sign, the elements
+        nothing contributes to."""
+        if self.ws is None:
+            raise L.VlmError("%s.report() needs a plan that has run" % type(self).__name__)
+        hdr = header_type.from_buffer_copy(self.ws[: ctypes.sizeof(header_type)].cpu().numpy().tobytes())
+        counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * self.COUNTERS * hdr.n_jobs].cpu().numpy()
+        counters = counters.view("<u8").reshape(-1, self.COUNTERS)
+        rows = [({"dst": self.names[i], "n": int(job.n_elem)},
+                 {"kept": [int(counters[i, m]) for m in range(job.n_src)],
+                  "conflict": int(counters[i, L.MERGE_MAX_SRC]), "empty": int(counters[i, L.MERGE_MAX_SRC + 1])})
+                for i, job in enumerate(self.jobs)]
+        return hdr, rows
+
 
 class MergePlan(_Plan):
     """The job table of csrc/merge.hip; run() launches one kernel."""
 
-    GPU_ONLY, JOB = "the merge kernel runs on the GPU only", L.MergeJob
+    KIND, GPU_ONLY, JOB = "merge", "the merge kernel runs on the GPU only", L.MergeJob
     BYTES, UPLOAD, RUN = "vlm_merge_plan_bytes", "vlm_merge_plan_upload", "vlm_merge_run"
 
     def add(self, mode, srcs, ratios, base=None, out=None):
-        srcs = [self._dev(s) for s in srcs]
-        n = srcs[0].numel()
-        self._same_shape(srcs)
-        if out is None:
-            out = torch.empty_like(srcs[0])
-        self.keep.append(out)
-        job = L.MergeJob()
-        job.dst = out.data_ptr()
-        job.base = 0
-        if mode == L.MERGE_TASKVEC:
-            b = self._dev(base)
-            job.base = b.data_ptr()
-            self.bytes_read += 4 * n
-        for k, s in enumerate(srcs):
-            job.src[k] = s.data_ptr()
-            job.ratio[k] = float(ratios[k]) if ratios is not None else 1.0
-        job.n_src = len(srcs)
-        job.mode = mode
-        job.n_elem = n
-        self.jobs.append(job)
-        self.total += n
-        self.bytes_read += 4 * n * len(srcs)
-        self.bytes_written += 4 * n
-        return out
+        def fill(job):
+            for k in range(job.n_src):
+                job.ratio[k] = float(ratios[k]) if ratios is not None else 1.0
+            job.mode = mode
+        return self._add(fill, srcs, base if mode == L.MERGE_TASKVEC else None, out)
 
 
 def _passthrough(state_dict):
@@ -196,6 +229,14 @@ def _tensors(srcs):
     return [t for _, t in srcs]
 
 
+def _finish(plan, plan_out, always=False):
+    """The tail of every merge: run the plan if it has jobs; `plan_out` receives it then -- `always`: even without jobs."""
+    if plan.jobs:
+        plan.run()
+    if plan_out is not None and (always or plan.jobs):
+        plan_out.append(plan)
+
+
 def merge_weights(state_dict: Dict[str, torch.Tensor], config, device="cuda", plan_out: Optional[list] = None):
     """Interpolation merge (vilt_module.py:533-638)."""
     out = _passthrough(state_dict)
@@ -206,10 +247,7 @@ def merge_weights(state_dict: Dict[str, torch.Tensor], config, device="cuda", pl
             out[dst] = through
         else:
             out[dst] = plan.add(L.MERGE_LERP, _tensors(srcs), [ratios[m] for m, _ in srcs])
-    if plan.jobs:
-        plan.run()
-    if plan_out is not None:
-        plan_out.append(plan)
+    _finish(plan, plan_out, always=True)
     return out
 
 
@@ -225,10 +263,7 @@ def sum_task_vectors(state_dict, config, central_weight=None, device="cuda", pla
         else:
             r = [1 if len(mods) == 1 else lam] * len(srcs)
             out[dst] = plan.add(L.MERGE_TASKVEC, _tensors(srcs), r, base=central[dst])
-    if plan.jobs:
-        plan.run()
-    if plan_out is not None:
-        plan_out.append(plan)
+    _finish(plan, plan_out, always=True)
     return out
 
 
@@ -243,63 +278,52 @@ class TiesPlan(_Plan):
     """The job table of csrc/ties.hip; run() enqueues the seven launches of a TIES merge (three histogram passes of the radix
     select, a bin pick after each, the apply pass) without a host synchronisation."""
 
-    GPU_ONLY, JOB = "the TIES kernels run on the GPU only", L.TiesJob
-    BYTES, UPLOAD, RUN = "vlm_ties_plan_bytes", "vlm_ties_plan_upload", "vlm_ties_run"
+    KIND, GPU_ONLY, JOB = "TIES", "the TIES kernels run on the GPU only", L.TiesJob
+    BYTES, UPLOAD, RUN, COUNTERS = "vlm_ties_plan_bytes", "vlm_ties_plan_upload", "vlm_ties_run", L.TIES_COUNTERS
     PASSES = 4  # three selection passes + the apply pass: each streams every source and the central tensor once
-
-    def __init__(self, device):
-        super().__init__(device)
-        self.names: List[Optional[str]] = []
 
     def add(self, srcs, base, density=None, lam=1.0, keep=None, name=None):
         """One output tensor.  `density` gives K for every source (ties_keep_count); `keep` = explicit K per source instead."""
-        srcs = [self._dev(s) for s in srcs]
-        if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
-            raise L.VlmError("a TIES job takes 1 .. %d sources, got %d" % (L.MERGE_MAX_SRC, len(srcs)))
-        n = srcs[0].numel()
-        b = self._dev(base)
-        self._same_shape(srcs + [b])
-        if keep is None:
-            keep = [ties_keep_count(density, n)] * len(srcs)
-        out = torch.empty_like(srcs[0])
-        self.keep.append(out)
-        job = L.TiesJob()
-        job.dst = out.data_ptr()
-        job.base = b.data_ptr()
-        for k, s in enumerate(srcs):
-            job.src[k] = s.data_ptr()
-            job.k[k] = int(keep[k])
-        job.n_src = len(srcs)
-        job.n_elem = n
-        job.lam = float(lam)
-        self.jobs.append(job)
-        self.names.append(name)
-        self.total += n
-        # what the passes move: every pass re-reads the sources and the central tensor (the task vectors are never stored);
-        # the histograms, thresholds and counters (16 KiB per source and tensor) are not counted
-        self.bytes_read += self.PASSES * 4 * n * (len(srcs) + 1)
-        self.bytes_written += 4 * n
-        return out
+        def fill(job):
+            ks = [ties_keep_count(density, int(job.n_elem))] * job.n_src if keep is None else keep
+            for k in range(job.n_src):
+                job.k[k] = int(ks[k])
+            job.lam = float(lam)
+        return self._add(fill, srcs, base, name=name)
 
     def report(self):
         """Per job, read back after a run (this synchronises): the threshold per source as a float and as its key, how many
         entries each source kept, the elements whose kept entries disagree in sign, the elements no source contributes to."""
-        if self.ws is None:
-            raise L.VlmError("TiesPlan.report() needs a plan that has run")
-        hdr = L.TiesHeader.from_buffer_copy(self.ws[: ctypes.sizeof(L.TiesHeader)].cpu().numpy().tobytes())
+        hdr, rows = self._read(L.TiesHeader)
         state = self.ws[hdr.state_off: hdr.state_off + 16 * hdr.n_units].cpu().numpy().view("<u4").reshape(-1, 4)
-        counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * L.TIES_COUNTERS * hdr.n_jobs].cpu().numpy()
-        counters = counters.view("<u8").reshape(-1, L.TIES_COUNTERS)
-        rows, unit = [], 0
-        for i, job in enumerate(self.jobs):
-            S = job.n_src
-            keys = [int(state[unit + m, 0]) for m in range(S)]
-            rows.append({"dst": self.names[i], "n": int(job.n_elem), "K": [int(job.k[m]) for m in range(S)],
-                         "threshold": [struct.unpack("<f", struct.pack("<I", k))[0] for k in keys], "threshold_bits": keys,
-                         "kept": [int(counters[i, m]) for m in range(S)],
-                         "conflict": int(counters[i, L.MERGE_MAX_SRC]), "empty": int(counters[i, L.MERGE_MAX_SRC + 1])})
-            unit += S
-        return rows
+        out, unit = [], 0
+        for (head, counts), job in zip(rows, self.jobs):
+            keys = [int(state[unit + m, 0]) for m in range(job.n_src)]
+            out.append({**head, "K": [int(job.k[m]) for m in range(job.n_src)],
+                        "threshold": [struct.unpack("<f", struct.pack("<I", k))[0] for k in keys], "threshold_bits": keys, **counts})
+            unit += job.n_src
+        return out
+
+
+def _task_vector_merge(plan, add, state_dict, config, central_weight, plan_out, report_out):
+    """The driver ties_merge and dare_merge share: sum_task_vectors' dictionary logic, `add(dst, tensors, central)` for a tensor
+    with several sources, the task-vector job with ratio 1 for a layer with ONE source.  `plan_out` receives `plan` first, then
+    the MergePlan of the single-source layers (each only if it has jobs); `report_out` receives plan.report()."""
+    single = MergePlan(plan.device)
+    out = _passthrough(state_dict)
+    central = _central(central_weight, config)
+    for dst, mods, srcs, through in _walk(state_dict, config, central):
+        if srcs is None:
+            out[dst] = through
+        elif len(mods) == 1:
+            out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
+        else:
+            out[dst] = add(dst, _tensors(srcs), central[dst])
+    for p in (plan, single):
+        _finish(p, plan_out)
+    if report_out is not None:
+        report_out.extend(plan.report() if plan.jobs else [])
+    return out
 
 
 def ties_merge(state_dict, config, central_weight=None, density=0.2, lam=None, device="cuda", plan_out: Optional[list] = None,
@@ -314,24 +338,8 @@ def ties_merge(state_dict, config, central_weight=None, density=0.2, lam=None, d
     if lam is None:
         lam = config["sum_lambda"]
     plan = TiesPlan(device)
-    single = MergePlan(device)
-    out = _passthrough(state_dict)
-    central = _central(central_weight, config)
-    for dst, mods, srcs, through in _walk(state_dict, config, central):
-        if srcs is None:
-            out[dst] = through
-        elif len(mods) == 1:
-            out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
-        else:
-            out[dst] = plan.add(_tensors(srcs), central[dst], density=density, lam=lam, name=dst)
-    for p in (plan, single):
-        if p.jobs:
-            p.run()
-            if plan_out is not None:
-                plan_out.append(p)
-    if report_out is not None:
-        report_out.extend(plan.report() if plan.jobs else [])
-    return out
+    return _task_vector_merge(plan, lambda dst, srcs, c: plan.add(srcs, c, density=density, lam=lam, name=dst),
+                              state_dict, config, central_weight, plan_out, report_out)
 
 
 def dare_keep_below(drop):
@@ -364,12 +372,8 @@ class DarePlan(_Plan):
     """The job table of csrc/dare.hip; run() enqueues the counter reset and the one streaming launch of a DARE merge without a
     host synchronisation.  The mask is a function of (seed, stream, source, element) and is never stored."""
 
-    GPU_ONLY, JOB = "the DARE kernel runs on the GPU only", L.DareJob
-    BYTES, UPLOAD, RUN = "vlm_dare_plan_bytes", "vlm_dare_plan_upload", "vlm_dare_run"
-
-    def __init__(self, device):
-        super().__init__(device)
-        self.names: List[Optional[str]] = []
+    KIND, GPU_ONLY, JOB = "DARE", "the DARE kernel runs on the GPU only", L.DareJob
+    BYTES, UPLOAD, RUN, COUNTERS = "vlm_dare_plan_bytes", "vlm_dare_plan_upload", "vlm_dare_run", L.DARE_COUNTERS
 
     def add(self, srcs, base, drop, lam, seed, stream, mode, rescale=True, out=None, name=None):
         """One output tensor.  `out` may be `base` or one of `srcs` (the pass is elementwise) or any tensor that meets none of them."""
@@ -377,51 +381,21 @@ class DarePlan(_Plan):
         keep_below = dare_keep_below(drop)
         if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(stream) < 2 ** 32:
             raise L.VlmError("DARE seed must fit 64 bits and stream 32 bits, got %r, %r" % (seed, stream))
-        srcs = [self._dev(s) for s in srcs]
-        if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
-            raise L.VlmError("a DARE job takes 1 .. %d sources, got %d" % (L.MERGE_MAX_SRC, len(srcs)))
-        n = srcs[0].numel()
-        b = self._dev(base)
-        self._same_shape(srcs + [b])
-        if out is None:
-            out = torch.empty_like(srcs[0])
-        else:
-            self._same_shape([srcs[0], out])
-            if out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or (out.data_ptr() & 15):
-                raise L.VlmError("a DARE output must be a contiguous, 16-byte aligned float32 tensor on %s" % (self.device,))
-        self.keep.append(out)
-        job = L.DareJob()
-        job.dst = out.data_ptr()
-        job.base = b.data_ptr()
-        for k, s in enumerate(srcs):
-            job.src[k] = s.data_ptr()
-        job.keep_below = keep_below
-        job.seed = int(seed)
-        job.n_elem = n
-        job.n_src = len(srcs)
-        job.mode = mode
-        job.lam = float(lam)
-        job.rescale = dare_rescale(drop, rescale)
-        job.stream = int(stream)
-        self.jobs.append(job)
-        self.names.append(name)
-        self.total += n
-        self.bytes_read += 4 * n * (len(srcs) + 1)  # one pass: every source and the central tensor once; the mask costs nothing
-        self.bytes_written += 4 * n
-        return out
+
+        def fill(job):
+            job.keep_below = keep_below
+            job.seed = int(seed)
+            job.mode = mode
+            job.lam = float(lam)
+            job.rescale = dare_rescale(drop, rescale)
+            job.stream = int(stream)
+        return self._add(fill, srcs, base, out, name)
 
     def report(self):
         """Per job, read back after a run (this synchronises): how many entries each source kept, the elements whose kept entries
         disagree in sign, the elements nothing contributes to."""
-        if self.ws is None:
-            raise L.VlmError("DarePlan.report() needs a plan that has run")
-        hdr = L.DareHeader.from_buffer_copy(self.ws[: ctypes.sizeof(L.DareHeader)].cpu().numpy().tobytes())
-        counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * L.DARE_COUNTERS * hdr.n_jobs].cpu().numpy()
-        counters = counters.view("<u8").reshape(-1, L.DARE_COUNTERS)
-        return [{"dst": self.names[i], "n": int(job.n_elem), "keep_below": int(job.keep_below),
-                 "kept": [int(counters[i, m]) for m in range(job.n_src)],
-                 "conflict": int(counters[i, L.MERGE_MAX_SRC]), "empty": int(counters[i, L.MERGE_MAX_SRC + 1])}
-                for i, job in enumerate(self.jobs)]
+        _, rows = self._read(L.DareHeader)
+        return [{**head, "keep_below": int(job.keep_below), **counts} for (head, counts), job in zip(rows, self.jobs)]
 
 
 DARE_STREAMS_PER_LAYER = 13  # the tensor names of a layer (_tensor_names)
@@ -450,21 +424,6 @@ def dare_merge(state_dict, config, central_weight=None, drop=0.9, lam=None, seed
     if lam is None:
         lam = config["sum_lambda"]
     plan = DarePlan(device)
-    single = MergePlan(device)
-    out = _passthrough(state_dict)
-    central = _central(central_weight, config)
-    for dst, mods, srcs, through in _walk(state_dict, config, central):
-        if srcs is None:
-            out[dst] = through
-        elif len(mods) == 1:
-            out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
-        else:
-            out[dst] = plan.add(_tensors(srcs), central[dst], drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst)
-    for p in (plan, single):
-        if p.jobs:
-            p.run()
-            if plan_out is not None:
-                plan_out.append(p)
-    if report_out is not None:
-        report_out.extend(plan.report() if plan.jobs else [])
-    return out
+    return _task_vector_merge(
+        plan, lambda dst, srcs, c: plan.add(srcs, c, drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
+        state_dict, config, central_weight, plan_out, report_out)

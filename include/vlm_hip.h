@@ -204,6 +204,80 @@ int vlm_dare_plan_upload(const vlm_dare_job_t* jobs_host, int n_jobs, void* work
 int vlm_dare_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Expert-pair statistics (L2 distance, cosine similarity, soft sign dissimilarity and its truncated form, sign conflicts),
+ * csrc/pairstats.hip.  NO REFERENCE SITE: the reference ships no such measure; the arithmetic below is the specification and is
+ * pinned to a numpy restatement of it (tests/pairstats_restatement.py), not to the reference.  One job = one tensor with sources
+ * W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), an optional central tensor c (base, may be NULL) and one threshold key tkey[m]
+ * per source.  A job writes no tensor.  Per element i; fp32 operations round once, no FMA; "f64" = the operand widened exactly
+ * and the operation done in double, one rounding:
+ *   1. x_m = W_m - c (fp32) with a base, else x_m = W_m;  key(x) = bits(x) & 0x7fffffff (the TIES key);  in_m = key(x_m) >= tkey[m]
+ *   2. per source:  sq[m] += f64(x_m) * f64(x_m);  nnz[m] += (x_m != 0)
+ *   3. per pair (a, b), a < b < S, in slot b (b - 1) / 2 + a (the slot does not depend on S):
+ *        den = |x_a| + |x_b| (fp32);  live = den > 0;  r = |x_a + x_b| / den (fp32, correctly rounded) if live else +0.0
+ *        conf = (x_a > 0 and x_b < 0) or (x_a < 0 and x_b > 0);  t = live and (in_a or in_b)
+ *        dot += f64(x_a) * f64(x_b);  dist2 += d * d with d = f64(x_a) - f64(x_b);  ssd += f64(r);  tssd += t ? f64(r) : +0.0
+ *        live += live;  conflict += conf;  tlive += t;  tconflict += (t and conf)
+ * The order of summation is part of the rule, so a result is the same bytes whatever the grid, the job's place in a plan or the
+ * number of runs.  Every accumulation starts at +0.0.
+ *   thread     thread t of a 16-KiB chunk (256 threads) adds its float4s u = 0 .. 3 (float4 index start4 + t + 256 u) and in each
+ *              the components 0 .. 3, in that order; then the ragged-tail element 4 n4 + t (n4 = n_elem / 4) if the chunk owns the
+ *              tail and t < (n_elem & 3).  A thread with nothing in range contributes +0.0.
+ *   wave       the 64 lanes are folded by halves, offsets 32, 16, 8, 4, 2, 1: after the first fold lane l holds v_l + v_{l+32}
+ *   workgroup  the four waves are added as ((w0 + w1) + w2) + w3: the chunk's record
+ *   job        the records of a job are added one after the other in chunk order
+ * The integer statistics are plain sums.  Slots of sources and pairs a job does not have are zero.  Non-finite inputs are
+ * outside the contract.  The derived measures (sqrt(dist2), dot / sqrt(sq_a sq_b), 1 - ssd / live, ...) are the caller's.
+ */
+#define VLM_PAIRSTATS_PAIRS 6   /* VLM_MERGE_MAX_SRC (VLM_MERGE_MAX_SRC - 1) / 2 */
+
+typedef struct {
+  const void* base;                     /* f32 [n_elem]: the central tensor c, or NULL */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each */
+  uint64_t n_elem;
+  uint32_t tkey[VLM_MERGE_MAX_SRC];     /* step 1: threshold keys; 0 puts every entry in */
+  int32_t n_src;
+  int32_t reserved;
+} vlm_pairstats_job_t;
+
+/* The workspace of a pair-statistics plan BEGINS with this header (byte offsets from its start); jobs keep their upload order. */
+typedef struct {
+  uint64_t n_jobs, n_chunks;
+  uint64_t jobs_off;      /* vlm_pairstats_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table */
+  uint64_t first_off;     /* uint64 [n_jobs + 1]: the first chunk of each job, then n_chunks */
+  uint64_t records_off;   /* vlm_pairstats_result_t [n_chunks]: one record per chunk, overwritten by every run */
+  uint64_t results_off;   /* vlm_pairstats_result_t [n_jobs]: overwritten by every run */
+} vlm_pairstats_header_t;
+
+/* per job after a run (and per chunk in between): 28 doubles, then 28 counts */
+typedef struct {
+  double sq[VLM_MERGE_MAX_SRC];
+  double dot[6];
+  double dist2[6];
+  double ssd[6];
+  double tssd[6];
+  uint64_t nnz[VLM_MERGE_MAX_SRC];
+  uint64_t live[6];
+  uint64_t conflict[6];
+  uint64_t tlive[6];
+  uint64_t tconflict[6];
+} vlm_pairstats_result_t;
+
+/* Bytes of device workspace a pair-statistics plan for n_jobs jobs over total_elems elements needs (header, jobs, chunk table,
+ * first-chunk table, one record per chunk, one result per job).  No reference site. */
+size_t vlm_pairstats_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (pointers non-NULL and 16-byte aligned, base may be NULL; 1 <= n_src <= VLM_MERGE_MAX_SRC and n_elem > 0, else
+ * VLM_ERR_ARG; a length or chunk count past 32 bits of float4s is VLM_ERR_UNSUPPORTED), build the chunk table on the host and
+ * copy header + jobs + tables into `workspace` (16-byte aligned).  SYNCHRONISES `stream` before it returns (pageable temporary
+ * source); it is the last host synchronisation of a plan.  Implements no step of the rule; no reference site. */
+int vlm_pairstats_plan_upload(const vlm_pairstats_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes,
+                              void* stream);
+/* Run an uploaded plan: ONE streaming launch over all jobs (steps 1-3, one record per chunk), then one launch that adds every
+ * job's records in chunk order; no atomics, no clearing launch, no host synchronisation.  The inputs are only read.  May be
+ * called again on the same workspace and gives the same bytes.  One run at a time per workspace.  No reference site. */
+int vlm_pairstats_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

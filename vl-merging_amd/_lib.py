@@ -82,6 +82,41 @@ class DareHeader(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("n_jobs", "n_chunks", "jobs_off", "chunks_off", "counters_off")]
 
 
+PAIRSTATS_PAIRS = MERGE_MAX_SRC * (MERGE_MAX_SRC - 1) // 2  # VLM_PAIRSTATS_PAIRS
+
+
+def pair_slot(a, b):
+    """The slot of the pair (a, b), a < b, in a pair-statistics result: it does not depend on the job's source count."""
+    if not 0 <= a < b < MERGE_MAX_SRC:
+        raise ValueError("a pair is (a, b) with 0 <= a < b < %d, got (%r, %r)" % (MERGE_MAX_SRC, a, b))
+    return b * (b - 1) // 2 + a
+
+
+class PairStatsJob(ctypes.Structure):
+    """vlm_pairstats_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("n_elem", c_u64),
+        ("tkey", ctypes.c_uint32 * MERGE_MAX_SRC),
+        ("n_src", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PairStatsHeader(ctypes.Structure):
+    """vlm_pairstats_header_t: the first bytes of a pair-statistics plan's workspace."""
+    _fields_ = [(n, c_u64) for n in ("n_jobs", "n_chunks", "jobs_off", "chunks_off", "first_off", "records_off", "results_off")]
+
+
+class PairStatsResult(ctypes.Structure):
+    """vlm_pairstats_result_t: the raw sums of one job."""
+    _fields_ = ([("sq", ctypes.c_double * MERGE_MAX_SRC)]
+                + [(n, ctypes.c_double * PAIRSTATS_PAIRS) for n in ("dot", "dist2", "ssd", "tssd")]
+                + [("nnz", c_u64 * MERGE_MAX_SRC)]
+                + [(n, c_u64 * PAIRSTATS_PAIRS) for n in ("live", "conflict", "tlive", "tconflict")])
+
+
 class ScatterSrc(ctypes.Structure):
     """vlm_scatter_src_t of include/vlm_hip.h."""
     _fields_ = [("g", c_void_p), ("g_is_f32", ctypes.c_int32), ("ld", ctypes.c_int32), ("first_row", ctypes.c_int32),
@@ -174,6 +209,9 @@ SIGNATURES = {
     "vlm_dare_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_dare_plan_upload": (c_int, [ctypes.POINTER(DareJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_dare_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_pairstats_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_pairstats_plan_upload": (c_int, [ctypes.POINTER(PairStatsJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_pairstats_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_bf16_grouped": (c_int, [c_int, ctypes.POINTER(GemmGroup), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

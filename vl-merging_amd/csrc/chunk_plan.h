@@ -61,13 +61,18 @@ static inline bool chunk_input_ok(chunk_overlap_t overlap, const void* dst, cons
 
 // The checks on a job's fields dst, base, src, n_src and n_elem, in the family's order of precedence.  `need_base`: a NULL base
 // is VLM_ERR_ARG (otherwise it is skipped).  Where byte ranges are compared, the length is checked before they are formed.
-template <class Job>
+// HAS_DST = false: a job type without a `dst` field (pair statistics write no tensor) -- nothing is asked of an output and no
+// byte ranges are compared, whatever `overlap` says; the inputs' pointers, the source count and the length are checked as ever.
+template <bool HAS_DST = true, class Job>
 static inline int chunk_job_check(const Job& j, chunk_overlap_t overlap, bool need_base) {
-  if (j.n_src < 1 || j.n_src > VLM_MERGE_MAX_SRC || !j.dst || (need_base && !j.base)) return VLM_ERR_ARG;
+  const void* dst = nullptr;
+  if constexpr (HAS_DST) dst = j.dst;
+  else overlap = CHUNK_OVERLAP_UNCHECKED;
+  if (j.n_src < 1 || j.n_src > VLM_MERGE_MAX_SRC || (HAS_DST && !dst) || (need_base && !j.base)) return VLM_ERR_ARG;
   if (overlap != CHUNK_OVERLAP_UNCHECKED && !chunk_len_ok(j.n_elem)) return VLM_ERR_UNSUPPORTED;
-  if (!chunk_ptr_ok(j.dst) || (j.base && !chunk_input_ok(overlap, j.dst, j.base, j.n_elem))) return VLM_ERR_ARG;
+  if ((HAS_DST && !chunk_ptr_ok(dst)) || (j.base && !chunk_input_ok(overlap, dst, j.base, j.n_elem))) return VLM_ERR_ARG;
   for (int m = 0; m < j.n_src; ++m)
-    if (!chunk_input_ok(overlap, j.dst, j.src[m], j.n_elem)) return VLM_ERR_ARG;
+    if (!chunk_input_ok(overlap, dst, j.src[m], j.n_elem)) return VLM_ERR_ARG;
   return chunk_len_ok(j.n_elem) ? VLM_OK : VLM_ERR_UNSUPPORTED;
 }
 

@@ -43,7 +43,8 @@ struct chunk_no_prep {  // what a rule's prep() returns when a float4 needs no p
 template <int NSRC, bool BASE, bool STORE, class Job, class Rule>
 __device__ __forceinline__ void chunk_stream(const Job& j, uint64_t start4, Rule& rule) {
   const uint64_t n4 = j.n_elem >> 2;
-  f32x4* dst = reinterpret_cast<f32x4*>(j.dst);
+  f32x4* dst = nullptr;  // a job type without a dst field (pair statistics) streams with STORE = false
+  if constexpr (STORE) dst = reinterpret_cast<f32x4*>(j.dst);
   const f32x4* base = BASE ? reinterpret_cast<const f32x4*>(j.base) : nullptr;
   const f32x4* s[NSRC];
 #pragma unroll
@@ -82,7 +83,7 @@ __device__ __forceinline__ void chunk_stream(const Job& j, uint64_t start4, Rule
     for (int m = 0; m < NSRC; ++m) w[m] = reinterpret_cast<const float*>(j.src[m])[i];
     const float bt = BASE ? reinterpret_cast<const float*>(j.base)[i] : 0.0f;
     const float o = rule.elem(rule.prep(n4), (int)threadIdx.x, bt, w);
-    if (STORE) reinterpret_cast<float*>(j.dst)[i] = o;
+    if constexpr (STORE) reinterpret_cast<float*>(j.dst)[i] = o;
   }
 }
 

@@ -1,4 +1,5 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE.
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE -- and the expert-pair statistics
+(expert_stats) that say how far apart the experts are before any of them is tried.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
 (reference src/vilt/modules/vilt_module.py:533-638, :640-746, :366-531): same `state_dict -> state_dict`
@@ -9,7 +10,8 @@ launch of the HIP merge kernel (csrc/merge.hip) and is bit-exact with the refere
 ties_merge (TIES-merging, Yadav et al. 2023) has NO reference site: the reference has no TIES.  It takes what sum_task_vectors
 takes and follows its dictionary logic; its arithmetic (include/vlm_hip.h, csrc/ties.hip) is pinned to a numpy restatement of
 the rule (tests/ties_restatement.py), not to the reference.  dare_merge (DARE, Yu et al. 2023) likewise: no reference site, the
-rule in include/vlm_hip.h, csrc/dare.hip held to tests/dare_restatement.py.
+rule in include/vlm_hip.h, csrc/dare.hip held to tests/dare_restatement.py.  expert_stats likewise: the rule (with the order of
+its sums) in include/vlm_hip.h, csrc/pairstats.hip held to tests/pairstats_restatement.py.
 """
 import ctypes
 import math
@@ -76,6 +78,7 @@ class _Plan:
 
     KIND = GPU_ONLY = JOB = BYTES = UPLOAD = RUN = COUNTERS = None
     PASSES = 1  # how often a run reads every source and the base
+    HAS_DST = True  # a job writes one tensor (PairStatsPlan: none)
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -108,22 +111,27 @@ class _Plan:
     def _add(self, fill, srcs, base=None, out=None, name=None):
         """The part of add() every method shares: stages the sources and the base, checks their count and shapes, allocates
         `out` or checks the one given, fills the job's dst / base / src / n_src / n_elem, has `fill(job)` set the method's own
-        fields (if it raises, the plan has no new job) and appends the job.  Returns `out`."""
+        fields (if it raises, the plan has no new job) and appends the job.  Returns `out`.  A plan without HAS_DST has no
+        output: nothing is allocated, the job has no dst, nothing is counted as written, and None is returned."""
         srcs = [self._dev(s) for s in srcs]
         if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
             raise L.VlmError("a %s job takes 1 .. %d sources, got %d" % (self.KIND, L.MERGE_MAX_SRC, len(srcs)))
         ins = srcs if base is None else srcs + [self._dev(base)]
         self._same_shape(ins)
-        if out is None:
+        if not self.HAS_DST:
+            out = None
+        elif out is None:
             out = torch.empty_like(srcs[0])
         else:
             self._same_shape([srcs[0], out])
             if out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or (out.data_ptr() & 15):
                 raise L.VlmError("a %s output must be a contiguous, 16-byte aligned float32 tensor on %s" % (self.KIND, self.device))
-        self.keep.append(out)
+        if self.HAS_DST:
+            self.keep.append(out)
         n = srcs[0].numel()
         job = self.JOB()
-        job.dst = out.data_ptr()
+        if self.HAS_DST:
+            job.dst = out.data_ptr()
         job.base = 0 if base is None else ins[-1].data_ptr()
         for k, s in enumerate(srcs):
             job.src[k] = s.data_ptr()
@@ -136,7 +144,7 @@ class _Plan:
         # what the passes move: each reads every source and the base once (TIES never stores the task vectors; its histograms,
         # thresholds and counters, 16 KiB per source and tensor, are not counted; DARE's mask costs nothing)
         self.bytes_read += self.PASSES * 4 * n * len(ins)
-        self.bytes_written += 4 * n
+        self.bytes_written += 4 * n if self.HAS_DST else 0
         return out
 
     def upload(self):
@@ -427,3 +435,143 @@ def dare_merge(state_dict, config, central_weight=None, drop=0.9, lam=None, seed
     return _task_vector_merge(
         plan, lambda dst, srcs, c: plan.add(srcs, c, drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
         state_dict, config, central_weight, plan_out, report_out)
+
+
+# ------------------------------------------------------------------------------------------------- expert-pair statistics
+_PAIR_SUMS = ("dot", "dist2", "ssd_sum", "tssd_sum")          # doubles
+_PAIR_COUNTS = ("live", "conflict", "tlive", "tconflict")     # integers
+
+
+def pair_derived(p):
+    """The measures derived from a pair's raw sums, in python doubles; None where the denominator is zero."""
+    norm = math.sqrt(p["sq_a"] * p["sq_b"])
+    return {"l2": math.sqrt(p["dist2"]),
+            "cosine": p["dot"] / norm if norm != 0 else None,
+            "ssd": 1.0 - p["ssd_sum"] / p["live"] if p["live"] else None,
+            "tssd": 1.0 - p["tssd_sum"] / p["tlive"] if p["tlive"] else None,
+            "conflict_rate": p["conflict"] / p["live"] if p["live"] else None}
+
+
+def float32_bits(x):
+    """bits(float32(x)) for a python double x."""
+    return struct.unpack("<I", struct.pack("<f", x))[0]
+
+
+class PairStatsPlan(_Plan):
+    """The job table of csrc/pairstats.hip; run() enqueues the streaming launch and the fold without a host synchronisation.
+    A job reads its sources (and its base) and writes no tensor: add() allocates nothing."""
+
+    KIND, GPU_ONLY, JOB = "pair-statistics", "the pair-statistics kernels run on the GPU only", L.PairStatsJob
+    BYTES, UPLOAD, RUN = "vlm_pairstats_plan_bytes", "vlm_pairstats_plan_upload", "vlm_pairstats_run"
+    HAS_DST = False
+
+    @staticmethod
+    def _keys(tkeys, n_src):
+        ks = [0] * n_src if tkeys is None else [int(k) for k in tkeys]
+        if len(ks) != n_src or not all(0 <= k < 2 ** 32 for k in ks):
+            raise L.VlmError("a pair-statistics job takes one 32-bit threshold key per source, got %r for %d sources" % (tkeys, n_src))
+        return ks
+
+    def add(self, srcs, base=None, tkeys=None, name=None):
+        """One tensor.  `base`: the central tensor the sources are taken relative to (None: the sources as they are);
+        `tkeys`: the threshold key (bits of a non-negative float32) per source for the truncated statistics, default 0."""
+        def fill(job):
+            for k, key in enumerate(self._keys(tkeys, job.n_src)):
+                job.tkey[k] = key
+        self._add(fill, srcs, base, name=name)
+
+    def set_tkeys(self, i, tkeys):
+        """Other threshold keys for job i: the next run() uploads the plan again (a host synchronisation)."""
+        job = self.jobs[i]
+        for k, key in enumerate(self._keys(tkeys, job.n_src)):
+            job.tkey[k] = key
+        self.ws = None
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): the raw sums as the device left them -- `sq`, `nnz` per source;
+        per pair (a, b), a < b, in the order of their slots, the sums of the rule (include/vlm_hip.h) with both sides' `sq` --
+        and the derived measures (pair_derived)."""
+        if self.ws is None:
+            raise L.VlmError("PairStatsPlan.report() needs a plan that has run")
+        hdr = L.PairStatsHeader.from_buffer_copy(self.ws[: ctypes.sizeof(L.PairStatsHeader)].cpu().numpy().tobytes())
+        size = ctypes.sizeof(L.PairStatsResult)
+        raw = self.ws[hdr.results_off: hdr.results_off + size * hdr.n_jobs].cpu().numpy().tobytes()
+        rows = []
+        for i, job in enumerate(self.jobs):
+            r = L.PairStatsResult.from_buffer_copy(raw[i * size: (i + 1) * size])
+            S = job.n_src
+            pairs = []
+            for b in range(1, S):
+                for a in range(b):
+                    k = L.pair_slot(a, b)
+                    p = {"a": a, "b": b, "sq_a": r.sq[a], "sq_b": r.sq[b], "dot": r.dot[k], "dist2": r.dist2[k], "ssd_sum": r.ssd[k],
+                         "tssd_sum": r.tssd[k], "live": int(r.live[k]), "conflict": int(r.conflict[k]), "tlive": int(r.tlive[k]),
+                         "tconflict": int(r.tconflict[k])}
+                    p.update(pair_derived(p))
+                    pairs.append(p)
+            rows.append({"dst": self.names[i], "n": int(job.n_elem), "tkey": [int(job.tkey[m]) for m in range(S)],
+                         "sq": [r.sq[m] for m in range(S)], "nnz": [int(r.nnz[m]) for m in range(S)], "pairs": pairs})
+        return rows
+
+
+def rms_tkeys(row, trunc_rms):
+    """The threshold keys of a report row for `trunc_rms` = r: bits(float32(r * sqrt(sq_m / n))), in python doubles."""
+    return [float32_bits(trunc_rms * math.sqrt(sq / row["n"])) for sq in row["sq"]]
+
+
+def expert_stats(state_dict, config, central_weight=None, raw=False, trunc_rms=None, device="cuda",
+                 plan_out: Optional[list] = None):
+    """How far apart the modality experts are, per tensor and over the checkpoint: squared norms, dot products, L2 distance,
+    cosine similarity, soft sign dissimilarity (1 - mean |x_a + x_b| / (|x_a| + |x_b|) over the elements where either is
+    non-zero), its truncated form and sign-conflict counts between every pair of experts (no reference site; the rule:
+    include/vlm_hip.h).  Nothing is merged and no tensor is written.
+
+    The statistics are those of the task vectors `W_m - central`: the walk is sum_task_vectors' (same keys, same pass-through rule,
+    same KeyError behaviour; `central_weight` defaults to torch.load(config["central_weight"])).  `raw=True` takes the experts'
+    weights as they are, needs no central checkpoint and walks as merge_weights does.  One job per tensor whose sources are all
+    present; a layer with ONE source has `sq` and `nnz` only.
+
+    `trunc_rms=r` (r > 0): the truncated statistics count an element only if one of the two entries has a magnitude of at least
+    r times its own tensor's root mean square.  The thresholds come from the sums of a first run, so this costs a SECOND pass
+    over the checkpoint and a host synchronisation between the two.  With None every threshold is zero: `tssd_sum == ssd_sum`
+    and `tlive == live`.
+
+    Returns {"raw", "trunc_rms", "tensors": [row per tensor, in the walk's order], "summary": {pair name: sums and measures}}.
+    A row names its sources ("v", "l", "vl"), keys `sq`, `nnz`, `tkey` by them and its pairs by "v-l", "v-vl", "l-vl".  The
+    summary adds a pair's raw sums over all tensors (math.fsum for the doubles) and derives the same measures from them.
+    Reading the results back synchronises.  `plan_out` receives the PairStatsPlan if it has jobs."""
+    if trunc_rms is not None and not (trunc_rms > 0.0 and math.isfinite(trunc_rms)):  # also rejects NaN
+        raise ValueError("trunc_rms must be a positive finite number, got %r" % (trunc_rms,))
+    plan = PairStatsPlan(device)
+    central = None if raw else _central(central_weight, config)
+    mods_of = []
+    for dst, mods, srcs, through in _walk(state_dict, config, central):
+        if srcs is not None:
+            plan.add(_tensors(srcs), None if raw else central[dst], name=dst)
+            mods_of.append([m for m, _ in srcs])
+    rows = []
+    if plan.jobs:
+        plan.run()
+        rows = plan.report()
+        if trunc_rms is not None:
+            for i, row in enumerate(rows):
+                plan.set_tkeys(i, rms_tkeys(row, trunc_rms))
+            plan.run()
+            rows = plan.report()
+        if plan_out is not None:
+            plan_out.append(plan)
+    tensors = []
+    for row, mods in zip(rows, mods_of):
+        tensors.append({"dst": row["dst"], "n": row["n"], "sources": mods,
+                        **{k: dict(zip(mods, row[k])) for k in ("sq", "nnz", "tkey")},
+                        "pairs": {"%s-%s" % (mods[p["a"]], mods[p["b"]]): {k: v for k, v in p.items() if k not in ("a", "b")}
+                                  for p in row["pairs"]}})
+    summary = {}
+    for name in sorted({k for t in tensors for k in t["pairs"]}, key=["v-l", "v-vl", "l-vl"].index):
+        ps = [t["pairs"][name] for t in tensors if name in t["pairs"]]
+        total = {"tensors": len(ps), "n": sum(t["n"] for t in tensors if name in t["pairs"])}
+        total.update({k: math.fsum(p[k] for p in ps) for k in ("sq_a", "sq_b") + _PAIR_SUMS})
+        total.update({k: sum(p[k] for p in ps) for k in _PAIR_COUNTS})
+        total.update(pair_derived(total))
+        summary[name] = total
+    return {"raw": bool(raw), "trunc_rms": trunc_rms, "tensors": tensors, "summary": summary}

@@ -285,6 +285,11 @@ class ViLTransformerSS(nn.Module):
         return merge_ops.dare_merge(state_dict, self.hparams.config, drop=drop, lam=lam, seed=seed, mode=mode, rescale=rescale,
                                     device=self._merge_device())
 
+    def expert_stats(self, state_dict, raw=False, trunc_rms=None):
+        """How far apart the modality experts of `state_dict` are (no reference site; merge.expert_stats).  Merges nothing; not
+        wired to a config key and not called from __init__."""
+        return merge_ops.expert_stats(state_dict, self.hparams.config, raw=raw, trunc_rms=trunc_rms, device=self._merge_device())
+
     def regmean(self, state_dict):
         return regmean_ops.regmean(state_dict, self.hparams.config, device=self._merge_device())
 

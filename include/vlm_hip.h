@@ -278,6 +278,86 @@ int vlm_pairstats_plan_upload(const vlm_pairstats_job_t* jobs_host, int n_jobs, 
 int vlm_pairstats_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Model Breadcrumbs merge (magnitude band trim; Davari & Belilovsky 2023), csrc/band.hip.  NO REFERENCE SITE: the reference has
+ * no such merge; the arithmetic below is the specification and is pinned to a numpy restatement of it
+ * (tests/band_restatement.py), not to the reference.  One job = one output tensor with central tensor c (base), sources
+ * W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), scale lam, mode, and two ranks per source computed by the caller: k_hi[m] and
+ * k_lo[m] with 0 <= k_hi[m] < k_lo[m] <= n_elem; fp32, one rounding per operation, no FMA, source order;
+ * key(x) = bits(x) & 0x7fffffff (the TIES key):
+ *   1. t_m = W_m - c
+ *   2. thr_lo_m = the k_lo[m]-th largest key(t_m[i]) of the tensor;
+ *      thr_hi_m = the k_hi[m]-th largest key if k_hi[m] >= 1, else 0x80000000 (above every key: nothing is an outlier);
+ *      out_m[i]  = key(t_m[i]) >= thr_hi_m                      (the outliers)
+ *      kept_m[i] = key(t_m[i]) >= thr_lo_m and not out_m[i]     (the band)
+ *      tt_m[i]   = t_m[i] if kept_m[i] else +0.0
+ *      So every entry equal to the lower threshold is kept (as in TIES), every entry equal to the upper threshold is dropped, and
+ *      a source whose two thresholds are the same key contributes nothing: a defined result, not an error.
+ *   3. VLM_BAND_LINEAR: d = ((0 + tt_0) + tt_1) + ...
+ *      VLM_BAND_TIES:   steps 3-4 of the TIES rule above on these tt_m (sign elected by comparison of the sum; d = mean of
+ *                       the agreeing entries, +0.0 if none agrees)
+ *   4. dst = c + lam * d
+ * With k_hi = 0 and VLM_BAND_TIES this is the TIES rule with k = k_lo.
+ * Counters per job (uint64; integer atomics only, so nothing depends on the order workgroups run in): kept[0 .. MAX_SRC) =
+ * entries with kept_m, then outlier[0 .. MAX_SRC) = entries with out_m, then `conflict` = elements whose kept entries hold both
+ * a positive and a negative value (tt_m > 0, tt_m < 0; both modes), then `empty` = elements where no source's entry is kept
+ * (LINEAR) or none agrees (TIES).
+ * dst must not overlap base or a source of its own job (the selection passes re-read them; vlm_band_plan_upload rejects such a
+ * job as vlm_ties_plan_upload does -- overlap ACROSS jobs is the caller's to avoid).  Non-finite inputs are outside the contract.
+ */
+#define VLM_BAND_LINEAR 0
+#define VLM_BAND_TIES 1
+
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each */
+  uint64_t k_hi[VLM_MERGE_MAX_SRC];     /* step 2: the largest k_hi entries per source are outliers; 0: none */
+  uint64_t k_lo[VLM_MERGE_MAX_SRC];     /* step 2: entries below the k_lo-th largest are dropped */
+  uint64_t n_elem;
+  int32_t n_src;
+  int32_t mode;                         /* VLM_BAND_LINEAR | VLM_BAND_TIES */
+  float lam;
+  uint32_t reserved;
+} vlm_band_job_t;
+
+/* The workspace of a band plan BEGINS with this header (byte offsets from its start): vlm_ties_header_t's fields with the band
+ * types behind them.  Jobs keep their upload order; the (job, source) pairs ("units") are numbered job-major, source-minor. */
+typedef struct {
+  uint64_t n_jobs, n_units, n_chunks;
+  uint64_t jobs_off;      /* vlm_band_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table */
+  uint64_t unit0_off;     /* uint32 [n_jobs]: first unit of each job */
+  uint64_t units_off;     /* {uint32 job, uint32 source} [n_units] */
+  uint64_t state_off;     /* vlm_band_state_t [n_units] */
+  uint64_t counters_off;  /* uint64 [n_jobs][VLM_BAND_COUNTERS] */
+  uint64_t hist_off;      /* uint64 [n_units][2048]: selection histograms (pass 0: one of 2048 bins serves both ranks; passes 1
+                             and 2: 1024 bins for k_lo, then 1024 for k_hi), zero between runs */
+} vlm_band_header_t;
+typedef struct {
+  uint32_t key_lo;    /* after a run: thr_lo_m as a key (= the bits of the threshold magnitude) */
+  uint32_t key_hi;    /* after a run: thr_hi_m as a key; 0x80000000 when k_hi = 0 */
+  uint64_t rank_lo;   /* after a run: 1 + how many of the keys equal to thr_lo_m rank above the k_lo-th place */
+  uint64_t rank_hi;   /* the same for thr_hi_m and k_hi; 0 when k_hi = 0 */
+} vlm_band_state_t;
+/* per job after a run: kept[0 .. MAX_SRC), outlier[0 .. MAX_SRC), conflict, empty (see above) */
+#define VLM_BAND_COUNTERS (2 * VLM_MERGE_MAX_SRC + 2)
+
+/* Bytes of device workspace a band plan for n_jobs jobs over total_elems elements needs (jobs, chunk table, selection state,
+ * histograms, counters): what a TIES plan needs but for the wider jobs, states and counters.  No reference site. */
+size_t vlm_band_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (the checks of vlm_ties_plan_upload; a valid mode and 0 <= k_hi[m] < k_lo[m] <= n_elem, else VLM_ERR_ARG),
+ * build the chunk table on the host, copy header + jobs + tables into `workspace` (16-byte aligned) and zero the histograms.
+ * SYNCHRONISES `stream` before it returns (pageable temporary source); it is the last host synchronisation of a plan.
+ * Implements no step of the rule; no reference site. */
+int vlm_band_plan_upload(const vlm_band_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: step 2's two thresholds per source by ONE radix select (three histogram launches over all jobs, 11 + 10 +
+ * 10 key bits -- the first histogram serves both ranks, the later ones count each rank's prefix in its half of the bins -- each
+ * followed by a tiny launch that picks both bins on the device), then steps 1-4 plus the counters (one launch); seven launches,
+ * four streaming passes, no host synchronisation.  May be called again on the same workspace and gives the same bytes and
+ * counters: the run zeroes its own histograms and counters on the stream.  One run at a time per workspace.  No reference site. */
+int vlm_band_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

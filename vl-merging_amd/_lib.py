@@ -77,6 +77,36 @@ class DareJob(ctypes.Structure):
     ]
 
 
+BAND_LINEAR, BAND_TIES = 0, 1
+BAND_COUNTERS = 2 * MERGE_MAX_SRC + 2  # VLM_BAND_COUNTERS: kept per source, outlier per source, conflict, empty
+
+
+class BandJob(ctypes.Structure):
+    """vlm_band_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("k_hi", c_u64 * MERGE_MAX_SRC),
+        ("k_lo", c_u64 * MERGE_MAX_SRC),
+        ("n_elem", c_u64),
+        ("n_src", ctypes.c_int32),
+        ("mode", ctypes.c_int32),
+        ("lam", c_float),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class BandHeader(ctypes.Structure):
+    """vlm_band_header_t: the first bytes of a band plan's workspace (vlm_ties_header_t's fields)."""
+    _fields_ = list(TiesHeader._fields_)
+
+
+class BandState(ctypes.Structure):
+    """vlm_band_state_t."""
+    _fields_ = [("key_lo", ctypes.c_uint32), ("key_hi", ctypes.c_uint32), ("rank_lo", c_u64), ("rank_hi", c_u64)]
+
+
 class DareHeader(ctypes.Structure):
     """vlm_dare_header_t: the first bytes of a DARE plan's workspace."""
     _fields_ = [(n, c_u64) for n in ("n_jobs", "n_chunks", "jobs_off", "chunks_off", "counters_off")]
@@ -209,6 +239,9 @@ SIGNATURES = {
     "vlm_dare_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_dare_plan_upload": (c_int, [ctypes.POINTER(DareJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_dare_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_band_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_band_plan_upload": (c_int, [ctypes.POINTER(BandJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_band_run": (c_int, [c_void_p, c_void_p]),
     "vlm_pairstats_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_pairstats_plan_upload": (c_int, [ctypes.POINTER(PairStatsJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_pairstats_run": (c_int, [c_void_p, c_void_p]),

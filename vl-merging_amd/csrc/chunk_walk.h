@@ -14,7 +14,7 @@ typedef unsigned long long u64_t;
 
 // A run flushes at the latest after 2^19 chunks of one job.  2^19 chunks x 4096 keys < 2^32: the 32-bit LDS bins of a histogram
 // pass cannot wrap between flushes; a thread counts at most 16 per chunk: 2^23 per thread, 2^29 in the 64-lane wave sum of
-// ties_flush_counts (32-bit).
+// chunk_flush_counts (32-bit).
 #define CHUNK_FLUSH_CHUNKS (1u << 19)
 
 // f(std::integral_constant<int, n_src>): the job's source count as a compile-time constant
@@ -152,22 +152,23 @@ __device__ __forceinline__ float ties_elect(float c, const float* tt, float lam,
   return __fadd_rn(c, __fmul_rn(lam, d));                                // step 5
 }
 
-// in-workgroup reduction of the six counters, then one 64-bit atomic per counter; `red` holds (CHUNK_THREADS / 64) x
-// VLM_TIES_COUNTERS entries of LDS
-__device__ __forceinline__ void ties_flush_counts(ties_counts_t& n, u64_t* red, u64_t* counters) {
+// in-workgroup reduction of a method's N counters (TIES and DARE: six, the band merge: ten), then one 64-bit atomic per
+// counter; `red` holds (CHUNK_THREADS / 64) x N entries of LDS
+template <int N>
+__device__ __forceinline__ void chunk_flush_counts(uint32_t (&c)[N], u64_t* red, u64_t* counters) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < VLM_TIES_COUNTERS; ++k) {
-    uint32_t v = n.c[k];
+  for (int k = 0; k < N; ++k) {
+    uint32_t v = c[k];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[wave * VLM_TIES_COUNTERS + k] = v;
-    n.c[k] = 0;
+    if (lane == 0) red[wave * N + k] = v;
+    c[k] = 0;
   }
   __syncthreads();
-  if (threadIdx.x < VLM_TIES_COUNTERS) {
+  if (threadIdx.x < N) {
     u64_t t = 0;
-    for (int wv = 0; wv < CHUNK_THREADS / 64; ++wv) t += red[wv * VLM_TIES_COUNTERS + threadIdx.x];
+    for (int wv = 0; wv < CHUNK_THREADS / 64; ++wv) t += red[wv * N + threadIdx.x];
     if (t) __hip_atomic_fetch_add(&counters[threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();

@@ -20,7 +20,7 @@
 #define DARE_THREADS CHUNK_THREADS
 #define DARE_APPLY_BLOCKS_PER_CU 12   // vlm_ties_apply_kernel's rule; not A/B-measured against other values (docs/experiments.md, "DARE merge")
 
-static_assert(VLM_DARE_COUNTERS == VLM_TIES_COUNTERS, "dare.hip flushes its counters with chunk_walk.h's ties_flush_counts");
+static_assert(VLM_DARE_COUNTERS == VLM_TIES_COUNTERS, "dare.hip counts into chunk_walk.h's ties_counts_t");
 
 struct dare_view_t {
   const vlm_dare_header_t* hdr;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(DARE_THREADS) void vlm_dare_apply_kernel(unsigned c
           }
         });
       },
-      [&](uint32_t cur) { ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_DARE_COUNTERS); });
+      [&](uint32_t cur) { chunk_flush_counts(n.c, red, w.counters + (uint64_t)cur * VLM_DARE_COUNTERS); });
 }
 
 // fills every offset of `h` for n_jobs jobs and n_chunks chunks; returns the total size

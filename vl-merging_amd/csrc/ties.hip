@@ -15,31 +15,13 @@
 //   vlm_ties_apply_kernel       steps 1-5 of the rule with the thresholds read from the workspace, and the per-job counters.
 // Integer counters only, so nothing depends on the order workgroups run in.  HBM-bound: every pass streams 4 (S + 1) B per
 // element; the apply pass also writes 4 B.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
-// This file holds the rules (ties_key, ties_bin, ties_elem), the scan kernel and the workspace layout.  The streaming body of a
+// This file holds the rules (ties_bin, ties_elem), the scan kernel and the workspace layout; the key, a pass's bins and the
+// histogram flush are ties_select.h's, shared with band.hip's two-rank select.  The streaming body of a
 // chunk, a workgroup's run loop with its flush cap, the source-count dispatch, steps 3-5 and the counters are chunk_walk.h's; the
 // chunk table, the per-job checks, the host image, the upload and the grid rule are chunk_plan.h's.
 #include "vlm_common.h"
 #include "chunk_walk.h"  // the chunk walker, the run loop, steps 3-5 and the counters: shared with dare.hip (and merge.hip)
-
-#define TIES_THREADS CHUNK_THREADS  // the chunk walkers need the chunk's 256; the scan kernel uses the same block
-#define TIES_BINS 2048u           // bins per source in LDS and in global memory (pass 0 uses all, passes 1 and 2 use 1024)
-#define TIES_HIST_BLOCKS_PER_CU 4  // under 128 VGPRs: four workgroups (one wave per SIMD each) are resident per CU; 32 KiB LDS each
-#define TIES_APPLY_BLOCKS_PER_CU 12  // three resident per CU (145 VGPRs): four even rounds
-#define TIES_SCAN_BLOCKS 1024
-// The three grid sizes above follow from the kernels' resident-workgroup counts (register and LDS use recorded by the build); none of
-// them has been A/B-measured against other values (docs/experiments.md, "TIES merge").
-
-struct ties_unit_t {  // one (job, source) pair
-  uint32_t job;
-  uint32_t m;
-};
-
-template <int PASS>
-__device__ __forceinline__ constexpr uint32_t ties_bins() { return PASS == 0 ? 2048u : 1024u; }
-template <int PASS>
-__device__ __forceinline__ constexpr int ties_shift() { return PASS == 0 ? 20 : (PASS == 1 ? 10 : 0); }
-
-__device__ __forceinline__ uint32_t ties_key(float w, float c) { return __float_as_uint(__fsub_rn(w, c)) & 0x7fffffffu; }
+#include "ties_select.h"  // the constants, the unit, the key, a pass's bins and shift, the histogram flush: shared with band.hip
 
 template <int PASS>
 __device__ __forceinline__ void ties_bin(uint32_t key, uint32_t prefix, uint32_t* h) {
@@ -83,20 +65,6 @@ __device__ __forceinline__ ties_view_t ties_view(unsigned char* ws) {
   v.hist = reinterpret_cast<u64_t*>(ws + v.hdr->hist_off);
   v.counters = reinterpret_cast<u64_t*>(ws + v.hdr->counters_off);
   return v;
-}
-
-template <int PASS>
-__device__ __forceinline__ void ties_flush(uint32_t* lds, u64_t* hist, int n_src) {
-  __syncthreads();  // every LDS atomic of the run has landed
-  for (int m = 0; m < n_src; ++m)
-    for (uint32_t i = threadIdx.x; i < ties_bins<PASS>(); i += TIES_THREADS) {
-      const uint32_t cnt = lds[m * TIES_BINS + i];
-      if (cnt) {
-        __hip_atomic_fetch_add(&hist[(uint64_t)m * TIES_BINS + i], (u64_t)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        lds[m * TIES_BINS + i] = 0;
-      }
-    }
-  __syncthreads();
 }
 
 template <int PASS>
@@ -229,7 +197,7 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_ties_apply_kernel(unsigned c
           chunk_stream<S(), true, true>(j, start4, rule);
         });
       },
-      [&](uint32_t cur) { ties_flush_counts(n, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS); });
+      [&](uint32_t cur) { chunk_flush_counts(n.c, red, w.counters + (uint64_t)cur * VLM_TIES_COUNTERS); });
 }
 
 // fills every offset of `h` for n_jobs jobs, n_units (job, source) pairs and n_chunks chunks; returns the total size

@@ -1,4 +1,4 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE -- and the expert-pair statistics
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs -- and the expert-pair statistics
 (expert_stats) that say how far apart the experts are before any of them is tried.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
@@ -11,7 +11,8 @@ ties_merge (TIES-merging, Yadav et al. 2023) has NO reference site: the referenc
 takes and follows its dictionary logic; its arithmetic (include/vlm_hip.h, csrc/ties.hip) is pinned to a numpy restatement of
 the rule (tests/ties_restatement.py), not to the reference.  dare_merge (DARE, Yu et al. 2023) likewise: no reference site, the
 rule in include/vlm_hip.h, csrc/dare.hip held to tests/dare_restatement.py.  expert_stats likewise: the rule (with the order of
-its sums) in include/vlm_hip.h, csrc/pairstats.hip held to tests/pairstats_restatement.py.
+its sums) in include/vlm_hip.h, csrc/pairstats.hip held to tests/pairstats_restatement.py.  band_merge (Model Breadcrumbs,
+Davari & Belilovsky 2023) likewise: the rule in include/vlm_hip.h, csrc/band.hip held to tests/band_restatement.py.
 """
 import ctypes
 import math
@@ -164,18 +165,22 @@ class _Plan:
             L.check(getattr(L.get_lib(), self.RUN)(L.ptr(self.ws), L.stream_ptr()), self.RUN)
 
     def _read(self, header_type):
-        """The workspace header after a run (this synchronises) and, per job, the start of its report row and the counters TIES
-        and DARE share: how many entries each source kept, the elements whose kept entries disagree in sign, the elements
-        nothing contributes to."""
+        """The workspace header after a run (this synchronises) and, per job, the start of its report row and the counters TIES,
+        DARE and the band merge share: how many entries each source kept, (band merge: how many it lost as outliers,) the
+        elements whose kept entries disagree in sign, the elements nothing contributes to -- the last two are the last two
+        counters of a job."""
         if self.ws is None:
             raise L.VlmError("%s.report() needs a plan that has run" % type(self).__name__)
         hdr = header_type.from_buffer_copy(self.ws[: ctypes.sizeof(header_type)].cpu().numpy().tobytes())
         counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * self.COUNTERS * hdr.n_jobs].cpu().numpy()
         counters = counters.view("<u8").reshape(-1, self.COUNTERS)
-        rows = [({"dst": self.names[i], "n": int(job.n_elem)},
-                 {"kept": [int(counters[i, m]) for m in range(job.n_src)],
-                  "conflict": int(counters[i, L.MERGE_MAX_SRC]), "empty": int(counters[i, L.MERGE_MAX_SRC + 1])})
-                for i, job in enumerate(self.jobs)]
+        rows = []
+        for i, job in enumerate(self.jobs):
+            counts = {"kept": [int(counters[i, m]) for m in range(job.n_src)]}
+            if self.COUNTERS == L.BAND_COUNTERS:
+                counts["outlier"] = [int(counters[i, L.MERGE_MAX_SRC + m]) for m in range(job.n_src)]
+            counts.update(conflict=int(counters[i, self.COUNTERS - 2]), empty=int(counters[i, self.COUNTERS - 1]))
+            rows.append(({"dst": self.names[i], "n": int(job.n_elem)}, counts))
         return hdr, rows
 
 
@@ -434,6 +439,92 @@ def dare_merge(state_dict, config, central_weight=None, drop=0.9, lam=None, seed
     plan = DarePlan(device)
     return _task_vector_merge(
         plan, lambda dst, srcs, c: plan.add(srcs, c, drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
+        state_dict, config, central_weight, plan_out, report_out)
+
+
+def band_ranks(n, density, gamma):
+    """(k_hi, k_lo) of the band trim, in python doubles: the k_hi = min(n - 1, floor(gamma * n)) largest entries are outliers, the
+    band reaches down to the k_lo = min(n, k_hi + max(1, ceil(density * n)))-th largest.  `density` is the fraction kept, `gamma`
+    the fraction of largest entries dropped; where the two overlap, the band is whatever lies below the outliers."""
+    if not (0.0 < density <= 1.0):  # also rejects NaN
+        raise ValueError("band density must lie in (0, 1], got %r" % (density,))
+    if not (0.0 <= gamma < 1.0):
+        raise ValueError("band gamma must lie in [0, 1), got %r" % (gamma,))
+    k_hi = min(n - 1, math.floor(gamma * n))
+    return k_hi, min(n, k_hi + max(1, math.ceil(density * n)))
+
+
+_BAND_MODES = {"linear": L.BAND_LINEAR, "ties": L.BAND_TIES, L.BAND_LINEAR: L.BAND_LINEAR, L.BAND_TIES: L.BAND_TIES}
+
+
+def _band_mode(mode):
+    if isinstance(mode, bool) or mode not in _BAND_MODES:
+        raise L.VlmError("band mode must be 'linear' or 'ties', got %r" % (mode,))
+    return _BAND_MODES[mode]
+
+
+class BandPlan(_Plan):
+    """The job table of csrc/band.hip; run() enqueues the seven launches of a band merge (three histogram passes of ONE radix
+    select for both ranks of every source, a pick of both bins after each, the apply pass) without a host synchronisation."""
+
+    KIND, GPU_ONLY, JOB = "band", "the band kernels run on the GPU only", L.BandJob
+    BYTES, UPLOAD, RUN, COUNTERS = "vlm_band_plan_bytes", "vlm_band_plan_upload", "vlm_band_run", L.BAND_COUNTERS
+    PASSES = 4  # three selection passes + the apply pass, as TIES: the second rank costs no pass of its own
+
+    def add(self, srcs, base, density=None, gamma=0.0, lam=1.0, mode="linear", ranks=None, name=None):
+        """One output tensor.  `density` and `gamma` give (k_hi, k_lo) for every source (band_ranks); `ranks` = an explicit
+        (k_hi, k_lo) per source instead."""
+        mode = _band_mode(mode)
+
+        def fill(job):
+            rs = [band_ranks(int(job.n_elem), density, gamma)] * job.n_src if ranks is None else ranks
+            for k in range(job.n_src):
+                job.k_hi[k], job.k_lo[k] = int(rs[k][0]), int(rs[k][1])
+            job.mode = mode
+            job.lam = float(lam)
+        return self._add(fill, srcs, base, name=name)
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): both ranks and both thresholds per source (as floats and as keys;
+        `threshold_hi` is None where k_hi = 0, its key is 0x80000000), how many entries each source kept and lost as outliers,
+        the elements whose kept entries disagree in sign, the elements no source contributes to."""
+        hdr, rows = self._read(L.BandHeader)
+        size = ctypes.sizeof(L.BandState)
+        state = self.ws[hdr.state_off: hdr.state_off + size * hdr.n_units].cpu().numpy().view("<u4").reshape(-1, size // 4)
+        out, unit = [], 0
+        for (head, counts), job in zip(rows, self.jobs):
+            S = job.n_src
+            lo, hi = [int(state[unit + m, 0]) for m in range(S)], [int(state[unit + m, 1]) for m in range(S)]
+            out.append({**head, "k_hi": [int(job.k_hi[m]) for m in range(S)], "k_lo": [int(job.k_lo[m]) for m in range(S)],
+                        "threshold_lo": [_key_float(k) for k in lo], "threshold_lo_bits": lo,
+                        "threshold_hi": [None if job.k_hi[m] == 0 else _key_float(hi[m]) for m in range(S)],
+                        "threshold_hi_bits": hi, **counts})
+            unit += S
+        return out
+
+
+def _key_float(key):
+    return struct.unpack("<f", struct.pack("<I", key))[0]
+
+
+def band_merge(state_dict, config, central_weight=None, density=0.9, gamma=0.01, mode="linear", lam=None, device="cuda",
+               plan_out: Optional[list] = None, report_out: Optional[list] = None):
+    """Model Breadcrumbs merge (Davari & Belilovsky 2023) of the modality experts' task vectors `W_m - central` (no reference
+    site; the rule: include/vlm_hip.h): per tensor and expert the `gamma` share of largest-magnitude entries (the outliers) and
+    everything below the band of `density` under them (the noise) are dropped; what is left is summed (mode "linear") or
+    sign-elected and averaged as in TIES (mode "ties": breadcrumbs_ties).  gamma = 0 with mode "linear" is magnitude-pruned task
+    arithmetic, gamma = 0 with mode "ties" is TIES.  Same inputs, keys, pass-through and KeyError behaviour as sum_task_vectors,
+    ties_merge and dare_merge; `lam=None` takes config["sum_lambda"].  A layer with ONE source is not trimmed: it is the
+    task-vector job with ratio 1 that sum_task_vectors issues for it.  `plan_out` receives the BandPlan FIRST whenever a layer has
+    several sources, then the MergePlan of the single-source layers if there are any; `report_out` receives BandPlan.report()
+    (reading it back synchronises)."""
+    band_ranks(1, density, gamma)  # ValueError before any device work
+    mode = _band_mode(mode)
+    if lam is None:
+        lam = config["sum_lambda"]
+    plan = BandPlan(device)
+    return _task_vector_merge(
+        plan, lambda dst, srcs, c: plan.add(srcs, c, density=density, gamma=gamma, lam=lam, mode=mode, name=dst),
         state_dict, config, central_weight, plan_out, report_out)
 
 

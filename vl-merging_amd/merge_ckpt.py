@@ -1,19 +1,22 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
 sum_task_vectors / regmean on the state_dict it has just read); a merged checkpoint on disk is what one hands on, so this tool
-runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge) and DARE (merge.dare_merge; neither
-has a reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
+runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge), DARE (merge.dare_merge) and Model
+Breadcrumbs (merge.band_merge; none of the three has a reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
 `vlffn_start_layer_index`, `only_activate_used_experts`, `loss_names`, `merge_ratio`, `sum_lambda`, `central_weight`.
 
   --method interp    merge_weights      (--ratio overrides merge_ratio)
   --method taskvec   sum_task_vectors   (--lambda overrides sum_lambda; --central or central_weight=<path> is the ufo checkpoint)
   --method ties      ties_merge         (--density, --lambda, --central as above)
   --method dare      dare_merge         (--drop, --seed, --dare-mode {linear,ties}, --no-rescale, --lambda, --central as above)
+  --method breadcrumbs  band_merge      (--density = the band kept, --gamma = the share of largest entries dropped above it,
+                                         --band-mode {linear,ties}, --lambda, --central as above)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
-                     dare: n, keep_below, kept per source, conflict, empty)
+                     dare: n, keep_below, kept per source, conflict, empty;
+                     breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -28,7 +31,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs")
 
 
 def build_parser():
@@ -36,14 +39,18 @@ def build_parser():
     p.add_argument("--method", choices=METHODS, required=True)
     p.add_argument("--ckpt", required=True, help="all_moe checkpoint (a Lightning .ckpt or a bare state_dict file)")
     p.add_argument("--out", required=True, help="merged checkpoint to write")
-    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare; default: central_weight of the config")
-    p.add_argument("--density", type=float, default=0.2, help="ties: fraction of each task vector kept, in (0, 1]")
-    p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare: overrides sum_lambda")
+    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs; default: central_weight of the config")
+    p.add_argument("--density", type=float, default=0.2, help="ties / breadcrumbs: fraction of each task vector kept, in (0, 1]")
+    p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare / breadcrumbs: overrides sum_lambda")
     p.add_argument("--drop", type=float, default=0.9, help="dare: probability of dropping a task-vector entry, in [0, 1)")
     p.add_argument("--seed", type=int, default=0, help="dare: seed of the mask (64 bits)")
     p.add_argument("--dare-mode", dest="dare_mode", choices=("linear", "ties"), default="linear",
                    help="dare: sum the rescaled survivors, or elect a sign and average them as TIES does")
     p.add_argument("--no-rescale", dest="rescale", action="store_false", help="dare: do not scale the survivors by 1 / (1 - drop)")
+    p.add_argument("--gamma", type=float, default=0.01,
+                   help="breadcrumbs: fraction of each task vector's largest entries dropped as outliers, in [0, 1)")
+    p.add_argument("--band-mode", dest="band_mode", choices=("linear", "ties"), default="linear",
+                   help="breadcrumbs: sum the band, or elect a sign and average it as TIES does")
     p.add_argument("--ratio", type=float, default=None, help="interp: overrides merge_ratio")
     p.add_argument("--report", default=None, help="write a JSON report here")
     p.add_argument("config", nargs="*", help="with <named configs> key=value ... (as for run.py)")
@@ -66,12 +73,14 @@ def parse_args(argv):
         importlib.import_module("vl_merging_amd.merge").dare_keep_below(args.drop)  # the one statement of the rule; ValueError
         if not 0 <= args.seed < 2 ** 64:
             raise ValueError("DARE seed must fit 64 bits, got %r" % (args.seed,))
+    if args.method == "breadcrumbs":
+        importlib.import_module("vl_merging_amd.merge").band_ranks(1, args.density, args.gamma)  # the one statement; ValueError
     return args, cfg
 
 
-def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None):
+def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None):
     """The merged state_dict (device tensors for merged keys, the input's objects for the rest).  `dare`: the keyword arguments of
-    merge.dare_merge (drop, seed, mode, rescale)."""
+    merge.dare_merge (drop, seed, mode, rescale); `band`: those of merge.band_merge beside the density (gamma, mode)."""
     merge = importlib.import_module("vl_merging_amd.merge")
     if method == "interp":
         out = merge.merge_weights(sd, cfg)
@@ -80,6 +89,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
     elif method == "dare":
         rows = []
         out = merge.dare_merge(sd, cfg, central_weight=central, report_out=rows, **(dare or {}))
+        if report is not None:
+            report.extend(rows)
+    elif method == "breadcrumbs":
+        rows = []
+        out = merge.band_merge(sd, cfg, central_weight=central, density=density, report_out=rows, **(band or {}))
         if report is not None:
             report.extend(rows)
     else:
@@ -102,16 +116,18 @@ def main(argv):
     sd = ckpt.load_ckpt(args.ckpt)
     central = ckpt.load_file(args.central) if args.central else None
     report = [] if args.report else None
-    is_dare = args.method == "dare"
+    is_dare, is_band = args.method == "dare", args.method == "breadcrumbs"
     out = merge_state(args.method, sd, cfg, central=central, density=args.density, report=report,
-                      dare=dict(drop=args.drop, seed=args.seed, mode=args.dare_mode, rescale=args.rescale))
+                      dare=dict(drop=args.drop, seed=args.seed, mode=args.dare_mode, rescale=args.rescale),
+                      band=dict(gamma=args.gamma, mode=args.band_mode))
     torch.cuda.synchronize()
     torch.save({"state_dict": {k: v.detach().to("cpu") for k, v in out.items()}}, args.out)
     if args.report:
         with open(args.report, "w") as f:
-            json.dump({"method": args.method, "density": args.density if args.method == "ties" else None,
+            json.dump({"method": args.method, "density": args.density if args.method == "ties" or is_band else None,
                        "drop": args.drop if is_dare else None, "seed": args.seed if is_dare else None,
                        "dare_mode": args.dare_mode if is_dare else None,
+                       "gamma": args.gamma if is_band else None, "band_mode": args.band_mode if is_band else None,
                        "sum_lambda": cfg["sum_lambda"], "merge_ratio": cfg["merge_ratio"], "tensors": report}, f, indent=1)
     print("merge_ckpt: %s -> %s (%s, %d tensors)" % (args.ckpt, args.out, args.method, len(out)))
     return 0

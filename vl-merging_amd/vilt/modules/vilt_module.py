@@ -285,6 +285,12 @@ class ViLTransformerSS(nn.Module):
         return merge_ops.dare_merge(state_dict, self.hparams.config, drop=drop, lam=lam, seed=seed, mode=mode, rescale=rescale,
                                     device=self._merge_device())
 
+    def band_merge(self, state_dict, density=0.9, gamma=0.01, mode="linear", lam=None):
+        """Model Breadcrumbs merge of the experts' task vectors (no reference site; merge.band_merge).  Same contract as
+        sum_task_vectors; not wired to a config key and not called from __init__."""
+        return merge_ops.band_merge(state_dict, self.hparams.config, density=density, gamma=gamma, mode=mode, lam=lam,
+                                    device=self._merge_device())
+
     def expert_stats(self, state_dict, raw=False, trunc_rms=None):
         """How far apart the modality experts of `state_dict` are (no reference site; merge.expert_stats).  Merges nothing; not
         wired to a config key and not called from __init__."""

@@ -358,6 +358,75 @@ int vlm_band_plan_upload(const vlm_band_job_t* jobs_host, int n_jobs, void* work
 int vlm_band_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DELLA merge (magnitude-ranked drop and rescale; Deep et al. 2024, "DELLA-Merging: Reducing Interference in Model Merging
+ * through Magnitude-Based Sampling"), csrc/della.hip.  NO REFERENCE SITE: the reference has no DELLA; the arithmetic below is the
+ * specification and is pinned to a numpy restatement of it (tests/della_restatement.py), not to the reference.  One job = one
+ * output tensor with central tensor c (base), sources W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), n_elem and row_len = L with
+ * 1 <= L <= VLM_DELLA_MAX_ROW and n_elem % L == 0, the window keep_lo, keep_hi (1 <= keep_lo <= keep_hi <= 2^32), seed, stream,
+ * mode, lam (fp32) and rescale (0 | 1); fp32, one rounding per operation, no FMA, source order:
+ *   1. t_m = W_m - c
+ *   2. key(x) = bits(x) & 0x7fffffff (the TIES key).  The row of element i is i / L.  r_m[i] = the number of elements j of the
+ *      same row with key(t_m[j]) < key(t_m[i]), or with equal keys and j < i: a permutation of 0 .. L-1 in every row, rank 0 the
+ *      smallest magnitude; ties, zeros and +-x pairs are ordered by index.
+ *   3. kb_m[i] = keep_lo + floor((keep_hi - keep_lo) * r_m[i] / (L - 1)) for L > 1, in unsigned 64-bit integers (the product is
+ *      below 2^44);  for L = 1: keep_lo + ((keep_hi - keep_lo) >> 1).
+ *   4. u_m[i] = step 2 of the DARE rule above: word (i & 3) of Philox4x32-10 with counter (i >> 2, 0, m, stream) and key
+ *      (seed & 0xffffffff, seed >> 32); i is the FLAT index in the tensor, not the index in the row.
+ *   5. kept = (uint64) u_m[i] < kb_m[i];  scale = rescale ? 4294967296.0f / (float) kb_m[i] : 1.0f (the conversion rounds to
+ *      nearest even, the division is correctly rounded);  tt_m = t_m * scale if kept else +0.0
+ *   6. VLM_DELLA_LINEAR: d = ((0 + tt_0) + tt_1) + ...
+ *      VLM_DELLA_TIES:   steps 3-4 of the TIES rule above on these tt_m
+ *   7. dst = c + lam * d
+ * With keep_lo == keep_hi the ranks drop out and steps 4-7 are the DARE rule with keep_below = keep_lo and rescale = scale.
+ * Nothing in the result depends on the grid, on where a job stands in a plan or on how often the plan runs.
+ * Counters per job (uint64; integer atomics only), DARE's: kept[0 .. MAX_SRC), then `conflict`, then `empty`.
+ * dst must not overlap base or a source of its own job (vlm_della_plan_upload rejects such a job as vlm_ties_plan_upload does --
+ * overlap ACROSS jobs is the caller's to avoid).  Non-finite inputs are outside the contract.
+ */
+#define VLM_DELLA_LINEAR 0
+#define VLM_DELLA_TIES 1
+#define VLM_DELLA_MAX_ROW 4096
+
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each */
+  uint64_t keep_lo;                     /* step 3: the keep threshold of rank 0, 1 .. keep_hi */
+  uint64_t keep_hi;                     /* step 3: the keep threshold of rank L - 1, keep_lo .. 2^32 */
+  uint64_t seed;
+  uint64_t n_elem;
+  uint32_t row_len;                     /* L: 1 .. VLM_DELLA_MAX_ROW, divides n_elem */
+  int32_t n_src;
+  int32_t mode;                         /* VLM_DELLA_LINEAR | VLM_DELLA_TIES */
+  int32_t rescale;                      /* step 5: 0 | 1 */
+  float lam;
+  uint32_t stream;                      /* counter word 3: which tensor */
+} vlm_della_job_t;
+
+/* The workspace of a DELLA plan BEGINS with this header (byte offsets from its start); jobs keep their upload order. */
+typedef struct {
+  uint64_t n_jobs, n_tiles;
+  uint64_t jobs_off;      /* vlm_della_job_t [n_jobs] */
+  uint64_t tiles_off;     /* {uint32 job, uint32 first row} [n_tiles]: a tile is as many whole rows as fit in 4096 elements */
+  uint64_t counters_off;  /* uint64 [n_jobs][VLM_DELLA_COUNTERS]: kept per source, conflict, empty */
+} vlm_della_header_t;
+#define VLM_DELLA_COUNTERS (VLM_MERGE_MAX_SRC + 2)
+
+/* Bytes of device workspace a DELLA plan for n_jobs jobs over total_elems elements needs (header, jobs, tile table, counters).
+ * No reference site. */
+size_t vlm_della_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (the checks of vlm_ties_plan_upload; row_len in [1, VLM_DELLA_MAX_ROW] and fewer than 2^32 rows, else
+ * VLM_ERR_UNSUPPORTED; n_elem % row_len == 0, 1 <= keep_lo <= keep_hi <= 2^32, a valid mode and rescale in {0, 1}, else
+ * VLM_ERR_ARG), build the tile table on the host and copy header + jobs + table into `workspace` (16-byte aligned).
+ * SYNCHRONISES `stream` before it returns (pageable temporary source); it is the last host synchronisation of a plan.
+ * Implements no step of the rule; no reference site. */
+int vlm_della_plan_upload(const vlm_della_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: a tiny launch that zeroes the counters, then ONE streaming launch over all jobs (steps 1-7 and the
+ * counters; the ranks of a tile's rows are made in LDS, so the inputs are read once); no host synchronisation.  May be called
+ * again on the same workspace and gives the same bytes and counters.  One run at a time per workspace.  No reference site. */
+int vlm_della_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

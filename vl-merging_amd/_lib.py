@@ -112,6 +112,35 @@ class DareHeader(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("n_jobs", "n_chunks", "jobs_off", "chunks_off", "counters_off")]
 
 
+DELLA_LINEAR, DELLA_TIES = 0, 1
+DELLA_COUNTERS = MERGE_MAX_SRC + 2  # VLM_DELLA_COUNTERS: kept per source, conflict, empty
+DELLA_MAX_ROW = 4096                # VLM_DELLA_MAX_ROW: the longest row whose ranks one workgroup makes in LDS
+
+
+class DellaJob(ctypes.Structure):
+    """vlm_della_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("keep_lo", c_u64),
+        ("keep_hi", c_u64),
+        ("seed", c_u64),
+        ("n_elem", c_u64),
+        ("row_len", ctypes.c_uint32),
+        ("n_src", ctypes.c_int32),
+        ("mode", ctypes.c_int32),
+        ("rescale", ctypes.c_int32),
+        ("lam", c_float),
+        ("stream", ctypes.c_uint32),
+    ]
+
+
+class DellaHeader(ctypes.Structure):
+    """vlm_della_header_t: the first bytes of a DELLA plan's workspace."""
+    _fields_ = [(n, c_u64) for n in ("n_jobs", "n_tiles", "jobs_off", "tiles_off", "counters_off")]
+
+
 PAIRSTATS_PAIRS = MERGE_MAX_SRC * (MERGE_MAX_SRC - 1) // 2  # VLM_PAIRSTATS_PAIRS
 
 
@@ -242,6 +271,9 @@ SIGNATURES = {
     "vlm_band_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_band_plan_upload": (c_int, [ctypes.POINTER(BandJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_band_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_della_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_della_plan_upload": (c_int, [ctypes.POINTER(DellaJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_della_run": (c_int, [c_void_p, c_void_p]),
     "vlm_pairstats_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_pairstats_plan_upload": (c_int, [ctypes.POINTER(PairStatsJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_pairstats_run": (c_int, [c_void_p, c_void_p]),

@@ -1,4 +1,4 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs -- and the expert-pair statistics
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA -- and the expert-pair statistics
 (expert_stats) that say how far apart the experts are before any of them is tried.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
@@ -12,7 +12,8 @@ takes and follows its dictionary logic; its arithmetic (include/vlm_hip.h, csrc/
 the rule (tests/ties_restatement.py), not to the reference.  dare_merge (DARE, Yu et al. 2023) likewise: no reference site, the
 rule in include/vlm_hip.h, csrc/dare.hip held to tests/dare_restatement.py.  expert_stats likewise: the rule (with the order of
 its sums) in include/vlm_hip.h, csrc/pairstats.hip held to tests/pairstats_restatement.py.  band_merge (Model Breadcrumbs,
-Davari & Belilovsky 2023) likewise: the rule in include/vlm_hip.h, csrc/band.hip held to tests/band_restatement.py.
+Davari & Belilovsky 2023) likewise: the rule in include/vlm_hip.h, csrc/band.hip held to tests/band_restatement.py.  della_merge
+(DELLA, Deep et al. 2024) likewise: the rule in include/vlm_hip.h, csrc/della.hip held to tests/della_restatement.py.
 """
 import ctypes
 import math
@@ -166,7 +167,7 @@ class _Plan:
 
     def _read(self, header_type):
         """The workspace header after a run (this synchronises) and, per job, the start of its report row and the counters TIES,
-        DARE and the band merge share: how many entries each source kept, (band merge: how many it lost as outliers,) the
+        DARE, DELLA and the band merge share: how many entries each source kept, (band merge: how many it lost as outliers,) the
         elements whose kept entries disagree in sign, the elements nothing contributes to -- the last two are the last two
         counters of a job."""
         if self.ws is None:
@@ -319,7 +320,7 @@ class TiesPlan(_Plan):
 
 
 def _task_vector_merge(plan, add, state_dict, config, central_weight, plan_out, report_out):
-    """The driver ties_merge and dare_merge share: sum_task_vectors' dictionary logic, `add(dst, tensors, central)` for a tensor
+    """The driver ties_merge, dare_merge, band_merge and della_merge share: sum_task_vectors' dictionary logic, `add(dst, tensors, central)` for a tensor
     with several sources, the task-vector job with ratio 1 for a layer with ONE source.  `plan_out` receives `plan` first, then
     the MergePlan of the single-source layers (each only if it has jobs); `report_out` receives plan.report()."""
     single = MergePlan(plan.device)
@@ -525,6 +526,97 @@ def band_merge(state_dict, config, central_weight=None, density=0.9, gamma=0.01,
     plan = BandPlan(device)
     return _task_vector_merge(
         plan, lambda dst, srcs, c: plan.add(srcs, c, density=density, gamma=gamma, lam=lam, mode=mode, name=dst),
+        state_dict, config, central_weight, plan_out, report_out)
+
+
+def della_window(density, epsilon):
+    """(keep_lo, keep_hi) of the DELLA rule, in python doubles: inside a row the keep probability rises linearly with the rank of
+    an entry's magnitude, from density - epsilon (a draw u keeps the smallest entry iff u < keep_lo = floor((density - epsilon) *
+    2**32)) to density + epsilon (keep_hi = floor((density + epsilon) * 2**32))."""
+    if not (epsilon >= 0.0 and density - epsilon > 0.0 and density + epsilon <= 1.0):  # also rejects NaN
+        raise ValueError("DELLA needs epsilon >= 0 and 0 < density - epsilon, density + epsilon <= 1, got density %r, epsilon %r"
+                         % (density, epsilon))
+    keep_lo, keep_hi = math.floor((density - epsilon) * 2 ** 32), math.floor((density + epsilon) * 2 ** 32)
+    if keep_lo < 1:
+        raise ValueError("DELLA density %r - epsilon %r keeps nothing of the smallest entries" % (density, epsilon))
+    return keep_lo, keep_hi
+
+
+def della_row_len(tensor):
+    """The row of the DELLA rank: the last dimension of a matrix (or of anything with more dimensions), a vector as a whole."""
+    return int(tensor.shape[-1]) if tensor.dim() >= 2 else int(tensor.numel())
+
+
+_DELLA_MODES = {"linear": L.DELLA_LINEAR, "ties": L.DELLA_TIES, L.DELLA_LINEAR: L.DELLA_LINEAR, L.DELLA_TIES: L.DELLA_TIES}
+
+
+def _della_mode(mode):
+    if isinstance(mode, bool) or mode not in _DELLA_MODES:
+        raise L.VlmError("DELLA mode must be 'linear' or 'ties', got %r" % (mode,))
+    return _DELLA_MODES[mode]
+
+
+class DellaPlan(_Plan):
+    """The job table of csrc/della.hip; run() enqueues the counter reset and the one streaming launch of a DELLA merge without a
+    host synchronisation.  The ranks are made in LDS and the mask is a function of (seed, stream, source, element, rank): neither
+    is stored."""
+
+    KIND, GPU_ONLY, JOB = "DELLA", "the DELLA kernel runs on the GPU only", L.DellaJob
+    BYTES, UPLOAD, RUN, COUNTERS = "vlm_della_plan_bytes", "vlm_della_plan_upload", "vlm_della_run", L.DELLA_COUNTERS
+
+    def add(self, srcs, base, density=None, epsilon=None, lam=1.0, seed=0, stream=0, mode="linear", rescale=True, row_len=None,
+            window=None, name=None):
+        """One output tensor.  `density` and `epsilon` give the window (della_window); `window` = an explicit (keep_lo, keep_hi)
+        instead.  `row_len` defaults to della_row_len of the first source and may not exceed DELLA_MAX_ROW."""
+        mode = _della_mode(mode)
+        keep_lo, keep_hi = della_window(density, epsilon) if window is None else (int(window[0]), int(window[1]))
+        if not 1 <= keep_lo <= keep_hi <= 2 ** 32:
+            raise L.VlmError("a DELLA window needs 1 <= keep_lo <= keep_hi <= 2**32, got %r" % ((keep_lo, keep_hi),))
+        if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(stream) < 2 ** 32:
+            raise L.VlmError("DELLA seed must fit 64 bits and stream 32 bits, got %r, %r" % (seed, stream))
+        rl = della_row_len(srcs[0]) if row_len is None else int(row_len)
+        if not 1 <= rl <= L.DELLA_MAX_ROW:
+            raise L.VlmError("a DELLA row holds 1 .. %d entries, got %d" % (L.DELLA_MAX_ROW, rl))
+        if srcs[0].numel() % rl:
+            raise L.VlmError("DELLA row length %d does not divide the tensor's %d entries" % (rl, srcs[0].numel()))
+
+        def fill(job):
+            job.keep_lo, job.keep_hi = keep_lo, keep_hi
+            job.seed = int(seed)
+            job.row_len = rl
+            job.mode = mode
+            job.rescale = 1 if rescale else 0
+            job.lam = float(lam)
+            job.stream = int(stream)
+        return self._add(fill, srcs, base, name=name)
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): the window, the row length, how many entries each source kept, the
+        elements whose kept entries disagree in sign, the elements nothing contributes to."""
+        _, rows = self._read(L.DellaHeader)
+        return [{**head, "keep_lo": int(job.keep_lo), "keep_hi": int(job.keep_hi), "row_len": int(job.row_len), **counts}
+                for (head, counts), job in zip(rows, self.jobs)]
+
+
+def della_merge(state_dict, config, central_weight=None, density=0.2, epsilon=0.1, mode="linear", lam=None, seed=0, rescale=True,
+                device="cuda", plan_out: Optional[list] = None, report_out: Optional[list] = None):
+    """DELLA merge (Deep et al. 2024) of the modality experts' task vectors `W_m - central` (no reference site; the rule:
+    include/vlm_hip.h): inside every row of a tensor (a vector is one row) the entries are ranked by magnitude and dropped with a
+    probability that falls linearly with the rank -- the smallest is kept with probability density - epsilon, the largest with
+    density + epsilon --, the survivors are scaled by the reciprocal of their own keep probability, then summed (mode "linear") or
+    sign-elected and averaged as in TIES (mode "ties").  epsilon = 0 is DARE with drop = 1 - density.  The draws are DARE's: the
+    stream of a tensor is dare_stream(dst).  Same inputs, keys, pass-through and KeyError behaviour as sum_task_vectors, ties_merge
+    and dare_merge; `lam=None` takes config["sum_lambda"].  A layer with ONE source is not dropped: it is the task-vector job with
+    ratio 1 that sum_task_vectors issues for it.  `plan_out` receives the DellaPlan FIRST whenever a layer has several sources,
+    then the MergePlan of the single-source layers if there are any; `report_out` receives DellaPlan.report() (reading it back
+    synchronises)."""
+    della_window(density, epsilon)  # ValueError before any device work
+    mode = _della_mode(mode)
+    if lam is None:
+        lam = config["sum_lambda"]
+    plan = DellaPlan(device)
+    return _task_vector_merge(
+        plan, lambda dst, srcs, c: plan.add(srcs, c, density, epsilon, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
         state_dict, config, central_weight, plan_out, report_out)
 
 

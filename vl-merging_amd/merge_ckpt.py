@@ -1,11 +1,11 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
 sum_task_vectors / regmean on the state_dict it has just read); a merged checkpoint on disk is what one hands on, so this tool
-runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge), DARE (merge.dare_merge) and Model
-Breadcrumbs (merge.band_merge; none of the three has a reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
+runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge), DARE (merge.dare_merge), Model
+Breadcrumbs (merge.band_merge) and DELLA (merge.della_merge; none of the four has a reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
 `vlffn_start_layer_index`, `only_activate_used_experts`, `loss_names`, `merge_ratio`, `sum_lambda`, `central_weight`.
 
   --method interp    merge_weights      (--ratio overrides merge_ratio)
@@ -14,9 +14,12 @@ Breadcrumbs (merge.band_merge; none of the three has a reference site) outside a
   --method dare      dare_merge         (--drop, --seed, --dare-mode {linear,ties}, --no-rescale, --lambda, --central as above)
   --method breadcrumbs  band_merge      (--density = the band kept, --gamma = the share of largest entries dropped above it,
                                          --band-mode {linear,ties}, --lambda, --central as above)
+  --method della     della_merge        (--density +- --epsilon = the keep probability of a row's largest / smallest entry,
+                                         --seed, --della-mode {linear,ties}, --no-rescale, --lambda, --central as above)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
                      dare: n, keep_below, kept per source, conflict, empty;
-                     breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty)
+                     breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty;
+                     della: n, keep_lo, keep_hi, row_len, kept per source, conflict, empty)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -31,7 +34,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della")
 
 
 def build_parser():
@@ -39,18 +42,23 @@ def build_parser():
     p.add_argument("--method", choices=METHODS, required=True)
     p.add_argument("--ckpt", required=True, help="all_moe checkpoint (a Lightning .ckpt or a bare state_dict file)")
     p.add_argument("--out", required=True, help="merged checkpoint to write")
-    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs; default: central_weight of the config")
-    p.add_argument("--density", type=float, default=0.2, help="ties / breadcrumbs: fraction of each task vector kept, in (0, 1]")
-    p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare / breadcrumbs: overrides sum_lambda")
+    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs / della; default: central_weight of the config")
+    p.add_argument("--density", type=float, default=0.2, help="ties / breadcrumbs: fraction of each task vector kept, in (0, 1]; della: the mean keep probability")
+    p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare / breadcrumbs / della: overrides sum_lambda")
     p.add_argument("--drop", type=float, default=0.9, help="dare: probability of dropping a task-vector entry, in [0, 1)")
-    p.add_argument("--seed", type=int, default=0, help="dare: seed of the mask (64 bits)")
+    p.add_argument("--seed", type=int, default=0, help="dare / della: seed of the mask (64 bits)")
     p.add_argument("--dare-mode", dest="dare_mode", choices=("linear", "ties"), default="linear",
                    help="dare: sum the rescaled survivors, or elect a sign and average them as TIES does")
-    p.add_argument("--no-rescale", dest="rescale", action="store_false", help="dare: do not scale the survivors by 1 / (1 - drop)")
+    p.add_argument("--no-rescale", dest="rescale", action="store_false", help="dare / della: do not scale the survivors by the reciprocal of their keep probability")
     p.add_argument("--gamma", type=float, default=0.01,
                    help="breadcrumbs: fraction of each task vector's largest entries dropped as outliers, in [0, 1)")
     p.add_argument("--band-mode", dest="band_mode", choices=("linear", "ties"), default="linear",
                    help="breadcrumbs: sum the band, or elect a sign and average it as TIES does")
+    p.add_argument("--epsilon", type=float, default=0.1,
+                   help="della: the keep probability runs from density - epsilon (a row's smallest entry) to density + epsilon "
+                        "(its largest); needs 0 < density - epsilon and density + epsilon <= 1")
+    p.add_argument("--della-mode", dest="della_mode", choices=("linear", "ties"), default="linear",
+                   help="della: sum the rescaled survivors, or elect a sign and average them as TIES does")
     p.add_argument("--ratio", type=float, default=None, help="interp: overrides merge_ratio")
     p.add_argument("--report", default=None, help="write a JSON report here")
     p.add_argument("config", nargs="*", help="with <named configs> key=value ... (as for run.py)")
@@ -75,12 +83,17 @@ def parse_args(argv):
             raise ValueError("DARE seed must fit 64 bits, got %r" % (args.seed,))
     if args.method == "breadcrumbs":
         importlib.import_module("vl_merging_amd.merge").band_ranks(1, args.density, args.gamma)  # the one statement; ValueError
+    if args.method == "della":
+        importlib.import_module("vl_merging_amd.merge").della_window(args.density, args.epsilon)  # the one statement; ValueError
+        if not 0 <= args.seed < 2 ** 64:
+            raise ValueError("DELLA seed must fit 64 bits, got %r" % (args.seed,))
     return args, cfg
 
 
-def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None):
+def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None, della=None):
     """The merged state_dict (device tensors for merged keys, the input's objects for the rest).  `dare`: the keyword arguments of
-    merge.dare_merge (drop, seed, mode, rescale); `band`: those of merge.band_merge beside the density (gamma, mode)."""
+    merge.dare_merge (drop, seed, mode, rescale); `band`: those of merge.band_merge beside the density (gamma, mode); `della`: those of
+    merge.della_merge beside the density (epsilon, seed, mode, rescale)."""
     merge = importlib.import_module("vl_merging_amd.merge")
     if method == "interp":
         out = merge.merge_weights(sd, cfg)
@@ -89,6 +102,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
     elif method == "dare":
         rows = []
         out = merge.dare_merge(sd, cfg, central_weight=central, report_out=rows, **(dare or {}))
+        if report is not None:
+            report.extend(rows)
+    elif method == "della":
+        rows = []
+        out = merge.della_merge(sd, cfg, central_weight=central, density=density, report_out=rows, **(della or {}))
         if report is not None:
             report.extend(rows)
     elif method == "breadcrumbs":
@@ -116,18 +134,21 @@ def main(argv):
     sd = ckpt.load_ckpt(args.ckpt)
     central = ckpt.load_file(args.central) if args.central else None
     report = [] if args.report else None
-    is_dare, is_band = args.method == "dare", args.method == "breadcrumbs"
+    is_dare, is_band, is_della = args.method == "dare", args.method == "breadcrumbs", args.method == "della"
     out = merge_state(args.method, sd, cfg, central=central, density=args.density, report=report,
                       dare=dict(drop=args.drop, seed=args.seed, mode=args.dare_mode, rescale=args.rescale),
-                      band=dict(gamma=args.gamma, mode=args.band_mode))
+                      band=dict(gamma=args.gamma, mode=args.band_mode),
+                      della=dict(epsilon=args.epsilon, seed=args.seed, mode=args.della_mode, rescale=args.rescale))
     torch.cuda.synchronize()
     torch.save({"state_dict": {k: v.detach().to("cpu") for k, v in out.items()}}, args.out)
     if args.report:
         with open(args.report, "w") as f:
-            json.dump({"method": args.method, "density": args.density if args.method == "ties" or is_band else None,
-                       "drop": args.drop if is_dare else None, "seed": args.seed if is_dare else None,
+            json.dump({"method": args.method, "density": args.density if args.method == "ties" or is_band or is_della else None,
+                       "drop": args.drop if is_dare else None, "seed": args.seed if is_dare or is_della else None,
                        "dare_mode": args.dare_mode if is_dare else None,
                        "gamma": args.gamma if is_band else None, "band_mode": args.band_mode if is_band else None,
+                       "epsilon": args.epsilon if is_della else None, "della_mode": args.della_mode if is_della else None,
+                       "rescale": args.rescale if is_dare or is_della else None,
                        "sum_lambda": cfg["sum_lambda"], "merge_ratio": cfg["merge_ratio"], "tensors": report}, f, indent=1)
     print("merge_ckpt: %s -> %s (%s, %d tensors)" % (args.ckpt, args.out, args.method, len(out)))
     return 0

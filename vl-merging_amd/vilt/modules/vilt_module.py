@@ -291,6 +291,12 @@ class ViLTransformerSS(nn.Module):
         return merge_ops.band_merge(state_dict, self.hparams.config, density=density, gamma=gamma, mode=mode, lam=lam,
                                     device=self._merge_device())
 
+    def della_merge(self, state_dict, density=0.2, epsilon=0.1, mode="linear", lam=None, seed=0, rescale=True):
+        """DELLA merge of the experts' task vectors (no reference site; merge.della_merge).  Same contract as sum_task_vectors;
+        not wired to a config key and not called from __init__."""
+        return merge_ops.della_merge(state_dict, self.hparams.config, density=density, epsilon=epsilon, mode=mode, lam=lam, seed=seed,
+                                     rescale=rescale, device=self._merge_device())
+
     def expert_stats(self, state_dict, raw=False, trunc_rms=None):
         """How far apart the modality experts of `state_dict` are (no reference site; merge.expert_stats).  Merges nothing; not
         wired to a config key and not called from __init__."""

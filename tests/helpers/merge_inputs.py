@@ -1,4 +1,5 @@
-"""Inputs the GPU tests of the merge family (test_merge_gpu.py, test_ties_gpu.py, test_dare_gpu.py) share."""
+"""Inputs the GPU tests of the merge family (test_merge_gpu.py, test_ties_gpu.py, test_dare_gpu.py, test_pairstats_gpu.py,
+test_band_gpu.py, test_della_gpu.py) share."""
 import functools
 
 import numpy as np

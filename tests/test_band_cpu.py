@@ -239,13 +239,13 @@ def test_band_kernels_keep_the_occupancy_the_ties_grids_count_on(resources):  # 
     """The band kernels take the TIES grids over (csrc/ties_select.h): four histogram workgroups per CU with 32 KiB of LDS each
     -- the second rank lives in the other half of a source's bins, not in bins of its own -- and the apply pass three to a CU.
     None may spill: the kernels are HBM-bound streams."""
-    hist = {k: v for k, v in resources.items() if "vlm_band_hist_kernel" in k}
+    hist = {k: v for k, v in resources.items() if "vlm_select_hist_kernel" in k and "band_sel" in k}
     assert len(hist) == 3, sorted(hist)  # PASS 0 / 1 / 2
     for name, r in hist.items():
         assert r["Occupancy"] == 4 and r["LDS Size"] == 32768, (name, r)
     apply_band = [v for k, v in resources.items() if "vlm_band_apply_kernel" in k]
     assert len(apply_band) == 1 and apply_band[0]["Occupancy"] >= 3, apply_band
-    scan = [v for k, v in resources.items() if "vlm_band_scan_kernel" in k]
+    scan = [v for k, v in resources.items() if "vlm_select_scan_kernel" in k and "band_sel" in k]
     assert len(scan) == 3
     for r in list(hist.values()) + apply_band + scan:
         assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, r

@@ -156,22 +156,30 @@ def test_one_fold_kernel(resources):
 
 
 def test_merge_family_keeps_the_occupancy_its_grids_count_on(resources):
-    """The chunk walkers of merge.hip, ties.hip and dare.hip are one template (csrc/chunk_walk.h) around each method's rule; the
-    grids are sized from resident workgroups (one wave per SIMD each).  TIES_HIST_BLOCKS_PER_CU = 4 counts on exactly four
-    histogram workgroups per CU (registers allow four, and four times 32 KiB of LDS fit); TIES_APPLY_BLOCKS_PER_CU =
-    DARE_APPLY_BLOCKS_PER_CU = 12 is four rounds of three; vlm_merge_run's 96 per CU strides the table with at least five
-    resident.  None of them may spill: the kernels are HBM-bound streams."""
+    """The chunk walkers of merge.hip, ties.hip, dare.hip, pairstats.hip, band.hip and della.hip are one template
+    (csrc/chunk_walk.h) around each method's rule, and the radix select of ties.hip (one rank) and band.hip (two ranks) is one
+    pair of kernel templates (csrc/ties_select.h); the grids are sized from resident workgroups (one wave per SIMD each).
+    TIES_HIST_BLOCKS_PER_CU = 4 counts on exactly four histogram workgroups per CU (registers allow four, and four times 32 KiB of
+    LDS fit), with one rank and with two; TIES_APPLY_BLOCKS_PER_CU = DARE_APPLY_BLOCKS_PER_CU = 12 is four rounds of three, for
+    vlm_band_apply_kernel too; vlm_merge_run's 96 per CU strides the table with at least five resident; DELLA_BLOCKS_PER_CU = 12
+    counts on two (66 KiB of LDS each).  None of them may spill: the kernels are HBM-bound streams."""
     def only(name):
         r = [v for k, v in resources.items() if name in k]
         assert len(r) == 1, (name, sorted(k for k in resources if name in k))
         return r[0]
 
-    hist = {k: v for k, v in resources.items() if "vlm_ties_hist_kernel" in k}
-    assert len(hist) == 3, sorted(hist)  # PASS 0 / 1 / 2
-    for name, r in hist.items():
-        assert r["Occupancy"] == 4 and r["LDS Size"] == 32768, (name, r)
+    hists = []
+    for sel in ("ties_sel", "band_sel"):  # one rank, two ranks
+        hist = {k: v for k, v in resources.items() if "vlm_select_hist_kernel" in k and sel in k}
+        assert len(hist) == 3, (sel, sorted(hist))  # PASS 0 / 1 / 2
+        for name, r in hist.items():
+            assert r["Occupancy"] == 4 and r["LDS Size"] == 32768, (name, r)
+        hists += hist.values()
     apply_ties, apply_dare, plain = only("vlm_ties_apply_kernel"), only("vlm_dare_apply_kernel"), only("vlm_merge_kernel")
-    assert apply_ties["Occupancy"] >= 3 and apply_dare["Occupancy"] >= 3, (apply_ties, apply_dare)
+    apply_band, apply_della = only("vlm_band_apply_kernel"), only("vlm_della_apply_kernel")
+    assert apply_ties["Occupancy"] >= 3 and apply_dare["Occupancy"] >= 3 and apply_band["Occupancy"] >= 3, (apply_ties, apply_dare,
+                                                                                                          apply_band)
     assert plain["Occupancy"] >= 5, plain
-    for r in list(hist.values()) + [apply_ties, apply_dare, plain]:
+    assert apply_della["Occupancy"] == 2, apply_della
+    for r in hists + [apply_ties, apply_dare, apply_band, apply_della, plain]:
         assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, r

@@ -1,4 +1,4 @@
-"""The host part of csrc/chunk_plan.h, the chunk plan merge.hip, ties.hip and dare.hip share, checked without HIP and without a GPU:
+"""The host part of csrc/chunk_plan.h, the chunk plan merge.hip, ties.hip, dare.hip, pairstats.hip and band.hip share (della.hip: its checks), checked without HIP and without a GPU:
 tests/helpers/chunk_plan_check.cpp is compiled with the host compiler under AddressSanitizer + UBSan and run as a child process."""
 import os
 import shutil

@@ -1,4 +1,5 @@
-// The chunk plan of the merge family (merge.hip, ties.hip, dare.hip): every job (one output tensor) is cut into 16-KiB chunks
+// The chunk plan of the merge family (merge.hip, ties.hip, dare.hip, pairstats.hip, band.hip; della.hip takes its checks, layout
+// cursor and upload and lists tiles of rows instead): every job (one tensor) is cut into 16-KiB chunks
 // listed in a device-resident table, so that ONE grid covers all tensors of a plan.  A chunk is what one 256-thread workgroup
 // moves as 4 float4 per thread; a job's ragged end (n_elem % 4 floats) rides with exactly one of its chunks.
 // This is the family's host side, stated once: the chunk table, the checks every job passes (chunk_job_check), the host image

@@ -1,10 +1,12 @@
-// The device skeleton of the merge family (merge.hip, ties.hip, dare.hip), stated once; a method's file holds only its rule.
+// The device skeleton of the merge family (merge.hip, ties.hip, dare.hip, pairstats.hip, band.hip, della.hip), stated once; a
+// method's file holds only its rule.
 //   with_nsrc      the one dispatch over a job's source count, 1 .. VLM_MERGE_MAX_SRC
 //   chunk_stream   the streaming body of one 16-KiB chunk (chunk_plan.h): loads, the rule per element, store, ragged tail
 //   chunk_run      the contiguous run of chunks a workgroup owns, with "entering job" / "leaving job" callbacks
-// and what ties.hip and dare.hip share per element and per workgroup: steps 3-5 of the TIES rule (include/vlm_hip.h) on
-// entries tt_m that a kernel has already trimmed (TIES: by magnitude, DARE: by its Philox mask), the per-thread counters and
-// their flush (integer atomics only).  Device code only.
+// and what ties.hip, dare.hip, band.hip and della.hip share per element and per workgroup: the combine rule (LINEAR: the sum;
+// TIES: steps 3-5 of the TIES rule, include/vlm_hip.h) on entries tt_m that a kernel has already trimmed (TIES, band: by
+// magnitude; DARE, DELLA: by their Philox masks), the per-thread counters, their flush (integer atomics only) and their clear.
+// Device code only.
 #pragma once
 #include "vlm_common.h"
 #include "chunk_plan.h"
@@ -121,13 +123,24 @@ __device__ __forceinline__ void chunk_run(const chunk_t* chunks, const Job* jobs
 }
 
 struct ties_counts_t {
-  uint32_t c[VLM_TIES_COUNTERS];  // kept[0..3], conflict, empty
+  uint32_t c[VLM_TIES_COUNTERS];  // kept[0..3], conflict, empty: what TIES, DARE and DELLA count per job
 };
+#define TIES_CONFLICT VLM_MERGE_MAX_SRC
+#define TIES_EMPTY (VLM_MERGE_MAX_SRC + 1)
 
-// Steps 3-5 on tt[0 .. NSRC): elect the sign by comparison of the sum, mean of the agreeing entries, dst = c + lam * d.
-// Counts `conflict` (a positive and a negative entry among tt) and `empty` (nothing agrees).
+// How the trimmed entries tt[0 .. NSRC) of an element become its output, for every method that trims or drops (ties.hip, dare.hip,
+// band.hip, della.hip).  Both rules bump the two counters they are handed: `conflict` (a positive and a negative entry among tt)
+// and `empty` (nothing contributes).
+#define COMBINE_LINEAR 0
+#define COMBINE_TIES 1
+static_assert(VLM_DARE_LINEAR == COMBINE_LINEAR && VLM_BAND_LINEAR == COMBINE_LINEAR && VLM_DELLA_LINEAR == COMBINE_LINEAR &&
+                  VLM_DARE_TIES == COMBINE_TIES && VLM_BAND_TIES == COMBINE_TIES && VLM_DELLA_TIES == COMBINE_TIES,
+              "one MODE serves the three methods' mode fields");
+
+// Steps 3-5 of the TIES rule: elect the sign by comparison of the sum, mean of the agreeing entries, dst = c + lam * d; `empty`:
+// nothing agrees.
 template <int NSRC>
-__device__ __forceinline__ float ties_elect(float c, const float* tt, float lam, ties_counts_t& n) {
+__device__ __forceinline__ float ties_elect(float c, const float* tt, float lam, uint32_t& conflict, uint32_t& empty) {
   float s = 0.0f;
   bool has_pos = false, has_neg = false;
 #pragma unroll
@@ -147,9 +160,33 @@ __device__ __forceinline__ float ties_elect(float c, const float* tt, float lam,
     }
   }
   const float d = cnt > 0 ? __fdiv_rn(num, (float)cnt) : 0.0f;
-  n.c[VLM_MERGE_MAX_SRC] += (has_pos && has_neg) ? 1u : 0u;
-  n.c[VLM_MERGE_MAX_SRC + 1] += cnt == 0 ? 1u : 0u;
+  conflict += (has_pos && has_neg) ? 1u : 0u;
+  empty += cnt == 0 ? 1u : 0u;
   return __fadd_rn(c, __fmul_rn(lam, d));                                // step 5
+}
+
+// COMBINE_TIES: ties_elect.  COMBINE_LINEAR: d = ((0 + tt_0) + tt_1) + ..., dst = c + lam * d; `empty`: no entry was kept
+// (`any` counts the kept ones -- a kept entry may be zero).
+template <int NSRC, int MODE>
+__device__ __forceinline__ float combine(float c, const float* tt, int any, float lam, uint32_t& conflict, uint32_t& empty) {
+  if (MODE == COMBINE_TIES) return ties_elect<NSRC>(c, tt, lam, conflict, empty);
+  float d = 0.0f;
+  bool has_pos = false, has_neg = false;
+#pragma unroll
+  for (int m = 0; m < NSRC; ++m) {
+    d = __fadd_rn(d, tt[m]);
+    has_pos |= tt[m] > 0.0f;
+    has_neg |= tt[m] < 0.0f;
+  }
+  conflict += (has_pos && has_neg) ? 1u : 0u;
+  empty += any == 0 ? 1u : 0u;
+  return __fadd_rn(c, __fmul_rn(lam, d));
+}
+
+// the body of DARE's and DELLA's clear launch: the counters of every job start the run at zero
+__device__ __forceinline__ void chunk_clear_counts(u64_t* counters, uint64_t total) {
+  for (uint64_t i = (uint64_t)blockIdx.x * CHUNK_THREADS + threadIdx.x; i < total; i += (uint64_t)gridDim.x * CHUNK_THREADS)
+    counters[i] = 0;
 }
 
 // in-workgroup reduction of a method's N counters (TIES and DARE: six, the band merge: ten), then one 64-bit atomic per

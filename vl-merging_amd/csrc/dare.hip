@@ -9,13 +9,13 @@
 //   vlm_dare_apply_kernel   one launch over the plan's 16-KiB chunk table (chunk_plan.h), the shape of vlm_ties_apply_kernel:
 //                           a workgroup owns a CONTIGUOUS run of chunks, 16-B non-temporal loads and stores, steps 1-5 of the
 //                           rule, and the per-job counters flushed (64-bit integer atomics) when the run leaves a job.
-// Steps 3-5 of VLM_DARE_TIES are chunk_walk.h's, shared with ties.hip.  Integer counters only, so nothing depends on the order
-// workgroups run in.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
+// Steps 4-5 (both modes) are chunk_walk.h's combine rule, shared with ties.hip, band.hip and della.hip.  Integer counters
+// only, so nothing depends on the order workgroups run in.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
 // This file holds the rule (dare_elem, the draws) and the workspace layout; the walker, the run loop and the host checks are
 // chunk_walk.h's and chunk_plan.h's, as in ties.hip.
 #include "vlm_common.h"
 #include "philox.h"
-#include "chunk_walk.h"  // the chunk walker, the run loop, steps 3-5 and the counters: shared with ties.hip (and merge.hip)
+#include "chunk_walk.h"  // the chunk walker, the run loop, the combine rule and the counters: the whole family's
 
 #define DARE_THREADS CHUNK_THREADS
 #define DARE_APPLY_BLOCKS_PER_CU 12   // vlm_ties_apply_kernel's rule; not A/B-measured against other values (docs/experiments.md, "DARE merge")
@@ -60,18 +60,7 @@ __device__ __forceinline__ float dare_elem(float c, const float* wv, const uint3
     n.c[m] += kept ? 1u : 0u;
     any += kept ? 1 : 0;
   }
-  if (MODE == VLM_DARE_TIES) return ties_elect<NSRC>(c, tt, p.lam, n);   // steps 4-5: the TIES rule's 3-5 (chunk_walk.h)
-  float d = 0.0f;
-  bool has_pos = false, has_neg = false;
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) {                                       // step 4, LINEAR
-    d = __fadd_rn(d, tt[m]);
-    has_pos |= tt[m] > 0.0f;
-    has_neg |= tt[m] < 0.0f;
-  }
-  n.c[VLM_MERGE_MAX_SRC] += (has_pos && has_neg) ? 1u : 0u;
-  n.c[VLM_MERGE_MAX_SRC + 1] += any == 0 ? 1u : 0u;
-  return __fadd_rn(c, __fmul_rn(p.lam, d));                              // step 5
+  return combine<NSRC, MODE>(c, tt, any, p.lam, n.c[TIES_CONFLICT], n.c[TIES_EMPTY]);  // steps 4-5 (chunk_walk.h)
 }
 
 // The rule as chunk_stream's rule (chunk_walk.h).  Step 2: prep draws one Philox block per source for float4 idx4, and element c
@@ -92,16 +81,14 @@ struct dare_rule {
   __device__ __forceinline__ float elem(const draw_t& d, int c, float base, const float* wv) const {
     uint32_t uu[NSRC];
 #pragma unroll
-    for (int m = 0; m < NSRC; ++m) uu[m] = c == 0 ? d.r[m].w[0] : (c == 1 ? d.r[m].w[1] : (c == 2 ? d.r[m].w[2] : d.r[m].w[3]));
+    for (int m = 0; m < NSRC; ++m) uu[m] = philox_word(d.r[m], (uint32_t)c);
     return dare_elem<NSRC, MODE>(base, wv, uu, p, n);
   }
 };
 
 __global__ __launch_bounds__(DARE_THREADS) void vlm_dare_clear_kernel(unsigned char* __restrict__ ws) {
   const dare_view_t w = dare_view(ws);
-  const uint64_t total = w.hdr->n_jobs * VLM_DARE_COUNTERS;
-  for (uint64_t i = (uint64_t)blockIdx.x * DARE_THREADS + threadIdx.x; i < total; i += (uint64_t)gridDim.x * DARE_THREADS)
-    w.counters[i] = 0;
+  chunk_clear_counts(w.counters, w.hdr->n_jobs * VLM_DARE_COUNTERS);
 }
 
 __global__ __launch_bounds__(DARE_THREADS) void vlm_dare_apply_kernel(unsigned char* __restrict__ ws) {

@@ -19,7 +19,7 @@
 // The draws are DARE's (philox.h), per float4 of the FLAT index: a tile of a job whose row_len is no multiple of 4 may begin inside
 // a Philox block, so the scalar path draws the block of each element's own flat index.
 // Integer counters only, so nothing depends on the order workgroups run in.  -ffp-contract=off and __f*_rn: one rounding per
-// operation, no FMA.  The source-count dispatch, steps 3-4 of the TIES mode, the run loop and the counter flush are
+// operation, no FMA.  The source-count dispatch, the combine rule (steps 6-7), the run loop, the counter flush and clear are
 // chunk_walk.h's, the per-job checks, the layout cursor and the upload chunk_plan.h's.
 #include "vlm_common.h"
 #include "philox.h"
@@ -171,27 +171,6 @@ __device__ __forceinline__ void della_rank(const uint32_t (&key)[U * C], uint32_
   __syncthreads();
 }
 
-__device__ __forceinline__ uint32_t della_word(const philox4_t& r, uint32_t c) {
-  return c == 0 ? r.w[0] : (c == 1 ? r.w[1] : (c == 2 ? r.w[2] : r.w[3]));
-}
-
-// steps 6-7 and the counters for one element whose trimmed entries are tt[0 .. NSRC), `any` of them kept
-template <int NSRC, int MODE>
-__device__ __forceinline__ float della_combine(float c, const float* tt, int any, float lam, ties_counts_t& n) {
-  if (MODE == VLM_DELLA_TIES) return ties_elect<NSRC>(c, tt, lam, n);    // step 6: the TIES rule's 3-5 (chunk_walk.h)
-  float d = 0.0f;
-  bool has_pos = false, has_neg = false;
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) {                                       // step 6, LINEAR
-    d = __fadd_rn(d, tt[m]);
-    has_pos |= tt[m] > 0.0f;
-    has_neg |= tt[m] < 0.0f;
-  }
-  n.c[VLM_MERGE_MAX_SRC] += (has_pos && has_neg) ? 1u : 0u;
-  n.c[VLM_MERGE_MAX_SRC + 1] += any == 0 ? 1u : 0u;
-  return __fadd_rn(c, __fmul_rn(lam, d));                                // step 7
-}
-
 // One tile: rows [row0, row0 + rows of the tile) of job j.  VEC: row_len % 4 == 0, so the tile begins on a float4 of the tensor,
 // a float4 lies in one row and a thread owns float4 t + 256 u of the tile (u < 4); otherwise it owns element t + 256 u (u < 16).
 template <int NSRC, bool VEC>
@@ -253,7 +232,7 @@ __device__ __forceinline__ void della_tile(const vlm_della_job_t& j, uint32_t ro
             draw = dr.w[c];
           } else {
             const uint64_t i = e0 + della_li<C>(u, 0);
-            draw = della_word(dare_draw4(p.seed, p.stream, (uint32_t)m, (uint32_t)(i >> 2)), (uint32_t)i & 3u);
+            draw = philox_word(dare_draw4(p.seed, p.stream, (uint32_t)m, (uint32_t)(i >> 2)), (uint32_t)i & 3u);
           }
           const uint32_t kb1 = s.thr[della_li<C>(u, c)];
           const bool kept = draw <= kb1;                                 // step 5: (uint64) u < kb
@@ -277,8 +256,9 @@ __device__ __forceinline__ void della_tile(const vlm_della_job_t& j, uint32_t ro
 #pragma unroll
         for (int m = 0; m < NSRC; ++m) tt[m] = v[m][k];
         const int some = (int)((any >> k) & 1u);
-        o[c] = j.mode == VLM_DELLA_TIES ? della_combine<NSRC, VLM_DELLA_TIES>(b[k], tt, some, p.lam, n)
-                                        : della_combine<NSRC, VLM_DELLA_LINEAR>(b[k], tt, some, p.lam, n);
+        o[c] = j.mode == VLM_DELLA_TIES                                  // steps 6-7 (chunk_walk.h)
+                   ? combine<NSRC, COMBINE_TIES>(b[k], tt, some, p.lam, n.c[TIES_CONFLICT], n.c[TIES_EMPTY])
+                   : combine<NSRC, COMBINE_LINEAR>(b[k], tt, some, p.lam, n.c[TIES_CONFLICT], n.c[TIES_EMPTY]);
       }
       if constexpr (VEC) {
         f32x4 x;
@@ -294,9 +274,7 @@ __device__ __forceinline__ void della_tile(const vlm_della_job_t& j, uint32_t ro
 
 __global__ __launch_bounds__(DELLA_THREADS) void vlm_della_clear_kernel(unsigned char* __restrict__ ws) {
   const della_view_t w = della_view(ws);
-  const uint64_t total = w.hdr->n_jobs * VLM_DELLA_COUNTERS;
-  for (uint64_t i = (uint64_t)blockIdx.x * DELLA_THREADS + threadIdx.x; i < total; i += (uint64_t)gridDim.x * DELLA_THREADS)
-    w.counters[i] = 0;
+  chunk_clear_counts(w.counters, w.hdr->n_jobs * VLM_DELLA_COUNTERS);
 }
 
 __global__ __launch_bounds__(DELLA_THREADS, 2) void vlm_della_apply_kernel(unsigned char* __restrict__ ws) {

@@ -1,7 +1,7 @@
 // Philox4x32-10 (Salmon et al. 2011, "Parallel random numbers: as easy as 1, 2, 3"): a counter-based generator, so a draw is a
-// pure function of (counter, key) and costs no memory.  dare.hip keys it by (seed, stream, source, element): include/vlm_hip.h,
-// the DARE block, step 2.  Plain C++ integer arithmetic (a 64-bit product per multiplier gives both halves); compiles without
-// HIP as chunk_plan.h does (tests/helpers/philox_check.cpp does so).
+// pure function of (counter, key) and costs no memory.  dare.hip and della.hip key it by (seed, stream, source, element):
+// include/vlm_hip.h, the DARE block, step 2.  Plain C++ integer arithmetic (a 64-bit product per multiplier gives both halves);
+// compiles without HIP as chunk_plan.h does (tests/helpers/philox_check.cpp does so).
 #pragma once
 #include <stdint.h>
 
@@ -42,6 +42,11 @@ PHILOX_HD philox4_t philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_
   o.w[2] = c2;
   o.w[3] = c3;
   return o;
+}
+
+// word c (0 .. 3) of a block, for a c that is not a compile-time constant: selects, not an indexed (scratch) access
+PHILOX_HD uint32_t philox_word(const philox4_t& r, uint32_t c) {
+  return c == 0 ? r.w[0] : (c == 1 ? r.w[1] : (c == 2 ? r.w[2] : r.w[3]));
 }
 
 // The four draws of DARE for the float4 `i4` (= element index >> 2) of source m: word (i & 3) belongs to element i.

@@ -78,7 +78,8 @@ class _Plan:
     kernels.  A subclass gives its ctypes job type, its three entry points and how often a run streams the inputs, and writes
     an add() that hands _add() a `fill(job)` for the fields of its own."""
 
-    KIND = GPU_ONLY = JOB = BYTES = UPLOAD = RUN = COUNTERS = None
+    KIND = GPU_ONLY = JOB = BYTES = UPLOAD = RUN = HEADER = STATE = None
+    GROUPS = ("kept",)  # a job's counters: MERGE_MAX_SRC per group, in this order, then `conflict` and `empty`
     PASSES = 1  # how often a run reads every source and the base
     HAS_DST = True  # a job writes one tensor (PairStatsPlan: none)
 
@@ -165,24 +166,31 @@ class _Plan:
         with torch.cuda.device(self.device):
             L.check(getattr(L.get_lib(), self.RUN)(L.ptr(self.ws), L.stream_ptr()), self.RUN)
 
-    def _read(self, header_type):
+    def _read(self):
         """The workspace header after a run (this synchronises) and, per job, the start of its report row and the counters TIES,
-        DARE, DELLA and the band merge share: how many entries each source kept, (band merge: how many it lost as outliers,) the
-        elements whose kept entries disagree in sign, the elements nothing contributes to -- the last two are the last two
-        counters of a job."""
+        DARE, DELLA and the band merge share: per group of GROUPS one count per source (how many entries each source kept; band
+        merge: how many it lost as outliers), then the elements whose kept entries disagree in sign and the elements nothing
+        contributes to."""
         if self.ws is None:
             raise L.VlmError("%s.report() needs a plan that has run" % type(self).__name__)
-        hdr = header_type.from_buffer_copy(self.ws[: ctypes.sizeof(header_type)].cpu().numpy().tobytes())
-        counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * self.COUNTERS * hdr.n_jobs].cpu().numpy()
-        counters = counters.view("<u8").reshape(-1, self.COUNTERS)
+        hdr = self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
+        width = len(self.GROUPS) * L.MERGE_MAX_SRC + 2
+        counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * width * hdr.n_jobs].cpu().numpy().view("<u8").reshape(-1, width)
         rows = []
         for i, job in enumerate(self.jobs):
-            counts = {"kept": [int(counters[i, m]) for m in range(job.n_src)]}
-            if self.COUNTERS == L.BAND_COUNTERS:
-                counts["outlier"] = [int(counters[i, L.MERGE_MAX_SRC + m]) for m in range(job.n_src)]
-            counts.update(conflict=int(counters[i, self.COUNTERS - 2]), empty=int(counters[i, self.COUNTERS - 1]))
+            counts = {g: [int(counters[i, k * L.MERGE_MAX_SRC + m]) for m in range(job.n_src)] for k, g in enumerate(self.GROUPS)}
+            counts.update(conflict=int(counters[i, width - 2]), empty=int(counters[i, width - 1]))
             rows.append(({"dst": self.names[i], "n": int(job.n_elem)}, counts))
         return hdr, rows
+
+    def _state(self, hdr):
+        """The selection state after a run, per job: one row of STATE's 32-bit words per source (TIES, band merge)."""
+        size = ctypes.sizeof(self.STATE)
+        state = self.ws[hdr.state_off: hdr.state_off + size * hdr.n_units].cpu().numpy().view("<u4").reshape(-1, size // 4)
+        first = 0
+        for job in self.jobs:
+            yield state[first: first + job.n_src]
+            first += job.n_src
 
 
 class MergePlan(_Plan):
@@ -288,12 +296,17 @@ def ties_keep_count(density, n):
     return max(1, min(n, math.ceil(density * n)))
 
 
+def _key_float(key):
+    return struct.unpack("<f", struct.pack("<I", key))[0]
+
+
 class TiesPlan(_Plan):
     """The job table of csrc/ties.hip; run() enqueues the seven launches of a TIES merge (three histogram passes of the radix
     select, a bin pick after each, the apply pass) without a host synchronisation."""
 
     KIND, GPU_ONLY, JOB = "TIES", "the TIES kernels run on the GPU only", L.TiesJob
-    BYTES, UPLOAD, RUN, COUNTERS = "vlm_ties_plan_bytes", "vlm_ties_plan_upload", "vlm_ties_run", L.TIES_COUNTERS
+    BYTES, UPLOAD, RUN = "vlm_ties_plan_bytes", "vlm_ties_plan_upload", "vlm_ties_run"
+    HEADER, STATE = L.TiesHeader, L.TiesState
     PASSES = 4  # three selection passes + the apply pass: each streams every source and the central tensor once
 
     def add(self, srcs, base, density=None, lam=1.0, keep=None, name=None):
@@ -308,21 +321,23 @@ class TiesPlan(_Plan):
     def report(self):
         """Per job, read back after a run (this synchronises): the threshold per source as a float and as its key, how many
         entries each source kept, the elements whose kept entries disagree in sign, the elements no source contributes to."""
-        hdr, rows = self._read(L.TiesHeader)
-        state = self.ws[hdr.state_off: hdr.state_off + 16 * hdr.n_units].cpu().numpy().view("<u4").reshape(-1, 4)
-        out, unit = [], 0
-        for (head, counts), job in zip(rows, self.jobs):
-            keys = [int(state[unit + m, 0]) for m in range(job.n_src)]
+        hdr, rows = self._read()
+        out = []
+        for (head, counts), job, state in zip(rows, self.jobs, self._state(hdr)):
+            keys = [int(k) for k in state[:, 0]]
             out.append({**head, "K": [int(job.k[m]) for m in range(job.n_src)],
-                        "threshold": [struct.unpack("<f", struct.pack("<I", k))[0] for k in keys], "threshold_bits": keys, **counts})
-            unit += job.n_src
+                        "threshold": [_key_float(k) for k in keys], "threshold_bits": keys, **counts})
         return out
 
 
-def _task_vector_merge(plan, add, state_dict, config, central_weight, plan_out, report_out):
-    """The driver ties_merge, dare_merge, band_merge and della_merge share: sum_task_vectors' dictionary logic, `add(dst, tensors, central)` for a tensor
-    with several sources, the task-vector job with ratio 1 for a layer with ONE source.  `plan_out` receives `plan` first, then
-    the MergePlan of the single-source layers (each only if it has jobs); `report_out` receives plan.report()."""
+def _task_vector_merge(plan_type, add, state_dict, config, central_weight, lam, device, plan_out, report_out):
+    """The driver ties_merge, dare_merge, band_merge and della_merge share: sum_task_vectors' dictionary logic,
+    `add(plan, dst, tensors, central, lam)` into a `plan_type(device)` for a tensor with several sources (`lam=None` takes
+    config["sum_lambda"]), the task-vector job with ratio 1 for a layer with ONE source.  `plan_out` receives the plan first, then
+    the MergePlan of the single-source layers (each only if it has jobs); `report_out` receives the plan's report()."""
+    if lam is None:
+        lam = config["sum_lambda"]
+    plan = plan_type(device)
     single = MergePlan(plan.device)
     out = _passthrough(state_dict)
     central = _central(central_weight, config)
@@ -332,7 +347,7 @@ def _task_vector_merge(plan, add, state_dict, config, central_weight, plan_out, 
         elif len(mods) == 1:
             out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
         else:
-            out[dst] = add(dst, _tensors(srcs), central[dst])
+            out[dst] = add(plan, dst, _tensors(srcs), central[dst], lam)
     for p in (plan, single):
         _finish(p, plan_out)
     if report_out is not None:
@@ -349,11 +364,8 @@ def ties_merge(state_dict, config, central_weight=None, density=0.2, lam=None, d
     there are any (the order is part of the contract: callers index [0] for the TiesPlan);
     `report_out` receives TiesPlan.report() (reading it back synchronises)."""
     ties_keep_count(density, 1)  # ValueError before any device work
-    if lam is None:
-        lam = config["sum_lambda"]
-    plan = TiesPlan(device)
-    return _task_vector_merge(plan, lambda dst, srcs, c: plan.add(srcs, c, density=density, lam=lam, name=dst),
-                              state_dict, config, central_weight, plan_out, report_out)
+    return _task_vector_merge(TiesPlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density=density, lam=lam, name=dst),
+                              state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
 def dare_keep_below(drop):
@@ -373,13 +385,22 @@ def dare_rescale(drop, rescale=True):
     return struct.unpack("<f", struct.pack("<f", 1.0 / (1.0 - drop)))[0]
 
 
-_DARE_MODES = {"linear": L.DARE_LINEAR, "ties": L.DARE_TIES, L.DARE_LINEAR: L.DARE_LINEAR, L.DARE_TIES: L.DARE_TIES}
+# how the trimmed entries are combined: DARE's, the band merge's and DELLA's LINEAR / TIES are one pair of values
+assert L.DARE_LINEAR == L.BAND_LINEAR == L.DELLA_LINEAR and L.DARE_TIES == L.BAND_TIES == L.DELLA_TIES
+_MODES = {"linear": L.DARE_LINEAR, "ties": L.DARE_TIES, L.DARE_LINEAR: L.DARE_LINEAR, L.DARE_TIES: L.DARE_TIES}
 
 
-def _dare_mode(mode):
-    if isinstance(mode, bool) or mode not in _DARE_MODES:
-        raise L.VlmError("DARE mode must be 'linear' or 'ties', got %r" % (mode,))
-    return _DARE_MODES[mode]
+def _mode(kind, mode):
+    if isinstance(mode, bool) or mode not in _MODES:
+        raise L.VlmError("%s mode must be 'linear' or 'ties', got %r" % (kind, mode))
+    return _MODES[mode]
+
+
+def _seed_stream(kind, seed, stream):
+    """The Philox key and stream of a DARE or DELLA job."""
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(stream) < 2 ** 32:
+        raise L.VlmError("%s seed must fit 64 bits and stream 32 bits, got %r, %r" % (kind, seed, stream))
+    return int(seed), int(stream)
 
 
 class DarePlan(_Plan):
@@ -387,28 +408,27 @@ class DarePlan(_Plan):
     host synchronisation.  The mask is a function of (seed, stream, source, element) and is never stored."""
 
     KIND, GPU_ONLY, JOB = "DARE", "the DARE kernel runs on the GPU only", L.DareJob
-    BYTES, UPLOAD, RUN, COUNTERS = "vlm_dare_plan_bytes", "vlm_dare_plan_upload", "vlm_dare_run", L.DARE_COUNTERS
+    BYTES, UPLOAD, RUN, HEADER = "vlm_dare_plan_bytes", "vlm_dare_plan_upload", "vlm_dare_run", L.DareHeader
 
     def add(self, srcs, base, drop, lam, seed, stream, mode, rescale=True, out=None, name=None):
         """One output tensor.  `out` may be `base` or one of `srcs` (the pass is elementwise) or any tensor that meets none of them."""
-        mode = _dare_mode(mode)
+        mode = _mode(self.KIND, mode)
         keep_below = dare_keep_below(drop)
-        if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(stream) < 2 ** 32:
-            raise L.VlmError("DARE seed must fit 64 bits and stream 32 bits, got %r, %r" % (seed, stream))
+        seed, stream = _seed_stream(self.KIND, seed, stream)
 
         def fill(job):
             job.keep_below = keep_below
-            job.seed = int(seed)
+            job.seed = seed
             job.mode = mode
             job.lam = float(lam)
             job.rescale = dare_rescale(drop, rescale)
-            job.stream = int(stream)
+            job.stream = stream
         return self._add(fill, srcs, base, out, name)
 
     def report(self):
         """Per job, read back after a run (this synchronises): how many entries each source kept, the elements whose kept entries
         disagree in sign, the elements nothing contributes to."""
-        _, rows = self._read(L.DareHeader)
+        _, rows = self._read()
         return [{**head, "keep_below": int(job.keep_below), **counts} for (head, counts), job in zip(rows, self.jobs)]
 
 
@@ -434,13 +454,10 @@ def dare_merge(state_dict, config, central_weight=None, drop=0.9, lam=None, seed
     sum_task_vectors issues for it.  `plan_out` receives the DarePlan FIRST whenever a layer has several sources, then the MergePlan
     of the single-source layers if there are any; `report_out` receives DarePlan.report() (reading it back synchronises)."""
     dare_keep_below(drop)  # ValueError before any device work
-    mode = _dare_mode(mode)
-    if lam is None:
-        lam = config["sum_lambda"]
-    plan = DarePlan(device)
+    mode = _mode(DarePlan.KIND, mode)
     return _task_vector_merge(
-        plan, lambda dst, srcs, c: plan.add(srcs, c, drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
-        state_dict, config, central_weight, plan_out, report_out)
+        DarePlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
+        state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
 def band_ranks(n, density, gamma):
@@ -455,27 +472,19 @@ def band_ranks(n, density, gamma):
     return k_hi, min(n, k_hi + max(1, math.ceil(density * n)))
 
 
-_BAND_MODES = {"linear": L.BAND_LINEAR, "ties": L.BAND_TIES, L.BAND_LINEAR: L.BAND_LINEAR, L.BAND_TIES: L.BAND_TIES}
-
-
-def _band_mode(mode):
-    if isinstance(mode, bool) or mode not in _BAND_MODES:
-        raise L.VlmError("band mode must be 'linear' or 'ties', got %r" % (mode,))
-    return _BAND_MODES[mode]
-
-
 class BandPlan(_Plan):
     """The job table of csrc/band.hip; run() enqueues the seven launches of a band merge (three histogram passes of ONE radix
     select for both ranks of every source, a pick of both bins after each, the apply pass) without a host synchronisation."""
 
     KIND, GPU_ONLY, JOB = "band", "the band kernels run on the GPU only", L.BandJob
-    BYTES, UPLOAD, RUN, COUNTERS = "vlm_band_plan_bytes", "vlm_band_plan_upload", "vlm_band_run", L.BAND_COUNTERS
+    BYTES, UPLOAD, RUN = "vlm_band_plan_bytes", "vlm_band_plan_upload", "vlm_band_run"
+    HEADER, STATE, GROUPS = L.BandHeader, L.BandState, ("kept", "outlier")
     PASSES = 4  # three selection passes + the apply pass, as TIES: the second rank costs no pass of its own
 
     def add(self, srcs, base, density=None, gamma=0.0, lam=1.0, mode="linear", ranks=None, name=None):
         """One output tensor.  `density` and `gamma` give (k_hi, k_lo) for every source (band_ranks); `ranks` = an explicit
         (k_hi, k_lo) per source instead."""
-        mode = _band_mode(mode)
+        mode = _mode(self.KIND, mode)
 
         def fill(job):
             rs = [band_ranks(int(job.n_elem), density, gamma)] * job.n_src if ranks is None else ranks
@@ -489,23 +498,16 @@ class BandPlan(_Plan):
         """Per job, read back after a run (this synchronises): both ranks and both thresholds per source (as floats and as keys;
         `threshold_hi` is None where k_hi = 0, its key is 0x80000000), how many entries each source kept and lost as outliers,
         the elements whose kept entries disagree in sign, the elements no source contributes to."""
-        hdr, rows = self._read(L.BandHeader)
-        size = ctypes.sizeof(L.BandState)
-        state = self.ws[hdr.state_off: hdr.state_off + size * hdr.n_units].cpu().numpy().view("<u4").reshape(-1, size // 4)
-        out, unit = [], 0
-        for (head, counts), job in zip(rows, self.jobs):
+        hdr, rows = self._read()
+        out = []
+        for (head, counts), job, state in zip(rows, self.jobs, self._state(hdr)):
             S = job.n_src
-            lo, hi = [int(state[unit + m, 0]) for m in range(S)], [int(state[unit + m, 1]) for m in range(S)]
+            lo, hi = [int(k) for k in state[:, 0]], [int(k) for k in state[:, 1]]
             out.append({**head, "k_hi": [int(job.k_hi[m]) for m in range(S)], "k_lo": [int(job.k_lo[m]) for m in range(S)],
                         "threshold_lo": [_key_float(k) for k in lo], "threshold_lo_bits": lo,
                         "threshold_hi": [None if job.k_hi[m] == 0 else _key_float(hi[m]) for m in range(S)],
                         "threshold_hi_bits": hi, **counts})
-            unit += S
         return out
-
-
-def _key_float(key):
-    return struct.unpack("<f", struct.pack("<I", key))[0]
 
 
 def band_merge(state_dict, config, central_weight=None, density=0.9, gamma=0.01, mode="linear", lam=None, device="cuda",
@@ -520,13 +522,10 @@ def band_merge(state_dict, config, central_weight=None, density=0.9, gamma=0.01,
     several sources, then the MergePlan of the single-source layers if there are any; `report_out` receives BandPlan.report()
     (reading it back synchronises)."""
     band_ranks(1, density, gamma)  # ValueError before any device work
-    mode = _band_mode(mode)
-    if lam is None:
-        lam = config["sum_lambda"]
-    plan = BandPlan(device)
+    mode = _mode(BandPlan.KIND, mode)
     return _task_vector_merge(
-        plan, lambda dst, srcs, c: plan.add(srcs, c, density=density, gamma=gamma, lam=lam, mode=mode, name=dst),
-        state_dict, config, central_weight, plan_out, report_out)
+        BandPlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density=density, gamma=gamma, lam=lam, mode=mode, name=dst),
+        state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
 def della_window(density, epsilon):
@@ -547,33 +546,23 @@ def della_row_len(tensor):
     return int(tensor.shape[-1]) if tensor.dim() >= 2 else int(tensor.numel())
 
 
-_DELLA_MODES = {"linear": L.DELLA_LINEAR, "ties": L.DELLA_TIES, L.DELLA_LINEAR: L.DELLA_LINEAR, L.DELLA_TIES: L.DELLA_TIES}
-
-
-def _della_mode(mode):
-    if isinstance(mode, bool) or mode not in _DELLA_MODES:
-        raise L.VlmError("DELLA mode must be 'linear' or 'ties', got %r" % (mode,))
-    return _DELLA_MODES[mode]
-
-
 class DellaPlan(_Plan):
     """The job table of csrc/della.hip; run() enqueues the counter reset and the one streaming launch of a DELLA merge without a
     host synchronisation.  The ranks are made in LDS and the mask is a function of (seed, stream, source, element, rank): neither
     is stored."""
 
     KIND, GPU_ONLY, JOB = "DELLA", "the DELLA kernel runs on the GPU only", L.DellaJob
-    BYTES, UPLOAD, RUN, COUNTERS = "vlm_della_plan_bytes", "vlm_della_plan_upload", "vlm_della_run", L.DELLA_COUNTERS
+    BYTES, UPLOAD, RUN, HEADER = "vlm_della_plan_bytes", "vlm_della_plan_upload", "vlm_della_run", L.DellaHeader
 
     def add(self, srcs, base, density=None, epsilon=None, lam=1.0, seed=0, stream=0, mode="linear", rescale=True, row_len=None,
             window=None, name=None):
         """One output tensor.  `density` and `epsilon` give the window (della_window); `window` = an explicit (keep_lo, keep_hi)
         instead.  `row_len` defaults to della_row_len of the first source and may not exceed DELLA_MAX_ROW."""
-        mode = _della_mode(mode)
+        mode = _mode(self.KIND, mode)
         keep_lo, keep_hi = della_window(density, epsilon) if window is None else (int(window[0]), int(window[1]))
         if not 1 <= keep_lo <= keep_hi <= 2 ** 32:
             raise L.VlmError("a DELLA window needs 1 <= keep_lo <= keep_hi <= 2**32, got %r" % ((keep_lo, keep_hi),))
-        if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(stream) < 2 ** 32:
-            raise L.VlmError("DELLA seed must fit 64 bits and stream 32 bits, got %r, %r" % (seed, stream))
+        seed, stream = _seed_stream(self.KIND, seed, stream)
         rl = della_row_len(srcs[0]) if row_len is None else int(row_len)
         if not 1 <= rl <= L.DELLA_MAX_ROW:
             raise L.VlmError("a DELLA row holds 1 .. %d entries, got %d" % (L.DELLA_MAX_ROW, rl))
@@ -582,18 +571,18 @@ class DellaPlan(_Plan):
 
         def fill(job):
             job.keep_lo, job.keep_hi = keep_lo, keep_hi
-            job.seed = int(seed)
+            job.seed = seed
             job.row_len = rl
             job.mode = mode
             job.rescale = 1 if rescale else 0
             job.lam = float(lam)
-            job.stream = int(stream)
+            job.stream = stream
         return self._add(fill, srcs, base, name=name)
 
     def report(self):
         """Per job, read back after a run (this synchronises): the window, the row length, how many entries each source kept, the
         elements whose kept entries disagree in sign, the elements nothing contributes to."""
-        _, rows = self._read(L.DellaHeader)
+        _, rows = self._read()
         return [{**head, "keep_lo": int(job.keep_lo), "keep_hi": int(job.keep_hi), "row_len": int(job.row_len), **counts}
                 for (head, counts), job in zip(rows, self.jobs)]
 
@@ -611,13 +600,11 @@ def della_merge(state_dict, config, central_weight=None, density=0.2, epsilon=0.
     then the MergePlan of the single-source layers if there are any; `report_out` receives DellaPlan.report() (reading it back
     synchronises)."""
     della_window(density, epsilon)  # ValueError before any device work
-    mode = _della_mode(mode)
-    if lam is None:
-        lam = config["sum_lambda"]
-    plan = DellaPlan(device)
+    mode = _mode(DellaPlan.KIND, mode)
     return _task_vector_merge(
-        plan, lambda dst, srcs, c: plan.add(srcs, c, density, epsilon, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
-        state_dict, config, central_weight, plan_out, report_out)
+        DellaPlan,
+        lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density, epsilon, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
+        state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
 # ------------------------------------------------------------------------------------------------- expert-pair statistics

@@ -427,6 +427,78 @@ int vlm_della_plan_upload(const vlm_della_job_t* jobs_host, int n_jobs, void* wo
 int vlm_della_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Model Stock merge (angle-derived interpolation ratio; Jang, Yun & Han, ECCV 2024), csrc/stock.hip.  NO REFERENCE SITE: the
+ * reference has no such merge; the arithmetic below is the specification and is pinned to a numpy restatement of it
+ * (tests/stock_restatement.py), not to the reference.  One job = one output tensor with central tensor c (base, required) and
+ * sources W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC); no scalar parameter.  fp32 operations round once, no FMA; "f64" = the
+ * operand widened exactly and the operation done in double, one rounding:
+ *   1. x_m = W_m - c (fp32)
+ *   2. sq[m] = sum f64(x_m) * f64(x_m);  per pair (a, b), a < b < S, in slot b (b - 1) / 2 + a:  dot[p] = sum f64(x_a) * f64(x_b).
+ *      These are steps 2-3 of the pair-statistics rule above restricted to these two sums, in that rule's order of summation
+ *      (thread, wave by halves, ((w0 + w1) + w2) + w3, records in chunk order, every sum from +0.0): sq and dot are the bytes
+ *      vlm_pairstats_run leaves for the same inputs with a base.
+ *   3. per job, in f64, one rounding per operation:
+ *        den_p = sqrt(sq[a] * sq[b]);  cos_p = den_p > 0 ? dot[p] / den_p : +0.0
+ *        cos = (((+0.0 + cos_0) + cos_1) + ...) / NP,  NP = S (S - 1) / 2
+ *        cc = cos > 0 ? (cos < 1 ? cos : 1.0) : 0.0   (decided by these comparisons: a NaN gives 0)
+ *        t = (S * cc) / (1 + (S - 1) * cc)
+ *        S = 1 has no pair: cos = +0.0 is recorded and t = 1.0
+ *        scale = f32(t / S): f64 division, then one rounding to fp32
+ *   4. d = ((+0.0 + x_0) + x_1) + ... (fp32, source order);  dst = c + scale * d
+ * This is t * mean(W) + (1 - t) * c with the paper's t = N cos / (1 + (N - 1) cos), cos the mean pairwise cosine of the task
+ * vectors.  Clamping cos to [0, 1] keeps t in [0, 1] (the formula has a pole at cos = -1 / (N - 1)): experts that point apart
+ * get the anchor back.  Non-finite inputs are outside the contract.  dst must not overlap base or a source of its own job (two
+ * passes read them; vlm_stock_plan_upload rejects such a job as vlm_ties_plan_upload does -- overlap ACROSS jobs is the
+ * caller's to avoid).  A run leaves the same bytes whatever the grid, the job's place in a plan or the number of runs: no
+ * atomics, nothing to clear.  Step 3 runs on the device: fp64 multiply, divide and square root are correctly rounded there.
+ */
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each */
+  uint64_t n_elem;
+  int32_t n_src;
+  int32_t reserved;
+} vlm_stock_job_t;
+
+/* The workspace of a Model Stock plan BEGINS with this header (byte offsets from its start); jobs keep their upload order. */
+typedef struct {
+  uint64_t n_jobs, n_chunks;
+  uint64_t jobs_off;      /* vlm_stock_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table */
+  uint64_t first_off;     /* uint64 [n_jobs + 1]: the first chunk of each job, then n_chunks */
+  uint64_t records_off;   /* double [n_chunks][10]: one record per chunk, sq[4] then dot[6], overwritten by every run */
+  uint64_t results_off;   /* vlm_stock_result_t [n_jobs]: overwritten by every run */
+} vlm_stock_header_t;
+#define VLM_STOCK_SUMS (VLM_MERGE_MAX_SRC + VLM_PAIRSTATS_PAIRS)   /* the doubles of a record */
+
+/* per job after a run; slots of sources and pairs a job does not have are zero */
+typedef struct {
+  double sq[VLM_MERGE_MAX_SRC];         /* step 2 */
+  double dot[6];
+  double cos_pair[6];                   /* step 3: cos_p */
+  double cos;                           /* the mean, unclamped */
+  double t;
+  float scale;                          /* f32(t / S): what step 4 multiplies by */
+  uint32_t reserved;
+} vlm_stock_result_t;
+
+/* Bytes of device workspace a Model Stock plan for n_jobs jobs over total_elems elements needs (header, jobs, chunk table,
+ * first-chunk table, one record per chunk, one result per job).  No reference site. */
+size_t vlm_stock_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (the checks of vlm_ties_plan_upload: pointers non-NULL and 16-byte aligned, base required, 1 <= n_src <=
+ * VLM_MERGE_MAX_SRC and n_elem > 0, dst's byte range meets no input's, else VLM_ERR_ARG; a length or chunk count past 32 bits of
+ * float4s is VLM_ERR_UNSUPPORTED), build the chunk table on the host and copy header + jobs + tables into `workspace` (16-byte
+ * aligned; VLM_ERR_WORKSPACE if it is too small).  SYNCHRONISES `stream` before it returns (pageable temporary source); it is
+ * the last host synchronisation of a plan.  Implements no step of the rule; no reference site. */
+int vlm_stock_plan_upload(const vlm_stock_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: three launches, stream-ordered, and nothing else -- the reducer over all jobs (steps 1-2, one record per
+ * chunk), the fold (a job's records in chunk order, then step 3: the whole result), the apply pass (steps 1 and 4, `scale`
+ * read from the job's result); no host synchronisation.  May be called again on the same workspace and gives the same bytes.
+ * One run at a time per workspace.  No reference site. */
+int vlm_stock_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

@@ -176,6 +176,33 @@ class PairStatsResult(ctypes.Structure):
                 + [(n, c_u64 * PAIRSTATS_PAIRS) for n in ("live", "conflict", "tlive", "tconflict")])
 
 
+STOCK_SUMS = MERGE_MAX_SRC + PAIRSTATS_PAIRS  # VLM_STOCK_SUMS: the doubles of a chunk's record, sq[4] then dot[6]
+
+
+class StockJob(ctypes.Structure):
+    """vlm_stock_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("n_elem", c_u64),
+        ("n_src", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class StockHeader(ctypes.Structure):
+    """vlm_stock_header_t: the first bytes of a Model Stock plan's workspace (vlm_pairstats_header_t's fields)."""
+    _fields_ = list(PairStatsHeader._fields_)
+
+
+class StockResult(ctypes.Structure):
+    """vlm_stock_result_t: the sums, the cosines, the ratio and the scale of one job."""
+    _fields_ = [("sq", ctypes.c_double * MERGE_MAX_SRC), ("dot", ctypes.c_double * PAIRSTATS_PAIRS),
+                ("cos_pair", ctypes.c_double * PAIRSTATS_PAIRS), ("cos", ctypes.c_double), ("t", ctypes.c_double),
+                ("scale", c_float), ("reserved", ctypes.c_uint32)]
+
+
 class ScatterSrc(ctypes.Structure):
     """vlm_scatter_src_t of include/vlm_hip.h."""
     _fields_ = [("g", c_void_p), ("g_is_f32", ctypes.c_int32), ("ld", ctypes.c_int32), ("first_row", ctypes.c_int32),
@@ -277,6 +304,9 @@ SIGNATURES = {
     "vlm_pairstats_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_pairstats_plan_upload": (c_int, [ctypes.POINTER(PairStatsJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_pairstats_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_stock_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_stock_plan_upload": (c_int, [ctypes.POINTER(StockJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_stock_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_bf16_grouped": (c_int, [c_int, ctypes.POINTER(GemmGroup), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

@@ -1,4 +1,4 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA -- and the expert-pair statistics
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock -- and the expert-pair statistics
 (expert_stats) that say how far apart the experts are before any of them is tried.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
@@ -14,6 +14,16 @@ rule in include/vlm_hip.h, csrc/dare.hip held to tests/dare_restatement.py.  exp
 its sums) in include/vlm_hip.h, csrc/pairstats.hip held to tests/pairstats_restatement.py.  band_merge (Model Breadcrumbs,
 Davari & Belilovsky 2023) likewise: the rule in include/vlm_hip.h, csrc/band.hip held to tests/band_restatement.py.  della_merge
 (DELLA, Deep et al. 2024) likewise: the rule in include/vlm_hip.h, csrc/della.hip held to tests/della_restatement.py.
+
+stock_merge (Model Stock, Jang, Yun & Han 2024) likewise: no reference site, csrc/stock.hip held to tests/stock_restatement.py.
+Its rule (include/vlm_hip.h), per tensor with central tensor c and sources W_0 .. W_{S-1}; fp32 rounds once, no FMA; f64 = the
+operand widened exactly, the operation in double:
+  1. x_m = W_m - c (fp32)
+  2. sq[m] = sum f64(x_m) f64(x_m);  dot[(a, b)] = sum f64(x_a) f64(x_b) -- the pair statistics' sums, in their order
+  3. in f64, on the device: cos_p = dot_p / sqrt(sq_a sq_b) (+0.0 where that root is not > 0);  cos = their mean;
+     cc = cos clamped to [0, 1] by comparison;  t = S cc / (1 + (S - 1) cc) (S = 1: t = 1);  scale = float32(t / S)
+  4. d = ((0 + x_0) + x_1) + ... (fp32);  dst = c + scale * d
+It has no hyper-parameter; the apply pass reads a scalar the reduction over the same tensor made, ordered by the stream alone.
 """
 import ctypes
 import math
@@ -607,8 +617,58 @@ def della_merge(state_dict, config, central_weight=None, density=0.2, epsilon=0.
         state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
+class StockPlan(_Plan):
+    """The job table of csrc/stock.hip; run() enqueues the three launches of a Model Stock merge (the reducer of the task
+    vectors' squared norms and dot products, the fold that ends in the ratio of step 3, the apply pass that reads it) without a
+    host synchronisation.  Step 3 runs on the device, in correctly rounded f64; there are no counters."""
+
+    KIND, GPU_ONLY, JOB = "Model Stock", "the Model Stock kernels run on the GPU only", L.StockJob
+    BYTES, UPLOAD, RUN, HEADER = "vlm_stock_plan_bytes", "vlm_stock_plan_upload", "vlm_stock_run", L.StockHeader
+    PASSES = 2  # the reducer and the apply pass: each streams every source and the central tensor once
+
+    def add(self, srcs, base, name=None):
+        """One output tensor; the method has no parameter."""
+        return self._add(lambda job: None, srcs, base, name=name)
+
+    def results(self):
+        """The raw vlm_stock_result_t of every job as the device left it (this synchronises)."""
+        if self.ws is None:
+            raise L.VlmError("StockPlan.report() needs a plan that has run")
+        hdr = self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
+        size = ctypes.sizeof(L.StockResult)
+        raw = self.ws[hdr.results_off: hdr.results_off + size * hdr.n_jobs].cpu().numpy().tobytes()
+        return [L.StockResult.from_buffer_copy(raw[i * size: (i + 1) * size]) for i in range(len(self.jobs))]
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): `sq` per source; per pair (a, b), a < b, in the order of their
+        slots, `dot` and `cosine`; the mean cosine `cos` (unclamped), the ratio `t`, and `scale` = float32(t / S) as a float and
+        as its bits -- all as the device made them."""
+        rows = []
+        for name, job, r in zip(self.names, self.jobs, self.results()):
+            S = job.n_src
+            pairs = [{"a": a, "b": b, "dot": r.dot[L.pair_slot(a, b)], "cosine": r.cos_pair[L.pair_slot(a, b)]}
+                     for b in range(1, S) for a in range(b)]
+            rows.append({"dst": name, "n": int(job.n_elem), "sq": [r.sq[m] for m in range(S)], "pairs": pairs, "cos": r.cos,
+                         "t": r.t, "scale": float(r.scale), "scale_bits": float32_bits(r.scale)})
+        return rows
+
+
+def stock_merge(state_dict, config, central_weight=None, device="cuda", plan_out: Optional[list] = None,
+                report_out: Optional[list] = None):
+    """Model Stock merge (Jang, Yun & Han 2024) of the modality experts (no reference site; the rule: include/vlm_hip.h): per
+    tensor, dst = t * mean(W_m) + (1 - t) * central with t = S cos / (1 + (S - 1) cos), cos the mean pairwise cosine between the
+    task vectors `W_m - central`, clamped to [0, 1] -- experts that agree keep their average, experts that point apart get the
+    central tensor back.  The method has no hyper-parameter: config["sum_lambda"] is NOT read.  Same inputs, keys, pass-through
+    and KeyError behaviour as sum_task_vectors and ties_merge.  A layer with ONE source is the task-vector job with ratio 1 that
+    sum_task_vectors issues for it (t = 1).  `plan_out` receives the StockPlan FIRST whenever a layer has several sources, then
+    the MergePlan of the single-source layers if there are any; `report_out` receives StockPlan.report() (reading it back
+    synchronises)."""
+    return _task_vector_merge(StockPlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, name=dst),
+                              state_dict, config, central_weight, 1.0, device, plan_out, report_out)
+
+
 # ------------------------------------------------------------------------------------------------- expert-pair statistics
-_PAIR_SUMS = ("dot", "dist2", "ssd_sum", "tssd_sum")          # doubles
+_PAIR_SUMS =("dot", "dist2", "ssd_sum", "tssd_sum")          # doubles
 _PAIR_COUNTS = ("live", "conflict", "tlive", "tconflict")     # integers
 
 

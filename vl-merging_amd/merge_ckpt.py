@@ -1,11 +1,12 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
 sum_task_vectors / regmean on the state_dict it has just read); a merged checkpoint on disk is what one hands on, so this tool
 runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge), DARE (merge.dare_merge), Model
-Breadcrumbs (merge.band_merge) and DELLA (merge.della_merge; none of the four has a reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
+Breadcrumbs (merge.band_merge), DELLA (merge.della_merge) and Model Stock (merge.stock_merge; none of the five has a reference
+site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
 `vlffn_start_layer_index`, `only_activate_used_experts`, `loss_names`, `merge_ratio`, `sum_lambda`, `central_weight`.
 
   --method interp    merge_weights      (--ratio overrides merge_ratio)
@@ -16,10 +17,13 @@ Breadcrumbs (merge.band_merge) and DELLA (merge.della_merge; none of the four ha
                                          --band-mode {linear,ties}, --lambda, --central as above)
   --method della     della_merge        (--density +- --epsilon = the keep probability of a row's largest / smallest entry,
                                          --seed, --della-mode {linear,ties}, --no-rescale, --lambda, --central as above)
+  --method stock     stock_merge        (--central as above; the method has no hyper-parameter: --lambda, --density and the rest are
+                                         ignored, as they are for interp)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
                      dare: n, keep_below, kept per source, conflict, empty;
                      breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty;
-                     della: n, keep_lo, keep_hi, row_len, kept per source, conflict, empty)
+                     della: n, keep_lo, keep_hi, row_len, kept per source, conflict, empty;
+                     stock: n, sq per source, dot and cosine per pair, the mean cosine, t, scale and its bits)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -34,7 +38,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock")
 
 
 def build_parser():
@@ -42,7 +46,7 @@ def build_parser():
     p.add_argument("--method", choices=METHODS, required=True)
     p.add_argument("--ckpt", required=True, help="all_moe checkpoint (a Lightning .ckpt or a bare state_dict file)")
     p.add_argument("--out", required=True, help="merged checkpoint to write")
-    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs / della; default: central_weight of the config")
+    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs / della / stock; default: central_weight of the config")
     p.add_argument("--density", type=float, default=0.2, help="ties / breadcrumbs: fraction of each task vector kept, in (0, 1]; della: the mean keep probability")
     p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare / breadcrumbs / della: overrides sum_lambda")
     p.add_argument("--drop", type=float, default=0.9, help="dare: probability of dropping a task-vector entry, in [0, 1)")
@@ -107,6 +111,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
     elif method == "della":
         rows = []
         out = merge.della_merge(sd, cfg, central_weight=central, density=density, report_out=rows, **(della or {}))
+        if report is not None:
+            report.extend(rows)
+    elif method == "stock":
+        rows = []
+        out = merge.stock_merge(sd, cfg, central_weight=central, report_out=rows)
         if report is not None:
             report.extend(rows)
     elif method == "breadcrumbs":

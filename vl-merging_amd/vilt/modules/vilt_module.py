@@ -297,6 +297,11 @@ class ViLTransformerSS(nn.Module):
         return merge_ops.della_merge(state_dict, self.hparams.config, density=density, epsilon=epsilon, mode=mode, lam=lam, seed=seed,
                                      rescale=rescale, device=self._merge_device())
 
+    def stock_merge(self, state_dict):
+        """Model Stock merge of the experts (no reference site; merge.stock_merge): no hyper-parameter.  Same contract as
+        sum_task_vectors; not wired to a config key and not called from __init__."""
+        return merge_ops.stock_merge(state_dict, self.hparams.config, device=self._merge_device())
+
     def expert_stats(self, state_dict, raw=False, trunc_rms=None):
         """How far apart the modality experts of `state_dict` are (no reference site; merge.expert_stats).  Merges nothing; not
         wired to a config key and not called from __init__."""

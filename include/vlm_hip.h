@@ -576,7 +576,7 @@ int vlm_gemm_bf16_grouped(int n_groups, const vlm_gemm_group_t* groups, int N, i
  * A = dY [tokens][lda] and B = X [tokens][ldb] (both bf16, token-major: ta = tb = 1 of vlm_gemm_bf16),
  *   C_g[M,N] (+)= A[rows_g]^T . B[rows_g]      (f32, ldc; accumulate per group)
  * in one launch of the 256x256 wgrad kernel plus one reduce launch: the K slices of all groups share one round of
- * workgroups, each group's share following its token count.  splitk_ws as in vlm_epilogue_t (without it, or for shapes the
+ * workgroups, each group's share following its token count (the plan of vlm_gemm_wgrad_batch below, over row ranges).  splitk_ws as in vlm_epilogue_t (without it, or for shapes the
  * kernel does not serve: one vlm_gemm_bf16 call per group on the same stream; an empty group leaves C_g unchanged when
  * accumulating and zeroes it otherwise). */
 typedef struct {
@@ -587,6 +587,28 @@ typedef struct {
 } vlm_wgrad_group_t;
 int vlm_gemm_wgrad_grouped(int n_groups, const vlm_wgrad_group_t* groups, int M, int N, const void* A, int lda,
                            const void* B, int ldb, int ldc, float* splitk_ws, uint64_t splitk_ws_bytes, void* stream);
+/* Batched weight gradients: n <= VLM_GEMM_MAX_GROUPS problems that reduce over the SAME T token rows, each with its own
+ * operands and its own shape (the fc2, fc1, proj and qkv weight gradients of one transformer block evaluation),
+ *   dW_i[M_i,N_i] (+)= dy_i[T,M_i]^T . x_i[T,N_i]      (dy, x bf16 token-major; dW f32, ldc; accumulate per problem)
+ * in ONE launch of the 256x256 wgrad kernel plus ONE reduce launch.  The reduction of every problem is cut into the fewest K
+ * slices whose (slice, tile) workgroups still fit one round of vlm_device_cus() compute units (at least 16 32-row steps per
+ * slice): four base-width problems are 108 tiles x 2 slices, where four vlm_gemm_bf16 calls store 999 tiles of partial sums.
+ * Slices are fp32 tiles in splitk_ws (as in vlm_epilogue_t, required here) and are added in slice order: no atomics, results
+ * do not depend on scheduling.  Made for a second stream, where a launch that leaves compute units free wastes nothing.
+ * Returns 0 after the two launches, a negative VLM_ERR_* for bad arguments, and 1 -- "not offered", NOTHING launched, the
+ * caller makes one vlm_gemm_bf16(ta = tb = 1) call per problem -- unless for every problem N % 256 == 0, ldc % 4 == 0, dy, x
+ * and dW are 16-byte aligned, ld_dy and ld_x are multiples of 8, M N 4 < 2^31 and T ld 2 < 2^31, and all tiles together are
+ * at most vlm_device_cus() and all slices fit splitk_ws_bytes. */
+typedef struct {
+  const void* dy;       /* bf16 [T][ld_dy], columns 0 .. M-1 */
+  int32_t ld_dy, M;
+  const void* x;        /* bf16 [T][ld_x], columns 0 .. N-1 */
+  int32_t ld_x, N;
+  float* dW;            /* f32 [M][ldc] */
+  int32_t ldc, accumulate;
+} vlm_wgrad_problem_t;
+int vlm_gemm_wgrad_batch(int n, const vlm_wgrad_problem_t* problems, int T, float* splitk_ws, uint64_t splitk_ws_bytes,
+                         void* stream);
 /* Which kernel serves ta = tb = 0 calls: 0 the 128x128 tile always, 1 by shape (default), 2 the 256x256 tile whenever the
  * call is legal for it, -1 back to the default; mode 0 also keeps wgrad (ta = tb = 1) off the 256x256 kernel.  Tests and
  * benchmarks only. */

@@ -231,6 +231,11 @@ class WgradGroup(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class WgradProblem(ctypes.Structure):  # vlm_wgrad_problem_t
+    _fields_ = [("dy", c_void_p), ("ld_dy", ctypes.c_int32), ("M", ctypes.c_int32), ("x", c_void_p), ("ld_x", ctypes.c_int32),
+                ("N", ctypes.c_int32), ("dW", c_void_p), ("ldc", ctypes.c_int32), ("accumulate", ctypes.c_int32)]
+
+
 class FoldJob(ctypes.Structure):
     _fields_ = [("partials", c_void_p), ("nblocks", ctypes.c_int32), ("D", ctypes.c_int32), ("out0", c_void_p),
                 ("out1", c_void_p)]
@@ -313,6 +318,7 @@ SIGNATURES = {
                                       ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_wgrad_grouped": (c_int, [c_int, ctypes.POINTER(WgradGroup), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                        c_void_p, c_u64, c_void_p]),
+    "vlm_gemm_wgrad_batch": (c_int, [c_int, ctypes.POINTER(WgradProblem), c_int, c_void_p, c_u64, c_void_p]),
     "vlm_attention_fwd": (c_int, [ctypes.POINTER(AttnDesc), c_void_p, c_int, c_void_p, c_void_p]),
     "vlm_attention_bwd_ws_floats": (c_size_t, [ctypes.POINTER(AttnDesc), c_int]),
     "vlm_attention_bwd": (c_int, [ctypes.POINTER(AttnDesc), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,

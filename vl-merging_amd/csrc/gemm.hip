@@ -20,6 +20,7 @@
 // up with 4 CONSECUTIVE output columns of one row: the epilogue then moves 16-B (fp32) / 8-B (bf16) vectors.
 #include "vlm_common.h"
 #include "vlm_diag.h"
+#include "wgrad_plan.h"
 #include <atomic>
 
 #define GEMM_BM 128
@@ -156,10 +157,15 @@ struct gemm_group_t {
   int ldb, row0, row_end, tile0;
 };
 
-// wgrad form (vlm_gemm_wgrad_grouped): a group is a range of TOKEN rows (the reduction) with its own K slices and its own
-// block of the slice workspace; item0 = first (slice, tile) item of the group in the launch's grid.
+// wgrad form (vlm_gemm_wgrad_batch, vlm_gemm_wgrad_grouped): a group is a whole problem -- its own operands, output shape and
+// tile grid, a range of TOKEN rows (the reduction) with its own K slices, and its own block of the slice workspace (ws_base
+// floats in; slice s at ws_base + s * M * N); item0 = first (slice, tile) item of the group in the launch's grid.
 struct gemmT_group_t {
-  int row0, row_end, item0, kps, slice0;
+  const void* A;
+  const void* B;
+  int lda, ldb, M, N, tiles_n, ntile;
+  int row0, row_end, item0, kps;
+  uint32_t ws_base;
 };
 
 struct gemm_params_t {
@@ -1116,8 +1122,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_big_kernel(const gem
 // output tiles on 256 CUs); a slice does not add into C with atomics (1 024 256-B float atomics per workgroup would cost
 // as much as 80 K steps, MI355X_MICROARCH.md "Global float atomics") but stores its fp32 tile into the caller's
 // workspace [slice][M][N] through the looped epilogue, and splitk_reduce_kernel adds the slices into C.
-// GROUPED (vlm_gemm_wgrad_grouped): the token rows of several experts reduce into several weight gradients in one launch;
-// a workgroup's item belongs to one group, whose row range bounds its K slice (rows past the range read zeros).
+// Plain launches are planned as exactly one round of workgroups (launch_gemm_bigT).
+// GROUPED (vlm_gemm_wgrad_batch: the four weight gradients of a block evaluation; vlm_gemm_wgrad_grouped: the token rows of
+// several experts): up to VLM_GEMM_MAX_GROUPS problems in one launch, planned by csrc/wgrad_plan.h.  A workgroup's item belongs
+// to one group, found by scalar compares; the group supplies the operands, the leading dimensions, the output shape, the tile
+// grid, the row range that bounds its K slices (rows past the range read zeros) and its block of the workspace -- all scalars
+// read before the K loop, which is the plain instantiation's.
 template <bool GROUPED = false>
 __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_bigT_kernel(const gemm_params_t p) {
   __shared__ __attribute__((aligned(1024))) unsigned char sA0[BIG_OP_BYTES], sA1[BIG_OP_BYTES], sB0[BIG_OP_BYTES], sB1[BIG_OP_BYTES];
@@ -1130,11 +1140,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_bigT_kernel(const ge
   // fastest -- its ~32 resident workgroups are then (nearly) all tiles of ONE K slice, so every byte of that slice of A
   // and B enters the XCD's L2 once instead of once per tile row / column (PMC: 726 MB fetched for 417 MB of operands with
   // slice = block / tiles).
-  const uint32_t ntile = p.tiles_m * p.tiles_n;
+  uint32_t ntile = p.tiles_m * p.tiles_n, tiles_n = (uint32_t)p.tiles_n;
   const uint32_t q8 = gridDim.x >> 3, r8 = gridDim.x & 7, xcd = blockIdx.x & 7;
   uint32_t item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  uint32_t k_base = 0, k_end = (uint32_t)p.K, slice0 = 0;
+  uint32_t k_base = 0, k_end = (uint32_t)p.K, ws_base = 0;
   int nk = p.ksteps_per_split;  // even, >= 4: launcher
+  const void *A = p.A, *B = p.B;
+  uint32_t lda = (uint32_t)p.lda, ldb = (uint32_t)p.ldb;
+  int M = p.M, N = p.N;
   if constexpr (GROUPED) {
     int g = 0;
 #pragma unroll
@@ -1145,16 +1158,20 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_bigT_kernel(const ge
     k_base = (uint32_t)G.row0;
     k_end = (uint32_t)G.row_end;
     nk = G.kps;
-    slice0 = (uint32_t)G.slice0;
+    ws_base = G.ws_base;
+    A = G.A; B = G.B;
+    lda = (uint32_t)G.lda; ldb = (uint32_t)G.ldb;
+    M = G.M; N = G.N;
+    ntile = (uint32_t)G.ntile; tiles_n = (uint32_t)G.tiles_n;
   }
   const uint32_t split = item / ntile, tile = item - split * ntile;
-  const uint32_t tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
+  const uint32_t tm = tile / tiles_n, tn = tile - tm * tiles_n;
   const uint32_t m0 = tm * BIG_BM, n0 = tn * BIG_BN;
   const uint32_t k_first = k_base + split * (uint32_t)nk * BIG_BK;
   const __amdgpu_buffer_rsrc_t ra =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, (int)((uint64_t)k_end * p.lda * 2), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(A), 0, (int)((uint64_t)k_end * lda * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rb =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.B), 0, (int)((uint64_t)k_end * p.ldb * 2), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(B), 0, (int)((uint64_t)k_end * ldb * 2), 0x00020000);
 
   // staging: wave instruction j = wave + 4u covers k-rows 2j, 2j+1; lane -> k-row 2j + (lane>>5), 16-B chunk lane&31.
   // Rows k >= K fall off the descriptor (zeros); x >= M or N reads the next row's head: those accumulators are dropped.
@@ -1162,8 +1179,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_bigT_kernel(const ge
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const uint32_t row = 2 * (wave + 4 * u) + (lane >> 5), c16 = lane & 31;
-    offa[u] = ((k_first + row) * (uint32_t)p.lda + m0 + c16 * 8) * 2;
-    offb[u] = ((k_first + row) * (uint32_t)p.ldb + n0 + c16 * 8) * 2;
+    offa[u] = ((k_first + row) * lda + m0 + c16 * 8) * 2;
+    offb[u] = ((k_first + row) * ldb + n0 + c16 * 8) * 2;
     wr_off[u] = row * 512 + (((c16 >> 1) ^ ((row & 3) | (((row >> 3) & 1) << 2))) << 5) + (c16 & 1) * 16;
   }
   // fragments: 16-wide x block i of this wave's 128, lane -> k-rows 8g + q (+4), g = lane>>4, q = (lane&15)>>2
@@ -1186,7 +1203,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_bigT_kernel(const ge
       acc10[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
       acc11[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-  const uint32_t stepa = BIG_BK * (uint32_t)p.lda * 2, stepb = BIG_BK * (uint32_t)p.ldb * 2;
+  const uint32_t stepa = BIG_BK * lda * 2, stepb = BIG_BK * ldb * 2;
   bf16x8 fa0[8], fb0[8], fa1[8], fb1[8];
   u32x4 ra0[4], rb0[4], ra1[4], rb1[4];
 #define BIGT_TR(PTR) __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(PTR))
@@ -1251,8 +1268,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_bigT_kernel(const ge
 
   // this slice's fp32 tile -> workspace [split][M][N] (plain f32 epilogue, alpha applied; rows >= M dropped)
   gemm_params_t pl = p;
-  pl.C = reinterpret_cast<float*>(p.C) + (size_t)(slice0 + split) * p.M * p.N;
-  pl.ldc = p.N;
+  pl.C = reinterpret_cast<float*>(p.C) + ws_base + (size_t)split * M * N;
+  pl.M = M;
+  pl.N = N;
+  pl.ldc = N;
   const uint32_t mw0 = m0 + wm * 128, nw0 = n0 + wn * 128;
   unsigned char* const wl = epl + wave * EPIL_WAVE_BYTES;
   big_epilogue_t<true, false, 0, 128, 0, true> ep(pl, wl, mw0, nw0, lane);  // plain stores: the reduce launch reads the slices right away
@@ -1272,19 +1291,24 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   *reinterpret_cast<f32x4*>(C + m * ldc + n) = t;
 }
 
-// grouped form: blockIdx.y = group; its slices start at slice0[g]
+// grouped form: blockIdx.y = group, with its own shape, leading dimension and block of the workspace; gridDim.x covers the
+// largest group and the workgroups past a smaller one's end leave
 struct splitk_groups_t {
   float* C[VLM_GEMM_MAX_GROUPS];
-  int slice0[VLM_GEMM_MAX_GROUPS], splits[VLM_GEMM_MAX_GROUPS], accumulate[VLM_GEMM_MAX_GROUPS];
+  int M[VLM_GEMM_MAX_GROUPS], N[VLM_GEMM_MAX_GROUPS], ldc[VLM_GEMM_MAX_GROUPS];
+  uint32_t ws_base[VLM_GEMM_MAX_GROUPS];
+  int splits[VLM_GEMM_MAX_GROUPS], accumulate[VLM_GEMM_MAX_GROUPS];
 };
-__global__ __launch_bounds__(256) void splitk_reduce_grouped_kernel(const float* __restrict__ ws, const splitk_groups_t g, int M, int N, int ldc) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, per = (size_t)M * N / 4;
-  if (i >= per) return;
+__global__ __launch_bounds__(256) void splitk_reduce_grouped_kernel(const float* __restrict__ ws, const splitk_groups_t g) {
   const int gi = blockIdx.y;
+  const int N = g.N[gi], ldc = g.ldc[gi];
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, mn = (size_t)g.M[gi] * N;
+  if (i >= mn / 4) return;
   float* const C = g.C[gi];
+  const float* const w = ws + g.ws_base[gi];
   const size_t e = i * 4, m = e / N, n = e - m * N;
   f32x4 t = g.accumulate[gi] ? *reinterpret_cast<const f32x4*>(C + m * ldc + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int s = 0; s < g.splits[gi]; ++s) t += *reinterpret_cast<const f32x4*>(ws + (size_t)(g.slice0[gi] + s) * M * N + e);
+  for (int s = 0; s < g.splits[gi]; ++s) t += *reinterpret_cast<const f32x4*>(w + (size_t)s * mn + e);
   *reinterpret_cast<f32x4*>(C + m * ldc + n) = t;
 }
 
@@ -1558,6 +1582,81 @@ extern "C" int vlm_gemm_bf16_grouped(int n_groups, const vlm_gemm_group_t* group
   return VLM_OK;
 }
 
+// One launch of the GROUPED wgrad kernel plus one reduce launch over up to VLM_GEMM_MAX_GROUPS problems, each a reduction over
+// the token rows [row0, row_end) of its own dY / X pair into its own M x N gradient; slices by csrc/wgrad_plan.h.
+// 1 = not offered (shape, alignment, more tiles than one round of workgroups, workspace), nothing launched.
+struct wgradT_problem_t {
+  const void* A;
+  const void* B;
+  int lda, ldb, M, N, row0, row_end;
+  float* C;
+  int ldc, accumulate;
+};
+static int launch_gemm_bigT_grouped(int n, const wgradT_problem_t* pr, float* splitk_ws, uint64_t splitk_ws_bytes, hipStream_t s) {
+  if (!splitk_ws || ((uintptr_t)splitk_ws & 15) || n < 1 || n > VLM_GEMM_MAX_GROUPS) return 1;
+  wgrad_plan_in_t in[VLM_GEMM_MAX_GROUPS];
+  for (int g = 0; g < n; ++g) {
+    const wgradT_problem_t& P = pr[g];
+    // whole 256-column tiles, 16-B vectors in the reduce, 32-bit offsets into a slice and into the rows of the operands
+    if (P.M < 1 || P.N < 1 || (P.N % BIG_BN) || (P.ldc % 4) || P.ldc < P.N || ((uintptr_t)P.C & 15) || ((uintptr_t)P.A & 15) ||
+        ((uintptr_t)P.B & 15) || (P.lda & 7) || (P.ldb & 7) || P.lda < P.M || P.ldb < P.N || P.row0 < 0 || P.row_end <= P.row0)
+      return 1;
+    if ((uint64_t)P.M * P.N * 4 >= (1ull << 31) || (uint64_t)P.row_end * P.lda * 2 >= (1ull << 31) ||
+        (uint64_t)P.row_end * P.ldb * 2 >= (1ull << 31))
+      return 1;
+    in[g] = wgrad_plan_in_t{((P.M + BIG_BM - 1) / BIG_BM) * (P.N / BIG_BN), (P.row_end - P.row0 + BIG_BK - 1) / BIG_BK,
+                            (uint64_t)P.M * P.N};
+  }
+  wgrad_plan_t plan;
+  if (wgrad_plan(n, in, plan_cus(), splitk_ws_bytes / 4, &plan)) return 1;
+  if (plan.ws_floats >= (1ull << 32)) return 1;  // ws_base is 32-bit
+  gemm_params_t p;
+  p.A = nullptr; p.B = nullptr; p.C = splitk_ws;
+  p.M = 0; p.N = 0; p.K = 0;
+  p.lda = 0; p.ldb = 0; p.ldc = 0;
+  p.epi = vlm_epilogue_t{};
+  p.epi.alpha = 1.0f;
+  p.epi.reserved = 1;
+  p.tiles_m = 0; p.tiles_n = 0;
+  p.group_m = 1;
+  p.splits = 1;
+  p.ksteps_per_split = 0;
+  p.n_groups = n;
+  splitk_groups_t rg{};
+  size_t per = 0;
+  for (int g = 0; g < n; ++g) {
+    const wgradT_problem_t& P = pr[g];
+    const wgrad_plan_group_t& G = plan.g[g];
+    p.grpT[g] = gemmT_group_t{P.A, P.B, P.lda, P.ldb, P.M, P.N, P.N / BIG_BN, in[g].tiles, P.row0, P.row_end, G.item0, G.kps,
+                              (uint32_t)G.ws_base};
+    rg.C[g] = P.C; rg.M[g] = P.M; rg.N[g] = P.N; rg.ldc[g] = P.ldc;
+    rg.ws_base[g] = (uint32_t)G.ws_base; rg.splits[g] = G.splits; rg.accumulate[g] = P.accumulate;
+    if ((size_t)P.M * P.N / 4 > per) per = (size_t)P.M * P.N / 4;
+  }
+  hipLaunchKernelGGL(vlm_gemm_bigT_kernel<true>, dim3(plan.items), dim3(GEMM_THREADS), 0, s, p);
+  VLM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(splitk_reduce_grouped_kernel, dim3((unsigned)((per + 255) / 256), n), dim3(256), 0, s,
+                     reinterpret_cast<const float*>(splitk_ws), rg);
+  VLM_CHECK_LAUNCH();
+  return VLM_OK;
+}
+
+// Batched wgrad: dW_i[M_i,N_i] (+)= dY_i^T X_i for up to VLM_GEMM_MAX_GROUPS problems that reduce over the same T token rows (the
+// fc2, fc1, proj and qkv weight gradients of one block evaluation) in ONE launch of the 256x256 wgrad kernel plus one reduce
+// launch.  1 = not offered: the caller makes the plain calls.
+extern "C" int vlm_gemm_wgrad_batch(int n, const vlm_wgrad_problem_t* problems, int T, float* splitk_ws, uint64_t splitk_ws_bytes,
+                                    void* stream) {
+  if (n < 1 || n > VLM_GEMM_MAX_GROUPS || !problems || T < 1) return VLM_ERR_ARG;
+  wgradT_problem_t pr[VLM_GEMM_MAX_GROUPS];
+  for (int i = 0; i < n; ++i) {
+    const vlm_wgrad_problem_t& P = problems[i];
+    if (!P.dy || !P.x || !P.dW || P.M < 1 || P.N < 1) return VLM_ERR_ARG;
+    pr[i] = wgradT_problem_t{P.dy, P.x, P.ld_dy, P.ld_x, P.M, P.N, 0, T, P.dW, P.ldc, P.accumulate};
+  }
+  if (gemm_big_mode() <= 0) return 1;
+  return launch_gemm_bigT_grouped(n, pr, splitk_ws, splitk_ws_bytes, (hipStream_t)stream);
+}
+
 // Grouped wgrad: dW_g[M,N] (+)= A[rows_g]^T B[rows_g] for every group of token rows in ONE launch of the 256x256 wgrad kernel
 // plus one reduce launch (the experts of an all_moe block, vision_transformer.py:607-681: the text expert's 3 520 tokens are a
 // tenth of a round on their own).  The workgroups of one round are dealt to the groups by their share of the reduction.
@@ -1577,67 +1676,16 @@ extern "C" int vlm_gemm_wgrad_grouped(int n_groups, const vlm_wgrad_group_t* gro
         hipMemset2DAsync(groups[g].C, (size_t)ldc * 4, 0, (size_t)N * 4, M, s) != hipSuccess)
       return VLM_ERR_LAUNCH;
   const int K_total = prev_end;
-  bool big = gemm_big_mode() > 0 && splitk_ws && (N % BIG_BN) == 0 && (ldc % 4) == 0 && (uint64_t)M * N * 4 < (1ull << 31) &&
-             (uint64_t)K_total * lda * 2 < (1ull << 31) && (uint64_t)K_total * ldb * 2 < (1ull << 31);
-  gemm_params_t p;
-  p.A = A; p.B = B; p.C = splitk_ws;
-  p.M = M; p.N = N; p.K = K_total;
-  p.lda = lda; p.ldb = ldb; p.ldc = N;
-  p.epi = vlm_epilogue_t{};
-  p.epi.alpha = 1.0f;
-  p.epi.reserved = 1;
-  p.tiles_m = (M + BIG_BM - 1) / BIG_BM;
-  p.tiles_n = (N + BIG_BN - 1) / BIG_BN;
-  p.group_m = 1;
-  p.splits = 1;
-  p.ksteps_per_split = 0;
-  p.n_groups = 0;
-  splitk_groups_t rg{};
-  if (big) {
-    const int ntile = p.tiles_m * p.tiles_n;
-    const int cus = plan_cus();
-    long total_steps = 0;
+  if (gemm_big_mode() > 0 && (uint64_t)K_total * lda * 2 < (1ull << 31) && (uint64_t)K_total * ldb * 2 < (1ull << 31)) {
+    wgradT_problem_t pr[VLM_GEMM_MAX_GROUPS];
     int live = 0;
-    for (int g = 0; g < n_groups; ++g)
-      if (groups[g].rows > 0) { total_steps += (groups[g].rows + BIG_BK - 1) / BIG_BK; ++live; }
-    if (live == 0) return VLM_OK;
-    if ((long)live * ntile > cus) big = false;  // more tiles than one round holds: the plain path's own split rules apply
-    // steps per workgroup so that the launch is one round: the smallest target whose slice count fits
-    long target = (total_steps * ntile + cus - 1) / cus;
-    if (target < 16) target = 16;
-    for (; big; target += 2) {
-      long items = 0;
-      for (int g = 0; g < n_groups; ++g)
-        if (groups[g].rows > 0) items += (((groups[g].rows + BIG_BK - 1) / BIG_BK + target - 1) / target) * ntile;
-      if (items <= cus) break;
-    }
-    int item0 = 0, slice0 = 0;
-    for (int g = 0; g < n_groups && big; ++g) {
+    for (int g = 0; g < n_groups; ++g) {
       const vlm_wgrad_group_t& G = groups[g];
-      if (G.rows == 0) continue;
-      if ((uintptr_t)G.C & 15) { big = false; break; }
-      const int nk = (G.rows + BIG_BK - 1) / BIG_BK;
-      int splits = (int)((nk + target - 1) / target);
-      int kps = (nk + splits - 1) / splits;
-      kps += kps & 1;
-      if (kps < 4) kps = 4;
-      splits = (nk + kps - 1) / kps;
-      const int i = p.n_groups++;
-      p.grpT[i] = gemmT_group_t{G.row0, G.row0 + G.rows, item0, kps, slice0};
-      rg.C[i] = G.C; rg.slice0[i] = slice0; rg.splits[i] = splits; rg.accumulate[i] = G.accumulate;
-      item0 += splits * ntile;
-      slice0 += splits;
+      if (G.rows > 0) pr[live++] = wgradT_problem_t{A, B, lda, ldb, M, N, G.row0, G.row0 + G.rows, G.C, ldc, G.accumulate};
     }
-    if (big && (size_t)slice0 * M * N * 4 > (size_t)splitk_ws_bytes) big = false;
-    if (big) {
-      hipLaunchKernelGGL(vlm_gemm_bigT_kernel<true>, dim3(item0), dim3(GEMM_THREADS), 0, s, p);
-      VLM_CHECK_LAUNCH();
-      const size_t per = (size_t)M * N / 4;
-      hipLaunchKernelGGL(splitk_reduce_grouped_kernel, dim3((unsigned)((per + 255) / 256), p.n_groups), dim3(256), 0, s,
-                         reinterpret_cast<const float*>(splitk_ws), rg, M, N, ldc);
-      VLM_CHECK_LAUNCH();
-      return VLM_OK;
-    }
+    if (live == 0) return VLM_OK;
+    const int rc = launch_gemm_bigT_grouped(live, pr, splitk_ws, splitk_ws_bytes, s);
+    if (rc <= 0) return rc;
   }
   for (int g = 0; g < n_groups; ++g) {  // not offered: one plain wgrad call per group
     const vlm_wgrad_group_t& G = groups[g];

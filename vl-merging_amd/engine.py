@@ -233,13 +233,20 @@ class FlatParams:
 
 
 # ----------------------------------------------------------------------------------------------------------------
-# weight-gradient side stream: wgrad GEMMs (a reduction over tokens into a small output: exactly one round of workgroups) are off
-# the critical path of backward; issued on a second HIP stream the hardware co-schedules them with the dgrad / attention / row
-# kernels of the main stream, whose last partial rounds leave CUs idle -- the more the smaller the pass: A/B on one box each,
+# weight-gradient side stream: wgrad GEMMs (a reduction over tokens into a small output) are off the critical path of backward;
+# issued on a second HIP stream the hardware co-schedules them with the dgrad / attention / row kernels of the main stream, whose
+# last partial rounds leave CUs idle -- the more the smaller the pass: A/B on one box each,
 # configs[4] (irtr, B = 20: M = 12 340 rows, 147 tiles of the N = 768 GEMMs on 256 CUs) 16.49 -> 15.58 ms per step (+5.8 %),
 # configs[1] (ufo, B = 22) 71.59 -> 70.88 ms (+1.0 %).  The main stream re-joins at the end of backward (and the optimizer and
 # every gradient bucket's collective wait for the side stream).  Default on since round 4 (the two-rank tests run with it);
 # VLM_WGRAD_STREAM=0 keeps every wgrad on the main stream.
+# On the side stream a launch that leaves CUs free wastes nothing, and what a wgrad costs its neighbours is CU-time and bytes, both
+# of which grow with the number of fp32 partial tiles it stores: a block with ONE row range therefore sends its four weight gradients
+# as one ops.gemm_wgrad_batch after the attention backward (108 tiles x 2 slices, where the four plain calls, each planned as a full
+# round, store 999 tiles): ufo B = 22 64.5 -> 63.0 ms per step, irtr B = 20 14.27 -> 13.65 ms (docs/experiments.md).  Batching
+# fc2 + fc1 + proj right after the proj dgrad and leaving qkv alone measured no gain (64.4 ms).  In stream order (side stream off)
+# an under-filled launch would idle CUs, so that schedule keeps the four plain calls, as do plans with several row ranges
+# (ops.gemm_wgrad_grouped per weight).
 _WGRAD = {"stream": None, "enabled": os.environ.get("VLM_WGRAD_STREAM", "1") != "0", "pending": False}
 
 
@@ -793,17 +800,22 @@ class _BlockFn(torch.autograd.Function):
         # other column partials (no atomics, no second pass over dh)
         _gemm_rows(dy2, [(r0, r1, wT16(e.fc2w), None, e.fc1b.grad) for r0, r1, e in rg], dh, act=L.ACT_MUL_AUX, aux=h,
                    col_sum_fold=fold)
-        with _Side(dy2, a, dh, ln2):
-            _wgrad_rows(dy2, a, [(r0, r1, wg(e.fc2w)) for r0, r1, e in rg])
-            _wgrad_rows(dh, ln2, [(r0, r1, e.fc1w.grad) for r0, r1, e in rg])
+        # side stream, one row range: the block's four weight gradients leave as ONE batched launch after the attention backward
+        batch = wgrad_stream() is not None and len(rg) == 1 and ops.wgrad_batch_serves(
+            rg[0][1] - rg[0][0], [(D, Fdim), (Fdim, D), (D, D), (3 * D, D)])
+        if not batch:
+            with _Side(dy2, a, dh, ln2):
+                _wgrad_rows(dy2, a, [(r0, r1, wg(e.fc2w)) for r0, r1, e in rg])
+                _wgrad_rows(dh, ln2, [(r0, r1, e.fc1w.grad) for r0, r1, e in rg])
         _gemm_rows(dh, [(r0, r1, wT16(e.fc1w), None, None) for r0, r1, e in rg], dln)
         for r0, r1, e in rg:
             rr = slice(r0, r1)
             _ln2_bwd_scale1(dln[rr], x1[rr], st2[rr], e, dx1[rr], dx2[rr], y1[rr] if y1 is not None else None, g1,
                             rs1[rr] if rs1 is not None else None, dy1[rr], fold)
         _gemm_rows(dy1, [(r0, r1, wT16(e.projw), None, None) for r0, r1, e in rg], do)
-        with _Side(dy1, o):
-            _wgrad_rows(dy1, o, [(r0, r1, wg(e.projw)) for r0, r1, e in rg])
+        if not batch:
+            with _Side(dy1, o):
+                _wgrad_rows(dy1, o, [(r0, r1, wg(e.projw)) for r0, r1, e in rg])
         dqkv = torch.empty(M, 3 * D, device=dev, dtype=BF16)
         dln1 = torch.empty(M, D, device=dev, dtype=BF16)
         rp = pc.relpos
@@ -821,8 +833,15 @@ class _BlockFn(torch.autograd.Function):
             if e.qb is not None and not fused_qv:
                 ops.colsum(dqkv[r0:r1, :D], e.qb.grad)
                 ops.colsum(dqkv[r0:r1, 2 * D:], e.vb.grad)
-        with _Side(dqkv, ln1):
-            _wgrad_rows(dqkv, ln1, [(r0, r1, e.qkvw.grad) for r0, r1, e in rg])
+        if batch:
+            (r0, r1, e), = rg
+            rr = slice(r0, r1)
+            with _Side(dy2, a, dh, ln2, dy1, o, dqkv, ln1):
+                ops.gemm_wgrad_batch([(dy2[rr], a[rr], wg(e.fc2w)), (dh[rr], ln2[rr], e.fc1w.grad),
+                                      (dy1[rr], o[rr], wg(e.projw)), (dqkv[rr], ln1[rr], e.qkvw.grad)])
+        else:
+            with _Side(dqkv, ln1):
+                _wgrad_rows(dqkv, ln1, [(r0, r1, e.qkvw.grad) for r0, r1, e in rg])
         _gemm_rows(dqkv, [(r0, r1, wT16(e.qkvw), None, None) for r0, r1, e in rg], dln1)
         for r0, r1, e in rg:
             rr = slice(r0, r1)

@@ -175,6 +175,47 @@ def gemm_wgrad_grouped(dy, x, groups, accumulate=True):
     L.check(rc, "vlm_gemm_wgrad_grouped")
 
 
+def wgrad_batch_serves(T, shapes):
+    """Does one gemm_wgrad_batch launch serve weight gradients of these (M, N) shapes over T contiguous token rows: the
+    workspace gate of gemm(), whole 256-column tiles, and all tiles within one round of the planned compute units."""
+    cus = L.get_lib().vlm_device_cus()
+    return (T >= 2048 and 1 <= len(shapes) <= L.GEMM_MAX_GROUPS and all(N % 256 == 0 for _, N in shapes)
+            and sum(-(-M // 256) * (N // 256) for M, N in shapes) <= (cus if cus > 0 else 256))
+
+
+def gemm_wgrad_batch(problems, accumulate=True):
+    """dW_i (+)= dy_i^T x_i for up to four problems (dy_i bf16 [T, M_i], x_i bf16 [T, N_i], dW_i f32 [M_i, N_i]) over the same T
+    token rows in one wgrad launch and one reduce launch (include/vlm_hip.h vlm_gemm_wgrad_batch): the four weight gradients of
+    a block evaluation.  `accumulate`: one flag, or one per problem.  Shapes the batch does not serve run as one gemm() each."""
+    n = len(problems)
+    if n < 1 or n > L.GEMM_MAX_GROUPS:
+        raise L.VlmError("gemm_wgrad_batch: 1..%d problems" % L.GEMM_MAX_GROUPS)
+    acc = [bool(accumulate)] * n if isinstance(accumulate, (bool, int)) else [bool(f) for f in accumulate]
+    if len(acc) != n:
+        raise L.VlmError("gemm_wgrad_batch: one accumulate flag, or one per problem")
+    T = problems[0][0].shape[0]
+    arr = (L.WgradProblem * n)()
+    for g, (dy, x, dW), f in zip(arr, problems, acc):
+        L.require_cuda(dy, x, dW)
+        if dy.dtype != BF16 or x.dtype != BF16 or dW.dtype != F32 or dy.dim() != 2 or x.dim() != 2 or dW.dim() != 2:
+            raise L.VlmError("gemm_wgrad_batch: bf16 dy [T, M] and x [T, N], f32 dW [M, N]")
+        if dy.shape[0] != T or x.shape[0] != T or tuple(dW.shape) != (dy.shape[1], x.shape[1]):
+            raise L.VlmError("gemm_wgrad_batch: dy %s, x %s, dW %s over T=%d rows" % (tuple(dy.shape), tuple(x.shape),
+                                                                                      tuple(dW.shape), T))
+        g.dy, g.ld_dy, g.M = dy.data_ptr(), _ld(dy), dy.shape[1]
+        g.x, g.ld_x, g.N = x.data_ptr(), _ld(x), x.shape[1]
+        g.dW, g.ldc, g.accumulate = dW.data_ptr(), _ld(dW), int(f)
+    rc = 1
+    if T >= 2048:  # the gate under which gemm() hands the wgrad kernel its workspace
+        ws = _scratch("splitk", SPLITK_WS_BYTES // 4, problems[0][0].device)
+        rc = L.get_lib().vlm_gemm_wgrad_batch(n, arr, T, L.ptr(ws), ws.numel() * 4, L.stream_ptr())
+    if rc == 1:  # not offered
+        for (dy, x, dW), f in zip(problems, acc):
+            gemm(dy, x, dW, ta=True, tb=True, accumulate=f)
+        return
+    L.check(rc, "vlm_gemm_wgrad_batch")
+
+
 def layernorm_fwd(x, gamma, beta, eps, out, stats=None):
     L.require_cuda(x, gamma, beta, out, stats)
     M, D = x.shape

@@ -499,6 +499,92 @@ int vlm_stock_plan_upload(const vlm_stock_job_t* jobs_host, int n_jobs, void* wo
 int vlm_stock_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SCE merge (select, calculate, erase; Wan et al. 2024, "FuseChat: Knowledge Fusion of Chat Models"; the `sce` method of
+ * mergekit), csrc/sce.hip.  NO REFERENCE SITE: the reference has no such merge; the arithmetic below is the specification and is
+ * pinned to a numpy restatement of it (tests/sce_restatement.py), not to the reference.  One job = one output tensor with central
+ * tensor c (base, required), sources W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), a rank k (1 <= k <= n_elem) and a scale lam.
+ * fp32 operations round once, no FMA, fp32 division is correctly rounded; "f64" = the operand widened exactly and the operation
+ * done in double, one rounding; key(x) = bits(x) & 0x7fffffff (the TIES key):
+ *   1. x_m = W_m - c (fp32)
+ *   2. per element:  mean = (((+0.0 + x_0) + x_1) + ...) / f32(S);  e_m = x_m - mean;
+ *      q = ((+0.0 + e_0 e_0) + e_1 e_1) + ...;  var = q / f32(S)
+ *   3. select: thr = the k-th largest key(var[i]) of the tensor;  sel[i] = key(var[i]) >= thr (every element equal to the
+ *      threshold is selected, as in TIES)
+ *   4. calculate: sq[m] = sum over the tensor of (sel ? f64(x_m) * f64(x_m) : +0.0), in the pair-statistics rule's order of
+ *      summation (thread, wave by halves, ((w0 + w1) + w2) + w3, records in chunk order, every sum from +0.0)
+ *   5. per job, in f64, on the device:  tot = ((+0.0 + sq[0]) + sq[1]) + ...;
+ *      w_m = tot > 0 ? f32(sq[m] / tot) : f32(1.0 / S)   (the comparison decides: a NaN gives the uniform weights)
+ *   6. erase, per element:  tt_m = sel ? x_m : +0.0;  s = ((+0.0 + tt_0) + tt_1) + ...;
+ *      source m agrees iff (s > 0 and tt_m > 0) or (s < 0 and tt_m < 0) (the TIES election);  over the agreeing m, in source
+ *      order:  num = ((+0.0 + w_a tt_a) + w_b tt_b) + ...,  den = ((+0.0 + w_a) + w_b) + ...;  d = den > 0 ? num / den : +0.0
+ *   7. dst = c + lam * d
+ * Counters per job (integer atomics only): `kept` = elements with sel (ONE count, not one per source), `conflict` = elements
+ * with a positive and a negative value among the tt_m, `empty` = elements where no entry agrees.
+ * Two differences from mergekit's form, on purpose:  k is the caller's rank over ALL n_elem elements (the host passes
+ * K = max(1, min(n, ceil(density n))), the TIES count; mergekit takes int(density * count_nonzero(var)));  a zero sum s elects
+ * nothing (mergekit elects + and clamps the denominator at 1e-6).
+ * S = 1 is the task-vector job: every var is +0.0, everything is selected, w_0 = 1, dst = c + lam * x_0.  k = n_elem goes through
+ * the same path with thr the smallest key.  Non-finite inputs are outside the contract.  dst must not overlap base or a source
+ * of its own job (five passes read them; vlm_sce_plan_upload rejects such a job as vlm_ties_plan_upload does -- overlap ACROSS
+ * jobs is the caller's to avoid).
+ */
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each */
+  uint64_t k;                           /* elements to select (step 3) */
+  uint64_t n_elem;
+  int32_t n_src;
+  float lam;
+} vlm_sce_job_t;
+
+/* The workspace of an SCE plan BEGINS with this header (byte offsets from its start): vlm_ties_header_t's fields -- with ONE
+ * selection unit per job, so n_units == n_jobs and a job's state is its whole result -- then the reducer's two tables. */
+typedef struct {
+  uint64_t n_jobs, n_units, n_chunks;
+  uint64_t jobs_off;      /* vlm_sce_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table */
+  uint64_t unit0_off;     /* uint32 [n_jobs]: the unit of each job (its own index) */
+  uint64_t units_off;     /* {uint32 job, uint32 0} [n_units] */
+  uint64_t state_off;     /* vlm_sce_result_t [n_jobs]: overwritten by every run */
+  uint64_t counters_off;  /* uint64 [n_jobs][VLM_SCE_COUNTERS] */
+  uint64_t hist_off;      /* uint64 [n_jobs][2048]: selection histograms, zero between runs */
+  uint64_t first_off;     /* uint64 [n_jobs + 1]: the first chunk of each job, then n_chunks */
+  uint64_t records_off;   /* double [n_chunks][VLM_MERGE_MAX_SRC]: one record of sq per chunk, overwritten by every run */
+} vlm_sce_header_t;
+/* per job after a run; slots of sources a job does not have are zero */
+typedef struct {
+  uint32_t key;       /* step 3: thr as a key (= the bits of the threshold variance) */
+  uint32_t reserved;
+  uint64_t rank;      /* 1 + how many of the keys equal to thr rank above the k-th place */
+  double sq[VLM_MERGE_MAX_SRC];         /* step 4 */
+  double tot;                           /* step 5 */
+  float w[VLM_MERGE_MAX_SRC];           /* step 5: what step 6 multiplies by */
+} vlm_sce_result_t;
+/* per job after a run: kept, conflict, empty */
+#define VLM_SCE_COUNTERS 3
+
+/* Bytes of device workspace an SCE plan for n_jobs jobs over total_elems elements needs (header, jobs, chunk table, unit and
+ * first-chunk tables, one result and one histogram per job, counters, one record per chunk).  No reference site. */
+size_t vlm_sce_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (the checks of vlm_ties_plan_upload: pointers non-NULL and 16-byte aligned, base required, 1 <= n_src <=
+ * VLM_MERGE_MAX_SRC and n_elem > 0, 1 <= k <= n_elem, dst's byte range meets no input's, else VLM_ERR_ARG; a length or chunk
+ * count past 32 bits of float4s is VLM_ERR_UNSUPPORTED), build the chunk table on the host, copy header + jobs + tables into
+ * `workspace` (16-byte aligned; VLM_ERR_WORKSPACE if it is too small) and zero the histograms.  SYNCHRONISES `stream` before it
+ * returns (pageable temporary source); it is the last host synchronisation of a plan.  Implements no step of the rule; no
+ * reference site. */
+int vlm_sce_plan_upload(const vlm_sce_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: nine launches, stream-ordered, and nothing else -- steps 1-3 (three histogram launches over all jobs,
+ * 11 + 10 + 10 bits of key(var), each followed by the tiny launch that picks the bin of the k-th largest key), the reducer
+ * (steps 1-4 with the threshold read from the job's result, one record per chunk), the fold (a job's records in chunk order,
+ * then step 5: the whole result) and the apply pass (steps 1-3 again and 6-7 with thr and w read from the job's result, plus the
+ * counters); no host synchronisation.  var and sel are recomputed by every pass: nothing per element is stored between passes,
+ * so a run streams the inputs five times and writes the output once.  May be called again on the same workspace and gives the
+ * same bytes and counters: the run zeroes its own histograms and counters on the stream.  One run at a time per workspace.
+ * No reference site. */
+int vlm_sce_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

@@ -203,6 +203,33 @@ class StockResult(ctypes.Structure):
                 ("scale", c_float), ("reserved", ctypes.c_uint32)]
 
 
+SCE_COUNTERS = 3  # VLM_SCE_COUNTERS: kept, conflict, empty
+
+
+class SceJob(ctypes.Structure):
+    """vlm_sce_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("k", c_u64),
+        ("n_elem", c_u64),
+        ("n_src", ctypes.c_int32),
+        ("lam", c_float),
+    ]
+
+
+class SceHeader(ctypes.Structure):
+    """vlm_sce_header_t: the first bytes of an SCE plan's workspace (vlm_ties_header_t's fields, then the reducer's two tables)."""
+    _fields_ = list(TiesHeader._fields_) + [(n, c_u64) for n in ("first_off", "records_off")]
+
+
+class SceResult(ctypes.Structure):
+    """vlm_sce_result_t: the threshold, the sums, their total and the weights of one job."""
+    _fields_ = [("key", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("rank", c_u64), ("sq", ctypes.c_double * MERGE_MAX_SRC),
+                ("tot", ctypes.c_double), ("w", c_float * MERGE_MAX_SRC)]
+
+
 class ScatterSrc(ctypes.Structure):
     """vlm_scatter_src_t of include/vlm_hip.h."""
     _fields_ = [("g", c_void_p), ("g_is_f32", ctypes.c_int32), ("ld", ctypes.c_int32), ("first_row", ctypes.c_int32),
@@ -312,6 +339,9 @@ SIGNATURES = {
     "vlm_stock_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_stock_plan_upload": (c_int, [ctypes.POINTER(StockJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_stock_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_sce_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_sce_plan_upload": (c_int, [ctypes.POINTER(SceJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_sce_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_bf16_grouped": (c_int, [c_int, ctypes.POINTER(GemmGroup), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

@@ -25,7 +25,8 @@ struct band_sel {
   typedef vlm_band_job_t job_t;
   typedef vlm_band_header_t hdr_t;
   typedef vlm_band_state_t state_t;
-  static constexpr int RANKS = 2, COUNTERS = VLM_BAND_COUNTERS;
+  static constexpr int RANKS = 2, COUNTERS = VLM_BAND_COUNTERS, RECORD_DOUBLES = 0;
+  static constexpr bool ELEM_KEY = false;  // one unit per (job, source)
   static __device__ __forceinline__ u64_t want(const job_t& j, uint32_t m, int r) { return r == 0 ? j.k_lo[m] : j.k_hi[m]; }
   static __device__ __forceinline__ bool none(const job_t& j, uint32_t m, int r) { return r == 1 && j.k_hi[m] == 0; }
   static __device__ __forceinline__ uint32_t key(const state_t& s, int r) { return r == 0 ? s.key_lo : s.key_hi; }

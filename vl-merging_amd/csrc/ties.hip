@@ -21,7 +21,8 @@ struct ties_sel {
   typedef vlm_ties_job_t job_t;
   typedef vlm_ties_header_t hdr_t;
   typedef vlm_ties_state_t state_t;
-  static constexpr int RANKS = 1, COUNTERS = VLM_TIES_COUNTERS;
+  static constexpr int RANKS = 1, COUNTERS = VLM_TIES_COUNTERS, RECORD_DOUBLES = 0;
+  static constexpr bool ELEM_KEY = false;  // one unit per (job, source)
   static __device__ __forceinline__ u64_t want(const job_t& j, uint32_t m, int) { return j.k[m]; }
   static __device__ __forceinline__ bool none(const job_t&, uint32_t, int) { return false; }
   static __device__ __forceinline__ uint32_t key(const state_t& s, int) { return s.key; }

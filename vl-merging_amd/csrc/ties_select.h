@@ -21,6 +21,12 @@
 // RANKS (1 or 2), COUNTERS, on the device want(job, m, r) (the rank asked for), none(job, m, r) (no such rank), key(state, r),
 // rank(state, r), store(state, r, key, rank left), and on the host mode_ok(job) and ranks_ok(job, m), its own job checks.
 // Everything below is then the method's but for its element rule and apply kernel.
+//
+// ELEM_KEY (sce.hip): the unit is the JOB, not the (job, source) pair -- the key is a function of the element's c and ALL its
+// sources, Sel::elem_key<NSRC>(c, wv), one 2048-bin histogram per job in global memory and ONE per workgroup in LDS (8 KiB, not
+// 32); m is 0 wherever the traits are asked.  RECORD_DOUBLES > 0: the header also has first_off (the first chunk of each job,
+// host-made) and records_off (that many doubles per chunk, device-made), for a reduction that follows the select.  ties_sel and
+// band_sel say false and 0 and get the kernels and the layout they had.
 #pragma once
 #include "vlm_common.h"
 #include "chunk_walk.h"
@@ -46,6 +52,15 @@ template <int PASS>
 __device__ __forceinline__ constexpr int ties_shift() { return PASS == 0 ? 20 : (PASS == 1 ? 10 : 0); }
 
 __device__ __forceinline__ uint32_t ties_key(float w, float c) { return __float_as_uint(__fsub_rn(w, c)) & 0x7fffffffu; }
+
+// how many units a job has: one per source, or the job itself
+template <class Sel>
+__host__ __device__ __forceinline__ int select_units(const typename Sel::job_t& j) {
+  if constexpr (Sel::ELEM_KEY) return 1;
+  else return j.n_src;
+}
+template <class Sel>
+constexpr int select_slots() { return Sel::ELEM_KEY ? 1 : VLM_MERGE_MAX_SRC; }  // histograms a workgroup holds in LDS
 
 template <class Sel>
 struct select_view_t {
@@ -100,6 +115,18 @@ struct select_hist_rule {
   }
 };
 
+// the element-keyed pass: one key per element into the workgroup's one histogram
+template <class Sel, int PASS, int NSRC>
+struct select_elem_hist_rule {
+  const uint32_t& p0;
+  uint32_t* lds;
+  __device__ __forceinline__ chunk_no_prep prep(uint64_t) const { return {}; }
+  __device__ __forceinline__ float elem(chunk_no_prep, int, float c, const float* wv) const {
+    select_bin<1, PASS>(Sel::template elem_key<NSRC>(c, wv), p0, 0u, lds);
+    return 0.0f;
+  }
+};
+
 // a workgroup's LDS histograms into a job's global ones: the first BINS bins of every source
 template <uint32_t BINS>
 __device__ __forceinline__ void select_flush(uint32_t* lds, u64_t* hist, int n_src) {
@@ -118,13 +145,15 @@ __device__ __forceinline__ void select_flush(uint32_t* lds, u64_t* hist, int n_s
 template <class Sel, int PASS>
 __global__ __launch_bounds__(TIES_THREADS) void vlm_select_hist_kernel(unsigned char* __restrict__ ws) {
   static_assert(Sel::RANKS == 1 || Sel::RANKS == 2, "a source's 2048-bin slot holds the 1024-bin halves of at most two ranks");
+  static_assert(!Sel::ELEM_KEY || Sel::RANKS == 1, "the element-keyed rule bins for one rank");
+  constexpr int SLOTS = select_slots<Sel>();
   // a run can have touched 1024 bins per source with one rank in passes 1 and 2, otherwise the whole slot
   constexpr uint32_t TOUCHED = PASS > 0 && Sel::RANKS == 1 ? ties_bins<PASS>() : TIES_BINS;
-  __shared__ uint32_t lds[VLM_MERGE_MAX_SRC * TIES_BINS];
+  __shared__ uint32_t lds[SLOTS * TIES_BINS];
   const select_view_t<Sel> w = select_view<Sel>(ws);
   uint64_t c0, c1;
   if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
-  for (uint32_t i = threadIdx.x; i < VLM_MERGE_MAX_SRC * TIES_BINS; i += TIES_THREADS) lds[i] = 0;
+  for (uint32_t i = threadIdx.x; i < SLOTS * TIES_BINS; i += TIES_THREADS) lds[i] = 0;
   __syncthreads();
   // two named arrays, not p[RANKS][4]: the two-rank passes 1 and 2 then keep the registers they had (docs/experiments.md)
   uint32_t p0[VLM_MERGE_MAX_SRC] = {0, 0, 0, 0}, p1[VLM_MERGE_MAX_SRC] = {0, 0, 0, 0};
@@ -133,8 +162,8 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_select_hist_kernel(unsigned 
       [&](uint32_t cur) {
         if (PASS > 0) {
 #pragma unroll
-          for (int m = 0; m < VLM_MERGE_MAX_SRC; ++m)
-            if (m < w.jobs[cur].n_src) {
+          for (int m = 0; m < SLOTS; ++m)
+            if (m < select_units<Sel>(w.jobs[cur])) {
               p0[m] = Sel::key(w.state[w.unit0[cur] + m], 0);
               if (Sel::RANKS > 1) p1[m] = Sel::key(w.state[w.unit0[cur] + m], 1);
             }
@@ -142,11 +171,16 @@ __global__ __launch_bounds__(TIES_THREADS) void vlm_select_hist_kernel(unsigned 
       },
       [&](const typename Sel::job_t& j, uint64_t start4) {
         with_nsrc(j.n_src, [&](auto S) {
-          select_hist_rule<Sel::RANKS, PASS, S()> rule{p0, p1, lds};
-          chunk_stream<S(), true, false>(j, start4, rule);
+          if constexpr (Sel::ELEM_KEY) {
+            select_elem_hist_rule<Sel, PASS, S()> rule{p0[0], lds};
+            chunk_stream<S(), true, false>(j, start4, rule);
+          } else {
+            select_hist_rule<Sel::RANKS, PASS, S()> rule{p0, p1, lds};
+            chunk_stream<S(), true, false>(j, start4, rule);
+          }
         });
       },
-      [&](uint32_t cur) { select_flush<TOUCHED>(lds, w.hist + (uint64_t)w.unit0[cur] * TIES_BINS, w.jobs[cur].n_src); });
+      [&](uint32_t cur) { select_flush<TOUCHED>(lds, w.hist + (uint64_t)w.unit0[cur] * TIES_BINS, select_units<Sel>(w.jobs[cur])); });
 }
 
 // One workgroup per unit: find, for every rank, the bin that holds the rank-th largest key, walking down from the top bin.
@@ -243,18 +277,20 @@ static size_t select_layout(typename Sel::hdr_t* h, uint64_t n_jobs, uint64_t n_
   h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
   h->unit0_off = at.take(n_jobs * sizeof(uint32_t));
   h->units_off = at.take(n_units * sizeof(ties_unit_t));
+  if constexpr (Sel::RECORD_DOUBLES > 0) h->first_off = at.take((n_jobs + 1) * sizeof(uint64_t));  // host-made: before the state
   h->state_off = at.take(n_units * sizeof(typename Sel::state_t));
   h->counters_off = at.take(n_jobs * Sel::COUNTERS * sizeof(uint64_t));
   h->hist_off = at.take(n_units * TIES_BINS * sizeof(uint64_t));
+  if constexpr (Sel::RECORD_DOUBLES > 0) h->records_off = at.take(n_chunks * Sel::RECORD_DOUBLES * sizeof(double));
   return at.off;
 }
 
 template <class Sel>
 static size_t select_plan_bytes(int n_jobs, uint64_t total_elems) {
   if (n_jobs < 0) return 0;
-  // upper bounds: chunks_bound, and every job has at most VLM_MERGE_MAX_SRC sources
+  // upper bounds: chunks_bound, and every job has at most VLM_MERGE_MAX_SRC sources (element-keyed: one unit)
   typename Sel::hdr_t h;
-  return select_layout<Sel>(&h, (uint64_t)n_jobs, (uint64_t)n_jobs * VLM_MERGE_MAX_SRC, chunks_bound(n_jobs, total_elems));
+  return select_layout<Sel>(&h, (uint64_t)n_jobs, (uint64_t)n_jobs * select_slots<Sel>(), chunks_bound(n_jobs, total_elems));
 }
 
 template <class Sel>
@@ -266,10 +302,10 @@ static int select_plan_upload(const typename Sel::job_t* jobs, int n_jobs, void*
     if (j.n_elem == 0 || !Sel::mode_ok(j)) return VLM_ERR_ARG;
     const int rc = chunk_job_check(j, CHUNK_OVERLAP_NONE, true);
     if (rc != VLM_OK) return rc;
-    for (int m = 0; m < j.n_src; ++m)
+    for (int m = 0; m < select_units<Sel>(j); ++m)
       if (!Sel::ranks_ok(j, m)) return VLM_ERR_ARG;
     n_chunks += chunks_of(j.n_elem);
-    n_units += (uint64_t)j.n_src;
+    n_units += (uint64_t)select_units<Sel>(j);
   }
   if (!chunk_count_ok(n_chunks) || n_units >= (1ull << 32)) return VLM_ERR_UNSUPPORTED;
   typename Sel::hdr_t hdr;
@@ -280,12 +316,19 @@ static int select_plan_upload(const typename Sel::job_t* jobs, int n_jobs, void*
   uint32_t* unit0 = reinterpret_cast<uint32_t*>(img.data() + hdr.unit0_off);
   ties_unit_t* units = reinterpret_cast<ties_unit_t*>(img.data() + hdr.units_off);
   uint64_t u = 0;
+  [[maybe_unused]] uint64_t c = 0;  // chunks before job i
   for (int i = 0; i < n_jobs; ++i) {
     unit0[i] = (uint32_t)u;
-    for (int m = 0; m < jobs[i].n_src; ++m) {
+    for (int m = 0; m < select_units<Sel>(jobs[i]); ++m) {
       units[u].job = (uint32_t)i;
       units[u].m = (uint32_t)m;
       ++u;
+    }
+    if constexpr (Sel::RECORD_DOUBLES > 0) {
+      uint64_t* first = reinterpret_cast<uint64_t*>(img.data() + hdr.first_off);
+      first[i] = c;
+      c += chunks_of(jobs[i].n_elem);
+      first[i + 1] = c;
     }
   }
   // the histograms start at zero; every scan launch leaves them at zero again

@@ -1,4 +1,4 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock -- and the expert-pair statistics
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock, SCE -- and the expert-pair statistics
 (expert_stats) that say how far apart the experts are before any of them is tried.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
@@ -24,6 +24,10 @@ operand widened exactly, the operation in double:
      cc = cos clamped to [0, 1] by comparison;  t = S cc / (1 + (S - 1) cc) (S = 1: t = 1);  scale = float32(t / S)
   4. d = ((0 + x_0) + x_1) + ... (fp32);  dst = c + scale * d
 It has no hyper-parameter; the apply pass reads a scalar the reduction over the same tensor made, ordered by the stream alone.
+
+sce_merge (SCE, Wan et al. 2024) likewise: no reference site, the rule in include/vlm_hip.h, csrc/sce.hip held to
+tests/sce_restatement.py: a select on the variance across the experts, a reduction that depends on its threshold, an apply pass
+that reads both.
 """
 import ctypes
 import math
@@ -665,6 +669,62 @@ def stock_merge(state_dict, config, central_weight=None, device="cuda", plan_out
     synchronises)."""
     return _task_vector_merge(StockPlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, name=dst),
                               state_dict, config, central_weight, 1.0, device, plan_out, report_out)
+
+
+class ScePlan(_Plan):
+    """The job table of csrc/sce.hip; run() enqueues the nine launches of an SCE merge (three histogram passes of the radix select
+    over the variance of every element's task vectors, a bin pick after each, the reducer of the selected entries' squared norms,
+    the fold that ends in the weights of step 5, the apply pass that reads them) without a host synchronisation."""
+
+    KIND, GPU_ONLY, JOB = "SCE", "the SCE kernels run on the GPU only", L.SceJob
+    BYTES, UPLOAD, RUN, HEADER = "vlm_sce_plan_bytes", "vlm_sce_plan_upload", "vlm_sce_run", L.SceHeader
+    PASSES = 5  # three selection passes, the reducer and the apply pass: each streams every source and the central tensor once
+
+    def add(self, srcs, base, density=None, lam=1.0, keep=None, name=None):
+        """One output tensor.  `density` gives K (ties_keep_count over all n elements); `keep` = an explicit K instead."""
+        def fill(job):
+            job.k = ties_keep_count(density, int(job.n_elem)) if keep is None else int(keep)
+            job.lam = float(lam)
+        return self._add(fill, srcs, base, name=name)
+
+    def results(self):
+        """(the raw vlm_sce_result_t, the three counters) of every job as the device left them (this synchronises)."""
+        if self.ws is None:
+            raise L.VlmError("ScePlan.report() needs a plan that has run")
+        hdr = self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
+        size, n = ctypes.sizeof(L.SceResult), len(self.jobs)
+        raw = self.ws[hdr.state_off: hdr.state_off + size * n].cpu().numpy().tobytes()
+        counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * L.SCE_COUNTERS * n].cpu().numpy().view("<u8").reshape(n, L.SCE_COUNTERS)
+        return [(L.SceResult.from_buffer_copy(raw[i * size: (i + 1) * size]), [int(v) for v in counters[i]]) for i in range(n)]
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): K, the variance threshold as a float and as its key, how many
+        elements were selected (`kept`: one count, not one per source), per source `sq` (the energy of its selected entries) and
+        `weight` (as a float and as its bits), their total `tot`, the elements whose selected entries disagree in sign and the
+        elements where no entry agrees -- all as the device made them."""
+        rows = []
+        for name, job, (r, (kept, conflict, empty)) in zip(self.names, self.jobs, self.results()):
+            S = job.n_src
+            rows.append({"dst": name, "n": int(job.n_elem), "K": int(job.k), "threshold": _key_float(r.key), "threshold_bits": int(r.key),
+                         "kept": kept, "sq": [r.sq[m] for m in range(S)], "tot": r.tot, "weight": [float(r.w[m]) for m in range(S)],
+                         "weight_bits": [float32_bits(r.w[m]) for m in range(S)], "conflict": conflict, "empty": empty})
+        return rows
+
+
+def sce_merge(state_dict, config, central_weight=None, density=0.1, lam=None, device="cuda", plan_out: Optional[list] = None,
+              report_out: Optional[list] = None):
+    """SCE merge (select, calculate, erase; Wan et al. 2024, mergekit's `sce`) of the modality experts' task vectors `W_m - central`
+    (no reference site; the rule: include/vlm_hip.h): per tensor, the `density` share of elements whose task vectors vary most
+    across the experts is selected, every expert is weighted by the energy of its selected entries, the entries whose sign loses
+    the TIES election are erased and the weighted mean of the rest is added to the central tensor.  Unlike mergekit's form, K counts
+    over all n elements (ties_keep_count) and a zero sum elects nothing.  Same inputs, keys, pass-through and KeyError behaviour as
+    sum_task_vectors and ties_merge; `lam=None` takes config["sum_lambda"].  A layer with ONE source is the task-vector job with
+    ratio 1 that sum_task_vectors issues for it.  `plan_out` receives the ScePlan FIRST whenever a layer has several sources, then
+    the MergePlan of the single-source layers if there are any; `report_out` receives ScePlan.report() (reading it back
+    synchronises)."""
+    ties_keep_count(density, 1)  # ValueError before any device work
+    return _task_vector_merge(ScePlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density=density, lam=lam, name=dst),
+                              state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
 # ------------------------------------------------------------------------------------------------- expert-pair statistics

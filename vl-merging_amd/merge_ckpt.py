@@ -1,12 +1,12 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
 sum_task_vectors / regmean on the state_dict it has just read); a merged checkpoint on disk is what one hands on, so this tool
 runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge), DARE (merge.dare_merge), Model
-Breadcrumbs (merge.band_merge), DELLA (merge.della_merge) and Model Stock (merge.stock_merge; none of the five has a reference
-site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
+Breadcrumbs (merge.band_merge), DELLA (merge.della_merge), Model Stock (merge.stock_merge) and SCE (merge.sce_merge; none of the six has a
+reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
 `vlffn_start_layer_index`, `only_activate_used_experts`, `loss_names`, `merge_ratio`, `sum_lambda`, `central_weight`.
 
   --method interp    merge_weights      (--ratio overrides merge_ratio)
@@ -19,11 +19,14 @@ site) outside a model.  The words after the options are a config in run.py's gra
                                          --seed, --della-mode {linear,ties}, --no-rescale, --lambda, --central as above)
   --method stock     stock_merge        (--central as above; the method has no hyper-parameter: --lambda, --density and the rest are
                                          ignored, as they are for interp)
+  --method sce       sce_merge          (--density = the share of elements selected by their variance across the experts;
+                                         --lambda, --central as above)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
                      dare: n, keep_below, kept per source, conflict, empty;
                      breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty;
                      della: n, keep_lo, keep_hi, row_len, kept per source, conflict, empty;
-                     stock: n, sq per source, dot and cosine per pair, the mean cosine, t, scale and its bits)
+                     stock: n, sq per source, dot and cosine per pair, the mean cosine, t, scale and its bits;
+                     sce: n, K, the variance threshold, kept, sq and weight per source, tot, conflict, empty)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -38,7 +41,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce")
 
 
 def build_parser():
@@ -46,9 +49,11 @@ def build_parser():
     p.add_argument("--method", choices=METHODS, required=True)
     p.add_argument("--ckpt", required=True, help="all_moe checkpoint (a Lightning .ckpt or a bare state_dict file)")
     p.add_argument("--out", required=True, help="merged checkpoint to write")
-    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs / della / stock; default: central_weight of the config")
-    p.add_argument("--density", type=float, default=0.2, help="ties / breadcrumbs: fraction of each task vector kept, in (0, 1]; della: the mean keep probability")
-    p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare / breadcrumbs / della: overrides sum_lambda")
+    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs / della / stock / sce; default: central_weight of the config")
+    p.add_argument("--density", type=float, default=0.2,
+                   help="ties / breadcrumbs: fraction of each task vector kept, in (0, 1]; della: the mean keep probability; "
+                        "sce: fraction of the elements selected by their variance across the experts, in (0, 1]")
+    p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare / breadcrumbs / della / sce: overrides sum_lambda")
     p.add_argument("--drop", type=float, default=0.9, help="dare: probability of dropping a task-vector entry, in [0, 1)")
     p.add_argument("--seed", type=int, default=0, help="dare / della: seed of the mask (64 bits)")
     p.add_argument("--dare-mode", dest="dare_mode", choices=("linear", "ties"), default="linear",
@@ -81,6 +86,8 @@ def parse_args(argv):
         cfg["merge_ratio"] = args.ratio
     if args.method == "ties" and not (0.0 < args.density <= 1.0):
         raise ValueError("TIES density must lie in (0, 1], got %r" % (args.density,))
+    if args.method == "sce" and not (0.0 < args.density <= 1.0):
+        raise ValueError("SCE density must lie in (0, 1], got %r" % (args.density,))
     if args.method == "dare":
         importlib.import_module("vl_merging_amd.merge").dare_keep_below(args.drop)  # the one statement of the rule; ValueError
         if not 0 <= args.seed < 2 ** 64:
@@ -118,6 +125,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
         out = merge.stock_merge(sd, cfg, central_weight=central, report_out=rows)
         if report is not None:
             report.extend(rows)
+    elif method == "sce":
+        rows = []
+        out = merge.sce_merge(sd, cfg, central_weight=central, density=density, report_out=rows)
+        if report is not None:
+            report.extend(rows)
     elif method == "breadcrumbs":
         rows = []
         out = merge.band_merge(sd, cfg, central_weight=central, density=density, report_out=rows, **(band or {}))
@@ -144,6 +156,7 @@ def main(argv):
     central = ckpt.load_file(args.central) if args.central else None
     report = [] if args.report else None
     is_dare, is_band, is_della = args.method == "dare", args.method == "breadcrumbs", args.method == "della"
+    has_density = args.method in ("ties", "sce") or is_band or is_della
     out = merge_state(args.method, sd, cfg, central=central, density=args.density, report=report,
                       dare=dict(drop=args.drop, seed=args.seed, mode=args.dare_mode, rescale=args.rescale),
                       band=dict(gamma=args.gamma, mode=args.band_mode),
@@ -152,7 +165,7 @@ def main(argv):
     torch.save({"state_dict": {k: v.detach().to("cpu") for k, v in out.items()}}, args.out)
     if args.report:
         with open(args.report, "w") as f:
-            json.dump({"method": args.method, "density": args.density if args.method == "ties" or is_band or is_della else None,
+            json.dump({"method": args.method, "density": args.density if has_density else None,
                        "drop": args.drop if is_dare else None, "seed": args.seed if is_dare or is_della else None,
                        "dare_mode": args.dare_mode if is_dare else None,
                        "gamma": args.gamma if is_band else None, "band_mode": args.band_mode if is_band else None,

@@ -302,6 +302,11 @@ class ViLTransformerSS(nn.Module):
         sum_task_vectors; not wired to a config key and not called from __init__."""
         return merge_ops.stock_merge(state_dict, self.hparams.config, device=self._merge_device())
 
+    def sce_merge(self, state_dict, density=0.1, lam=None):
+        """SCE merge of the experts' task vectors (no reference site; merge.sce_merge).  Same contract as sum_task_vectors; not
+        wired to a config key and not called from __init__."""
+        return merge_ops.sce_merge(state_dict, self.hparams.config, density=density, lam=lam, device=self._merge_device())
+
     def expert_stats(self, state_dict, raw=False, trunc_rms=None):
         """How far apart the modality experts of `state_dict` are (no reference site; merge.expert_stats).  Merges nothing; not
         wired to a config key and not called from __init__."""

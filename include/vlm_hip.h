@@ -637,6 +637,18 @@ typedef struct {
 
 int vlm_gemm_bf16(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,
                   int ldc, int c_is_f32, const vlm_epilogue_t* epi, void* stream);
+/* vlm_gemm_bf16 with a row vector: row_live is f32 [M] (or NULL: the call above).  A row is DEAD where its entry is 0.0f; only
+ * zero is tested, the vector's other values are never used (DropPath's per-row factors, 0 or 1 / keep, serve as they are).
+ * A 256-row tile of the 256x256 kernel whose rows inside [0, M) are ALL dead skips its operand loads and its K loop and runs
+ * its normal epilogue on accumulators that are +0: it writes epilogue(0) -- bias, gelu(bias), gelu'(bias) into aux, or
+ * residual + row_scale * col_scale * bias -- and the column sums of those values; no output row is left unwritten.  Every
+ * other tile computes exactly what vlm_gemm_bf16 computes, and so does every tile of a call that the 128x128 kernel serves and
+ * of the residual variant that also stores aux (same results, no skip).  row_live needs the 4-byte alignment of a float only.  The caller promises
+ * that nothing it uses depends on the dead rows' products: in the forward pass their branch is multiplied by a zero
+ * row_scale, in the backward pass the dead rows of A are exact zeros, so the skipped products are zeros too.  No reference
+ * site (timm's DropPath, vision_transformer.py:586/:603, computes the dropped branch and multiplies it by 0). */
+int vlm_gemm_bf16_live(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,
+                       int ldc, int c_is_f32, const vlm_epilogue_t* epi, const float* row_live, void* stream);
 /* Grouped form of the ta = tb = 0 call (K9): row ranges of ONE activation matrix go through DIFFERENT weights -- the
  * modality experts of an all_moe block act on the text rows and on the image rows of the segment-major token matrix
  * (modules/vision_transformer.py:607-681: x[:, :max_text_len] through mlp['l'] / attn['l'], the rest through ['v'], then
@@ -1027,6 +1039,16 @@ size_t vlm_attention_bwd_ws_floats(const vlm_attn_desc_t* d, int with_dbias);
 int vlm_attention_bwd(const vlm_attn_desc_t* d, const void* out_bf16, int ld_out, const void* dout_bf16, int ld_dout,
                       const float* lse, float* delta_ws, size_t ws_floats, void* dqkv_bf16, int ld_dqkv, float* dbias_t,
                       const vlm_attn_colsum_t* colsum, void* stream);
+/* vlm_attention_bwd with a row vector: row_live is f32 [total rows] (or NULL: the call above), DropPath's per-row factors.  A
+ * (sample, segment) is DEAD where the factor of its segment's first row is 0.0f -- in JOINT mode the two segments of a sample
+ * share one draw and both first rows must be zero, in SEPARATE mode each segment has its own.  The caller promises that the dO
+ * rows of a dead (sample, segment) are zeros; its dQ, dK and dV rows and its share of every column sum and of the bias-table
+ * gradient are then zeros as well, and the fused dK / dV / bias-gradient kernel and the hand-placed dQ stream store those zeros
+ * without recomputing the sample (delta and the bias-gradient kernel's operands are still written for its rows).  The other
+ * kernels of the plan compute every sample.  Every other row of dqkv is what vlm_attention_bwd writes.  No reference site. */
+int vlm_attention_bwd_live(const vlm_attn_desc_t* d, const void* out_bf16, int ld_out, const void* dout_bf16, int ld_dout,
+                           const float* lse, float* delta_ws, size_t ws_floats, void* dqkv_bf16, int ld_dqkv, float* dbias_t,
+                           const vlm_attn_colsum_t* colsum, const float* row_live, void* stream);
 
 #ifdef __cplusplus
 }

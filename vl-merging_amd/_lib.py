@@ -344,6 +344,8 @@ SIGNATURES = {
     "vlm_sce_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
+    "vlm_gemm_bf16_live": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                   c_int, ctypes.POINTER(Epilogue), c_void_p, c_void_p]),
     "vlm_gemm_bf16_grouped": (c_int, [c_int, ctypes.POINTER(GemmGroup), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                       ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_wgrad_grouped": (c_int, [c_int, ctypes.POINTER(WgradGroup), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
@@ -353,6 +355,8 @@ SIGNATURES = {
     "vlm_attention_bwd_ws_floats": (c_size_t, [ctypes.POINTER(AttnDesc), c_int]),
     "vlm_attention_bwd": (c_int, [ctypes.POINTER(AttnDesc), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vlm_attention_bwd_live": (c_int, [ctypes.POINTER(AttnDesc), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vlm_layernorm_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int,
                                   c_void_p, c_void_p]),
     "vlm_layernorm_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,

@@ -29,7 +29,18 @@ struct attn_bwd_params_t {
   float* nstat;           // [2][H][rows]: -lse / c1 and -delta for the 16-wave bias-gradient kernel (written by the dQ kernel) or NULL
   float* dq_colsum[2];    // per segment (0 text rows, 1 image rows): [H*64] += column sums of dQ (q_bias grad) or NULL
   float* dv_colsum[2];    // same for dV (v_bias gradient)
+  const float* row_live;  // vlm_attention_bwd_live: f32 [rows] DropPath factors (0 = dead) or NULL
 };
+
+// vlm_attention_bwd_live: is (sample b, dense-table part) dead -- the factor of its segment's first row zero?  SEPARATE mode: the
+// part's own segment.  JOINT mode: the two segments of a sample share one draw and attend to each other, so both must say so.
+// Uniform wherever b is (the dQ stream's workgroup, a wave of the dK/dV kernel).
+__device__ __forceinline__ bool att_bwd_dead(const attn_bwd_params_t& bp, const att_pos_t& ps, int part, int b) {
+  if (!bp.row_live) return false;
+  const bool d0 = ps.n0 == 0 || bp.row_live[ps.base0 + b * ps.n0] == 0.0f;
+  const bool d1 = ps.n1 == 0 || bp.row_live[ps.base1 + b * ps.n1] == 0.0f;
+  return bp.f.mode == VLM_ATTN_SEPARATE ? (part ? d1 : d0) : (d0 && d1);
+}
 
 #include "attention_bwd_dkvb.h"
 #include "attention_bwd_dq2.h"
@@ -846,10 +857,11 @@ static void dkvb_launch(const attn_bwd_params_t& bp, const att_bwd_plan_t& pl, h
   hipLaunchKernelGGL((attn_bwd_dkvb_kernel<W>), dim3((unsigned)((pl.items + 7) / 8 * 8)), dim3(W * 64), pl.lds, s, bp, pl.groups, pl.panel_blocks);
 }
 
-extern "C" int vlm_attention_bwd(const vlm_attn_desc_t* d, const void* out, int ld_out, const void* d_out,
-                                 int ld_dout, const float* lse, float* delta_ws, size_t ws_floats, void* dqkv, int ld_dqkv,
-                                 float* dbias_t, const vlm_attn_colsum_t* colsum, void* stream) {
+static int attention_bwd(const vlm_attn_desc_t* d, const void* out, int ld_out, const void* d_out, int ld_dout, const float* lse,
+                         float* delta_ws, size_t ws_floats, void* dqkv, int ld_dqkv, float* dbias_t, const vlm_attn_colsum_t* colsum,
+                         const float* row_live, void* stream) {
   attn_bwd_params_t bp;
+  bp.row_live = row_live;
   int rc = att_fill_params(d, bp.f);
   if (rc != VLM_OK) return rc;
   if (!out || !d_out || !lse || !delta_ws || !dqkv) return VLM_ERR_ARG;
@@ -906,4 +918,19 @@ extern "C" int vlm_attention_bwd(const vlm_attn_desc_t* d, const void* out, int 
   }
   VLM_CHECK_LAUNCH();
   return VLM_OK;
+}
+
+extern "C" int vlm_attention_bwd(const vlm_attn_desc_t* d, const void* out, int ld_out, const void* d_out,
+                                 int ld_dout, const float* lse, float* delta_ws, size_t ws_floats, void* dqkv, int ld_dqkv,
+                                 float* dbias_t, const vlm_attn_colsum_t* colsum, void* stream) {
+  return attention_bwd(d, out, ld_out, d_out, ld_dout, lse, delta_ws, ws_floats, dqkv, ld_dqkv, dbias_t, colsum, nullptr, stream);
+}
+
+// vlm_attention_bwd plus the row vector of include/vlm_hip.h: the fused dK / dV / bias-gradient kernel and the dQ stream store
+// zeros for a dead (sample, segment) instead of recomputing it; the other kernels of the plan compute every sample as before.
+extern "C" int vlm_attention_bwd_live(const vlm_attn_desc_t* d, const void* out, int ld_out, const void* d_out,
+                                      int ld_dout, const float* lse, float* delta_ws, size_t ws_floats, void* dqkv, int ld_dqkv,
+                                      float* dbias_t, const vlm_attn_colsum_t* colsum, const float* row_live, void* stream) {
+  if (row_live && ((uintptr_t)row_live & 3)) return VLM_ERR_ARG;
+  return attention_bwd(d, out, ld_out, d_out, ld_dout, lse, delta_ws, ws_floats, dqkv, ld_dqkv, dbias_t, colsum, row_live, stream);
 }

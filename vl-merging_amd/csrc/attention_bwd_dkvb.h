@@ -140,7 +140,23 @@ __global__ __launch_bounds__(W * 64, 1) void attn_bwd_dkvb_kernel(const attn_bwd
   const int rounds = (b_hi - b_lo + wact - 1) / wact;
   for (int rd = 0; rd < rounds; ++rd) {
     const int b = b_lo + rd * wact + wave;
-    const bool active = wave < wact && b < b_hi;  // wave-uniform
+    bool active = wave < wact && b < b_hi;  // wave-uniform
+    // vlm_attention_bwd_live: the dO rows of a dead sample are zeros, and so are its dK / dV rows and its share of G.  The wave
+    // stores the zero rows here and now (the addresses of the store at the end of the round), adds nothing to the panel or the
+    // column sums, and spends the round as an idle wave does: it executes every barrier of the sample loop and never leaves or
+    // branches around one its workgroup still executes.
+    if (active && __builtin_amdgcn_readfirstlane((int)att_bwd_dead(bp, ps, part, b)) != 0) {  // (wave-uniform)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int kpi = kp0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const int row = kpi < s_hi ? att_row_of(ps, b, kpi) : -1;
+        if (row >= 0) {
+          bf16_t* dst = bp.dqkv + (size_t)row * bp.ld_dqkv + D + h * 64 + r;
+          dst[0] = dst[32] = dst[D] = dst[D + 32] = (bf16_t)0.f;
+        }
+      }
+      active = false;
+    }
 
     // ---- this wave's sample: K (scaled by scale * log2 e), V fragments of the 32 keys; the key side of the statistics k-step ----
     bf16x8 kf[4], vf[4], bstat;

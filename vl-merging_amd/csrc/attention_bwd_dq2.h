@@ -55,6 +55,30 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq2_kernel(const attn
   if (!att_work_item(att_num_tiles(ps.n0, ps.n1, ps.pos1, p.mode), ps.B, p.H, wtile, b, h)) return;
   const att_span_t sp = att_span(ps, p.mode, wtile);
   ATT_STAMP(0);
+  // vlm_attention_bwd_live: a workgroup belongs to ONE sample, so a dead sample is a whole-workgroup skip in front of the
+  // stream: zero dQ rows, and what the kernels after this one read from the prologue for these rows -- delta = rowsum(dO O) = 0
+  // (dO is zero there) and the bias-gradient kernel's C operands.  Nothing is added to the q_bias column sums.
+  if (att_bwd_dead(bp, ps, sp.part, b)) {  // (workgroup-uniform)
+    const int qpd = sp.p0 + wave * 32 + r;
+    const int rowd = qpd < sp.s_hi ? att_row_of(ps, b, qpd) : -1;
+    if (rowd >= 0) {
+      bf16_t* op = bp.dqkv + (size_t)rowd * bp.ld_dqkv + h * 64 + 4 * hh;
+      const bf16x4 z = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) *reinterpret_cast<bf16x4*>(op + db * 32 + 8 * g4) = z;
+      if (hh == 0) {
+        const size_t at = (size_t)h * p.total_rows + (size_t)rowd;
+        bp.delta[at] = 0.f;
+        if (bp.nstat) {
+          bp.nstat[at] = -bp.lse[at] * bp.inv_c1;
+          bp.nstat[(size_t)p.H * p.total_rows + at] = 0.f;
+        }
+      }
+    }
+    return;
+  }
   const int D = p.H * 64;
   const int ntiles = (sp.s_hi - sp.s_lo + ATT_BK - 1) / ATT_BK;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(att_lds_void*)lds;

@@ -181,6 +181,7 @@ struct gemm_params_t {
   int n_groups;                  // 256x256 kernel, GROUPED instantiations only
   gemm_group_t grp[VLM_GEMM_MAX_GROUPS];
   gemmT_group_t grpT[VLM_GEMM_MAX_GROUPS];  // wgrad kernel, GROUPED instantiation only
+  const float* row_live = nullptr;  // 256x256 kernel (vlm_gemm_bf16_live): f32 [M], a row is dead where its entry is 0
   VLM_DIAG_GEMM_FIELD  // empty in the product build (vlm_diag.h)
 };
 
@@ -945,6 +946,25 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_big_kernel(const gem
   }
   const gemm_params_t& p = GROUPED ? p_grp : p_in;
   GEMM_STAMP(0)
+  // row_live (vlm_gemm_bf16_live): are this workgroup's rows inside [0, M) ALL dead (entry == 0)?  Every wave asks for all 256
+  // values itself, four consecutive rows per lane (1 KiB: one 16-B load where the vector's address allows it, else four 4-B
+  // loads -- a site's factors are a row of the pass's table and start wherever that row starts; the ragged last tile reads row
+  // M - 1 in place of the rows past it, which is in this tile), and decides alone by a ballot: no LDS, no barrier.  The load goes out first and is
+  // looked at only after the prologue's first two stages are requested (BIG_DEAD_TILE below): waited for right here, with a
+  // workgroup reduction behind it, the check cost every tile a memory round trip -- as much as the skipped tiles gave back.
+  // (The residual variant that also stores the branch copy -- the unfolded LayerScale form -- computes every tile: with the
+  // branch in it hipcc's allocation passes the 248 VGPRs tests/test_build_cpu.py holds that variant to, wherever the branch stands.)
+  constexpr bool SKIPS = !(RES && AUX == 1);
+  f32x4 lv = {1.f, 1.f, 1.f, 1.f};
+  if (SKIPS && p.row_live) {
+    const uint32_t m = m0 + 4 * (uint32_t)lane;
+    if (m0 + BIG_BM <= (uint32_t)p.M && ((uintptr_t)p.row_live & 15) == 0) {  // (workgroup-uniform; m0 is a multiple of 256)
+      lv = *reinterpret_cast<const f32x4*>(p.row_live + m);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) lv[e] = p.row_live[min(m + e, (uint32_t)p.M - 1)];
+    }
+  }
   const uint32_t n0 = tn * BIG_BN;
   const __amdgpu_buffer_rsrc_t ra =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, (int)((uint64_t)p.M * p.lda * 2), 0x00020000);
@@ -1071,6 +1091,32 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void vlm_gemm_big_kernel(const gem
   // prologue (nk >= 4, nk even: launcher): stages 0, 1 in LDS, 2, 3 in flight to registers, fragments of stage 0 read
   BIG_GLOAD(ra0, rb0, 0)
   BIG_GLOAD(ra1, rb1, 1)
+  // A dead tile takes ONE scalar branch past the rest of the prologue, the K loop and the tail steps (the two stages already
+  // requested are dropped), and no output row is left unwritten: it writes epilogue(0) -- the epilogue's own arithmetic,
+  // block by block in the same order, on a 16-row block of +0 that stands in LDS for the accumulators a skipped K loop would
+  // have left at +0.  (A copy of the looped epilogue that names no accumulator: joining the two paths in front of ONE
+  // epilogue cost the live path 26 VGPRs and the residual variants 12-16 spilled registers, tests/test_build_cpu.py; this
+  // way the code after the branch is the kernel as it was.)  The bytes are those of the full computation on zero rows of A,
+  // column sums included.  DESIGN.md ("Row skipping") says why epilogue(0) and not nothing.
+  if (SKIPS && p.row_live && __builtin_amdgcn_ballot_w64(lv[0] != 0.0f || lv[1] != 0.0f || lv[2] != 0.0f || lv[3] != 0.0f) == 0) {
+    // (an opaque copy of the lane index: with the plain one hipcc hoists what this epilogue's setup shares with the live path's
+    // -- the bias and scale vectors -- above the branch and carries it through the K loop, 8-14 more VGPRs there)
+    int lane_d = lane;
+    asm volatile("" : "+v"(lane_d));
+    big_epilogue_t<OUT_F32, RES, AUX> ep(p, wl, mw0, nw0, lane_d);
+    unsigned char* const wz = wl + (lane_d & 15) * EPIL_PITCH + (lane_d >> 4) * 16;  // EPIL_DUMP_ROW's addresses
+#pragma unroll
+    for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(wz + 64 * j) = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int i = 0; i < 8; ++i) {
+      epil_in_t in;
+      ep.load_inputs(in, i);
+      ep.process(in, i, 0);
+    }
+    ep.finish(lane_d, (p.epi.col_sum_ws && mw0 + 128 <= (uint32_t)p.M) ? p.epi.col_sum_ws + ((size_t)(tm_ws * 2 + wm) * 2) * p.N : nullptr);
+    GEMM_STAMP_END()
+    return;
+  }
   BIG_LWRITE(ra0, rb0, sA0, sB0)
   BIG_GLOAD(ra0, rb0, 2)
   BIG_LWRITE(ra1, rb1, sA1, sB1)
@@ -1432,8 +1478,8 @@ extern "C" int vlm_gemm_set_big_tile_mode(int mode) {
 // 1024 cycles per K step); with staging and no MFMAs it takes as long as the full loop: what remains is the vector-memory
 // issue path (8 LDS-DMA instructions per wave and K step) overlapped only by the partner workgroup's MFMAs.
 
-extern "C" int vlm_gemm_bf16(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
-                             void* C, int ldc, int c_is_f32, const vlm_epilogue_t* epi, void* stream) {
+static int gemm_bf16(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
+                     int c_is_f32, const vlm_epilogue_t* epi, const float* row_live, void* stream) {
   if (M < 0 || N < 0 || K < 0 || !C) return VLM_ERR_ARG;
   if (M == 0 || N == 0) return VLM_OK;
   if (!A || !B || !epi) return VLM_ERR_ARG;
@@ -1500,8 +1546,10 @@ extern "C" int vlm_gemm_bf16(int ta, int tb, int M, int N, int K, const void* A,
     const bool ws_ok = (N % BIG_BN) == 0 && p.epi.reserved == 1 && epi_off32(epi, M, lda, ldc) && !epi->accumulate;
     // measured (tools/bench_gemm.py, M = 13 574 and 54 296): ahead of the 128x128 kernel from half a round of tiles up
     if (ws_ok && (gemm_big_mode() >= 2 || 2 * big_tiles >= plan_cus())) {
+      p.row_live = row_live;  // the 256x256 kernel alone looks at it
       const int rc = launch_gemm_big_variant<>(p, c_is_f32 != 0, s);
       if (rc <= 0) return rc;
+      p.row_live = nullptr;
     }
   }
 #ifdef GEMM_ONLY_BIG  // tools/scratch/gemm_bench.hip: skip the other instantiations (compile time)
@@ -1518,6 +1566,19 @@ extern "C" int vlm_gemm_bf16(int ta, int tb, int M, int N, int K, const void* A,
     case 6: return launch_gemm<true, true, false, false>(p, s);
     default: return launch_gemm<true, true, true, false>(p, s);
   }
+}
+
+extern "C" int vlm_gemm_bf16(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
+                             void* C, int ldc, int c_is_f32, const vlm_epilogue_t* epi, void* stream) {
+  return gemm_bf16(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, c_is_f32, epi, nullptr, stream);
+}
+
+// vlm_gemm_bf16 plus the row vector of include/vlm_hip.h: 256-row tiles of the 256x256 kernel whose rows are all dead skip their
+// K loop and write epilogue(0); calls the 128x128 kernel serves compute every row as before.
+extern "C" int vlm_gemm_bf16_live(int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
+                                  void* C, int ldc, int c_is_f32, const vlm_epilogue_t* epi, const float* row_live, void* stream) {
+  if (row_live && ((uintptr_t)row_live & 3)) return VLM_ERR_ARG;
+  return gemm_bf16(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, c_is_f32, epi, row_live, stream);
 }
 
 // Grouped call: the row ranges of `groups` (ascending, disjoint) of ONE activation matrix go through different weights

@@ -307,9 +307,26 @@ def wT16(p):
 # Grouped GEMM: with two row ranges (the modality experts of an all_moe block, the ufo layers before fusion) each of
 # the block's GEMMs is ONE launch over both ranges (ops.gemm_grouped): the text expert's 14 row tiles ride in the image expert's
 # rounds of 256x256 tiles instead of under-filling launches of their own (9.6 % of the all_moe step for 6.5 % of its rows).
-def _gemm_rows(a, groups, out, *, act=L.ACT_NONE, aux=None, col_scale=None, row_scale=None, residual=None, col_sum_fold=None):
+# DropPath's per-row factors (PassCtx.drop_path_rows) go to the block GEMMs of their site as `row_live`: a 256-row tile that lies
+# inside dropped samples skips its K loop (vlm_gemm_bf16_live; DESIGN.md, "Row skipping").  False: every row is computed (tests run both
+# ways in one process).
+_ROWSKIP = {"enabled": True}
+
+
+def _live(rs, plan, pc):
+    """The row vector a site's GEMMs and attention backward may skip by: the site's DropPath factors, unless the Gram cache is
+    being recorded (it reads the activations of every row) or joint attention mixes two draws (a live segment would then read the
+    keys of a dead one; no pass the model builds does that)."""
+    if not _ROWSKIP["enabled"] or pc.gram is not None or (pc.independent_segments and plan.mode == L.ATTN_JOINT):
+        return None
+    return rs
+
+
+def _gemm_rows(a, groups, out, *, act=L.ACT_NONE, aux=None, col_scale=None, row_scale=None, residual=None, col_sum_fold=None,
+               row_live=None):
     """out[r0:r1] = epilogue(a[r0:r1] @ w^T) over a plan's row ranges, groups (r0, r1, w, bias, col_sum) as in
-    ops.gemm_grouped: one range is an ops.gemm on the row slices, more are one grouped launch."""
+    ops.gemm_grouped: one range is an ops.gemm on the row slices, more are one grouped launch (which computes every row:
+    row_live reaches the single-range call only)."""
     if len(groups) > 1:
         return ops.gemm_grouped(a, groups, out, act=act, aux=aux, col_scale=col_scale, row_scale=row_scale,
                                 residual=residual, col_sum_fold=col_sum_fold)
@@ -319,7 +336,8 @@ def _gemm_rows(a, groups, out, *, act=L.ACT_NONE, aux=None, col_scale=None, row_
         return t[r0:r1] if t is not None else None
 
     return ops.gemm(a[r0:r1], w, out[r0:r1], bias=bias, act=act, aux=rows(aux), col_scale=col_scale,
-                    row_scale=rows(row_scale), residual=rows(residual), col_sum=col_sum, col_sum_fold=col_sum_fold)
+                    row_scale=rows(row_scale), residual=rows(residual), col_sum=col_sum, col_sum_fold=col_sum_fold,
+                    row_live=rows(row_live))
 
 
 def _wgrad_rows(dy, x, groups):
@@ -695,10 +713,12 @@ class _BlockFn(torch.autograd.Function):
         qkv = torch.empty(M, 3 * D, device=dev, dtype=BF16)
         rs1 = pc.drop_path_rows(plan.drop_prob, training, dev)
         rs2 = pc.drop_path_rows(plan.drop_prob, training, dev)
+        live1, live2 = _live(rs1, plan, pc), _live(rs2, plan, pc)
         rg = plan.ranges
         for r0, r1, e in rg:
             ops.layernorm_fwd(x[r0:r1], e.n1w, e.n1b, plan.eps, ln1[r0:r1], st1[r0:r1])
-        _gemm_rows(ln1, [(r0, r1, w16(e.qkvw), _qkv_bias(e), None) for r0, r1, e in rg], qkv)
+        # live1 / live2 tell their site's GEMMs which rows DropPath has zeroed: nothing the step returns depends on them
+        _gemm_rows(ln1, [(r0, r1, w16(e.qkvw), _qkv_bias(e), None) for r0, r1, e in rg], qkv, row_live=live1)
         o = torch.empty(M, D, device=dev, dtype=BF16)
         lse = torch.empty(H, M, device=dev, dtype=F32)
         rp = pc.relpos
@@ -720,14 +740,15 @@ class _BlockFn(torch.autograd.Function):
         pb = (lambda e: _fb(e.projb)) if folded else (lambda e: e.projb)
         fb2 = (lambda e: _fb(e.fc2b)) if folded else (lambda e: e.fc2b)
         _gemm_rows(o, [(r0, r1, w16(e.projw), pb(e), None) for r0, r1, e in rg], x1, col_scale=cs1, row_scale=rs1,
-                   residual=x, aux=y1)
+                   residual=x, aux=y1, row_live=live1)
         for r0, r1, e in rg:
             ops.layernorm_fwd(x1[r0:r1], e.n2w, e.n2b, plan.eps, ln2[r0:r1], st2[r0:r1])
         # h = gelu'(pre-activation): the forward epilogue has erf and exp in hand anyway, and the fc2-dgrad epilogue of the
         # backward pass becomes a multiplication
-        _gemm_rows(ln2, [(r0, r1, w16(e.fc1w), e.fc1b, None) for r0, r1, e in rg], a, act=L.ACT_GELU_DERIV, aux=h)
+        _gemm_rows(ln2, [(r0, r1, w16(e.fc1w), e.fc1b, None) for r0, r1, e in rg], a, act=L.ACT_GELU_DERIV, aux=h,
+                   row_live=live2)
         _gemm_rows(a, [(r0, r1, w16(e.fc2w), fb2(e), None) for r0, r1, e in rg], x2, col_scale=cs2, row_scale=rs2,
-                   residual=x1, aux=y2)
+                   residual=x1, aux=y2, row_live=live2)
         if pc.gram is not None:
             # Gram cache: the LayerNorm outputs enter in fp32 (re-computed here, capture runs are not timed), like the
             # fp32 activations the reference's hooks see; the attention output and the GELU output exist only as the bf16
@@ -760,6 +781,7 @@ class _BlockFn(torch.autograd.Function):
         x, st1, ln1, qkv, o, lse, y1, x1, st2, ln2, h, a, y2, rs1, rs2, bias_t = ctx.saved_tensors
         rs1 = rs1 if rs1.numel() else None
         rs2 = rs2 if rs2.numel() else None
+        live1, live2 = _live(rs1, plan, pc), _live(rs2, plan, pc)
         bias_t = bias_t if ctx.has_bias else None
         M, D = x.shape
         dev = x.device
@@ -799,7 +821,7 @@ class _BlockFn(torch.autograd.Function):
         # fc1 bias gradient = column sums of dh: per-tile sums from the epilogue that produces dh, folded with the block's
         # other column partials (no atomics, no second pass over dh)
         _gemm_rows(dy2, [(r0, r1, wT16(e.fc2w), None, e.fc1b.grad) for r0, r1, e in rg], dh, act=L.ACT_MUL_AUX, aux=h,
-                   col_sum_fold=fold)
+                   col_sum_fold=fold, row_live=live2)
         # side stream, one row range: the block's four weight gradients leave as ONE batched launch after the attention backward
         batch = wgrad_stream() is not None and len(rg) == 1 and ops.wgrad_batch_serves(
             rg[0][1] - rg[0][0], [(D, Fdim), (Fdim, D), (D, D), (3 * D, D)])
@@ -807,12 +829,12 @@ class _BlockFn(torch.autograd.Function):
             with _Side(dy2, a, dh, ln2):
                 _wgrad_rows(dy2, a, [(r0, r1, wg(e.fc2w)) for r0, r1, e in rg])
                 _wgrad_rows(dh, ln2, [(r0, r1, e.fc1w.grad) for r0, r1, e in rg])
-        _gemm_rows(dh, [(r0, r1, wT16(e.fc1w), None, None) for r0, r1, e in rg], dln)
+        _gemm_rows(dh, [(r0, r1, wT16(e.fc1w), None, None) for r0, r1, e in rg], dln, row_live=live2)
         for r0, r1, e in rg:
             rr = slice(r0, r1)
             _ln2_bwd_scale1(dln[rr], x1[rr], st2[rr], e, dx1[rr], dx2[rr], y1[rr] if y1 is not None else None, g1,
                             rs1[rr] if rs1 is not None else None, dy1[rr], fold)
-        _gemm_rows(dy1, [(r0, r1, wT16(e.projw), None, None) for r0, r1, e in rg], do)
+        _gemm_rows(dy1, [(r0, r1, wT16(e.projw), None, None) for r0, r1, e in rg], do, row_live=live1)
         if not batch:
             with _Side(dy1, o):
                 _wgrad_rows(dy1, o, [(r0, r1, wg(e.projw)) for r0, r1, e in rg])
@@ -827,7 +849,7 @@ class _BlockFn(torch.autograd.Function):
                           rel_index_t=rp.index_t if rp is not None else None, keep0=pc.keep0, keep1=pc.keep1,
                           mode=plan.mode, dbias_t=rp.holder.get("dbias_t") if rp is not None else None,
                           dq_colsum=qb_grads, dv_colsum=vb_grads,
-                          bias_dense=rp.dense_for(pc.seq, plan.mode) if rp is not None else None)
+                          bias_dense=rp.dense_for(pc.seq, plan.mode) if rp is not None else None, row_live=live1)
         dx = torch.empty(M, D, device=dev, dtype=F32)
         for r0, r1, e in rg:
             if e.qb is not None and not fused_qv:
@@ -842,7 +864,7 @@ class _BlockFn(torch.autograd.Function):
         else:
             with _Side(dqkv, ln1):
                 _wgrad_rows(dqkv, ln1, [(r0, r1, e.qkvw.grad) for r0, r1, e in rg])
-        _gemm_rows(dqkv, [(r0, r1, wT16(e.qkvw), None, None) for r0, r1, e in rg], dln1)
+        _gemm_rows(dqkv, [(r0, r1, wT16(e.qkvw), None, None) for r0, r1, e in rg], dln1, row_live=live1)
         for r0, r1, e in rg:
             rr = slice(r0, r1)
             ops.layernorm_bwd(dln1[rr], x[rr], st1[rr], e.n1w, dx[rr], dres=dx1[rr], dgamma=e.n1w.grad, dbeta=e.n1b.grad,

@@ -64,12 +64,14 @@ def _epilogue(N, *, bias=None, col_scale=None, row_scale=None, residual=None, au
 
 
 def gemm(a, b, out, ta=False, tb=False, *, bias=None, act=L.ACT_NONE, aux=None, col_scale=None, row_scale=None,
-         residual=None, alpha=1.0, accumulate=False, col_sum=None, col_sum_fold=None):
+         residual=None, alpha=1.0, accumulate=False, col_sum=None, col_sum_fold=None, row_live=None):
     """out[M,N] = epilogue(op(a)[M,K] @ op(b)[K,N]); see include/vlm_hip.h for the epilogue algebra.
 
     a: bf16 [M,K] (ta=False) or [K,M] (ta=True);  b: bf16 [N,K] (tb=False, nn.Linear layout) or [K,N] (tb=True).
+    row_live: f32 [M], a row is dead where it is 0 (vlm_gemm_bf16_live): 256-row tiles of dead rows skip their K loop and hold
+    epilogue(0).
     """
-    L.require_cuda(a, b, out, bias, aux, col_scale, row_scale, residual, col_sum)
+    L.require_cuda(a, b, out, bias, aux, col_scale, row_scale, residual, col_sum, row_live)
     if a.dtype != BF16 or b.dtype != BF16:
         raise L.VlmError("gemm operands must be bfloat16")
     M, N = out.shape
@@ -96,8 +98,14 @@ def gemm(a, b, out, ta=False, tb=False, *, bias=None, act=L.ACT_NONE, aux=None, 
         e.splitk_ws_bytes = ws.numel() * 4
     if out.dtype not in (BF16, F32):
         raise L.VlmError("gemm output must be bf16 or f32")
-    rc = L.get_lib().vlm_gemm_bf16(int(ta), int(tb), M, N, K, L.ptr(a), _ld(a), L.ptr(b), _ld(b), L.ptr(out), _ld(out),
-                                   int(out.dtype == F32), ctypes.byref(e), L.stream_ptr())
+    if row_live is not None:
+        if row_live.dtype != F32 or row_live.dim() != 1 or row_live.shape[0] != M or row_live.stride(0) != 1:
+            raise L.VlmError("gemm: row_live must be a dense f32 vector of M=%d elements" % M)
+        rc = L.get_lib().vlm_gemm_bf16_live(int(ta), int(tb), M, N, K, L.ptr(a), _ld(a), L.ptr(b), _ld(b), L.ptr(out), _ld(out),
+                                            int(out.dtype == F32), ctypes.byref(e), L.ptr(row_live), L.stream_ptr())
+    else:
+        rc = L.get_lib().vlm_gemm_bf16(int(ta), int(tb), M, N, K, L.ptr(a), _ld(a), L.ptr(b), _ld(b), L.ptr(out), _ld(out),
+                                       int(out.dtype == F32), ctypes.byref(e), L.stream_ptr())
     L.check(rc, "vlm_gemm_bf16")
     if region is not None:
         col_sum_fold.add(region, M // 128, N, col_sum, None)
@@ -959,10 +967,12 @@ _ATTN_WS = {}
 
 def attention_bwd(qkv, out, dout, lse, dqkv, seq, H, *, bias_t=None, head_row0=0, rel_index=None, rel_index_t=None,
                   keep0=None, keep1=None, mode=L.ATTN_JOINT, scale=0.125, dbias_t=None, delta_ws=None,
-                  dq_colsum=None, dv_colsum=None, bias_dense=None):
+                  dq_colsum=None, dv_colsum=None, bias_dense=None, row_live=None):
     """dqkv <- d(loss)/d(qkv) (bf16, same layout as qkv); dbias_t += d(loss)/d(bias_t).  dq_colsum / dv_colsum:
     optional pairs (text-segment target, image-segment target) of f32 [H*64] vectors (None entries allowed) that
-    receive += column sums of dQ / dV over that segment's rows (the q_bias / v_bias gradients)."""
+    receive += column sums of dQ / dV over that segment's rows (the q_bias / v_bias gradients).
+    row_live: f32 [rows] DropPath factors; a (sample, segment) whose first row is 0 has zero dout rows and gets zero dqkv rows
+    without being recomputed (vlm_attention_bwd_live)."""
     d = _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, keep1, mode, scale, bias_dense)
     L.require_cuda(out, dout, lse, dqkv, dbias_t, delta_ws)
     cs = None
@@ -983,9 +993,15 @@ def attention_bwd(qkv, out, dout, lse, dqkv, seq, H, *, bias_t=None, head_row0=0
             delta_ws = _ATTN_WS[key] = torch.empty(need, device=qkv.device, dtype=F32)
     if bias_t is not None and rel_index is None:
         raise L.VlmError("attention_bwd needs both orientations of the int16 relative index")
-    rc = L.get_lib().vlm_attention_bwd(ctypes.byref(d), L.ptr(out), _ld(out), L.ptr(dout), _ld(dout), L.ptr(lse),
-                                       L.ptr(delta_ws), delta_ws.numel(), L.ptr(dqkv), _ld(dqkv), L.ptr(dbias_t),
-                                       ctypes.byref(cs) if cs is not None else None, L.stream_ptr())
+    args = (ctypes.byref(d), L.ptr(out), _ld(out), L.ptr(dout), _ld(dout), L.ptr(lse), L.ptr(delta_ws), delta_ws.numel(),
+            L.ptr(dqkv), _ld(dqkv), L.ptr(dbias_t), ctypes.byref(cs) if cs is not None else None)
+    if row_live is not None:
+        L.require_cuda(row_live)
+        if row_live.dtype != F32 or row_live.dim() != 1 or row_live.shape[0] < qkv.shape[0] or row_live.stride(0) != 1:
+            raise L.VlmError("attention_bwd: row_live must be a dense f32 vector over the rows of qkv")
+        rc = L.get_lib().vlm_attention_bwd_live(*args, L.ptr(row_live), L.stream_ptr())
+    else:
+        rc = L.get_lib().vlm_attention_bwd(*args, L.stream_ptr())
     L.check(rc, "vlm_attention_bwd")
     return dqkv
 

@@ -585,6 +585,124 @@ int vlm_sce_plan_upload(const vlm_sce_job_t* jobs_host, int n_jobs, void* worksp
 int vlm_sce_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Spherical merge: SLERP for two sources, the weighted Karcher (Riemannian) mean of the directions for more (mergekit's
+ * `nuslerp` with its `row_wise` option, `karcher`, `multislerp`), csrc/sphere.hip.  NO REFERENCE SITE: the reference has no such
+ * merge; the arithmetic below is the specification and is pinned to a restatement of it in numpy and python doubles
+ * (tests/sphere_restatement.py), not to the reference.  One job = one output tensor with sources W_0 .. W_{S-1} (1 <= S <=
+ * VLM_MERGE_MAX_SRC), an optional central tensor c (base, may be NULL), weights w[m] >= 0 (doubles, not all zero), lam (fp32) and
+ * row_len: 0 = the GROUP is the whole tensor, otherwise 1 <= row_len <= VLM_DELLA_MAX_ROW divides n_elem and a group is a row.
+ * The coefficients are one scalar per source and per group.  fp32 and f64 operations round once, no FMA; "f64" = the operand
+ * widened exactly and the operation done in double:
+ *   1. x_m = W_m - c (fp32);  x_m = W_m without a base
+ *   2. per group:  sq[m] = sum f64(x_m) * f64(x_m);  per pair (a, b), a < b < S, in slot b (b - 1) / 2 + a:
+ *      dot[p] = sum f64(x_a) * f64(x_b).
+ *      Tensor groups: step 2 of the Model Stock rule above, order of summation included (csrc/gram_reduce.h serves both): sq and
+ *      dot are the bytes vlm_stock_run leaves for the same inputs.
+ *      Row groups: lane l of 64 adds the products of the row's elements l, l + 64, l + 128, ... in rising order, from +0.0; the 64
+ *      lane sums are folded by halves (l + 32 into l, then 16, 8, 4, 2, 1).  The order depends on row_len alone.
+ *   3. per group, in f64, in the order written; ITERS = 24, EDGE = 2^-20, QMIN = 2^-40; acos, sin, cos are the device library's
+ *      f64 functions, everything else is one correctly rounded operation:
+ *        ws = ((+0.0 + w[m0]) + w[m1]) + ... over the m with sq[m] > 0, in source order
+ *        if not ws > 0:  status = ZERO;  coef64[:] = +0.0;  rho = resid = +0.0;  done
+ *        ww[m] = sq[m] > 0 ? w[m] / ws : +0.0;   n[m] = sqrt(sq[m])
+ *        C[i][i] = 1;  C[i][j] = (ww[i] > 0 and ww[j] > 0) ? dot[slot(i, j)] / (n[i] * n[j]) : +0.0
+ *        nrm2(v):  t = +0.0;  for i: for j:  t = t + (v[i] * v[j]) * C[i][j]          (i, j over 0 .. S-1, i outer)
+ *        rho = ((+0.0 + ww[0] * n[0]) + ww[1] * n[1]) + ...
+ *        a = ww;  q = nrm2(a)
+ *        if not q > QMIN:  status = LINEAR;  coef64[m] = ww[m];  resid = +0.0;  done       (antipodal: plain interpolation)
+ *        r = sqrt(q);  a[j] = a[j] / r;  vn = +0.0
+ *        repeat ITERS times (no tolerance test: the count is part of the rule):
+ *          v[:] = +0.0
+ *          for i with ww[i] > 0, in order:
+ *            ci = ((+0.0 + a[0] * C[0][i]) + a[1] * C[1][i]) + ...
+ *            k = 1 if ci >= 1 - EDGE;  k = 0 if ci <= -1 + EDGE;  else th = acos(ci), k = th / sin(th)
+ *            for j:  v[j] = v[j] + (ww[i] * k) * ((j == i ? 1.0 : +0.0) - ci * a[j])
+ *          q = nrm2(v);  if not q > 0: vn = +0.0, break            (the step has vanished)
+ *          vn = sqrt(q);  cv = cos(vn);  sv = sin(vn) / vn (the library's sincos);  b[j] = cv * a[j] + sv * v[j]
+ *          q2 = nrm2(b);  if not q2 > QMIN: break
+ *          r = sqrt(q2);  a[j] = b[j] / r
+ *        status = OK;  coef64[m] = ww[m] > 0 ? (rho * a[m]) / n[m] : +0.0;  resid = vn (the size of the last step)
+ *        coef32[m] = f32(coef64[m])     (one rounding)
+ *   4. per element, fp32:  d = +0.0;  for m in order: d = d + coef32[m] * x_m (multiply, then add);
+ *      dst = c + lam * d with a base;  dst = d without one (then lam must be 1.0).
+ * This is the weighted Karcher mean of the unit vectors x_m / |x_m|, iterated in the coordinates of the sources themselves (so it
+ * needs the S x S Gram matrix and no second reduction), scaled by the weighted mean rho of the norms.  For S = 2 and
+ * w = (1 - t, t) it is SLERP(t) of the directions with the norm interpolated linearly: mergekit's `nuslerp`.  mergekit's plain
+ * `slerp` does NOT renormalise (it interpolates the unnormalised tensors with the angle's weights); that form is not offered.
+ * An exactly opposite pair with equal weights takes LINEAR; with unequal weights the iteration converges to the heavier side.
+ * Inputs without a unique mean (more directions than dimensions, say) stay finite and deterministic but are sensitive to the last
+ * bits of acos / sin / cos.  Non-finite inputs are outside the contract.
+ * Per job after a run, vlm_sphere_result_t.  A tensor job fills sq, dot, coef64, coef32, rho, resid and status; a row job leaves
+ * those zero and fills the row counters: rows_linear and rows_zero (integer atomics) and resid_max (the maximum of non-negative
+ * doubles, taken as an integer maximum of their bits: order-free).  coef_out, where given, receives coef32 of every group
+ * (float [n_groups][VLM_MERGE_MAX_SRC], slots past S zero; n_groups = 1 for a tensor job).
+ * A run leaves the same bytes whatever the grid, the job's place in a plan or the number of runs.  dst must not overlap base or
+ * a source of its own job; coef_out must meet none of the job's tensors (overlap ACROSS jobs is the caller's to avoid).
+ */
+#define VLM_SPHERE_OK 0
+#define VLM_SPHERE_LINEAR 1
+#define VLM_SPHERE_ZERO 2
+#define VLM_SPHERE_ITERS 24
+
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c, or NULL */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each */
+  void* coef_out;                       /* device f32 [n_groups][VLM_MERGE_MAX_SRC], 16-byte aligned, or NULL */
+  double w[VLM_MERGE_MAX_SRC];          /* step 3: the weights, >= 0, finite, not all zero */
+  uint64_t n_elem;
+  uint32_t row_len;                     /* 0: one group, the tensor; else 1 .. VLM_DELLA_MAX_ROW, divides n_elem: a group is a row */
+  int32_t n_src;
+  float lam;                            /* step 4; 1.0 without a base */
+  uint32_t reserved;
+} vlm_sphere_job_t;
+
+/* The workspace of a spherical plan BEGINS with this header (byte offsets from its start); jobs keep their upload order.  Tensor
+ * jobs own the chunks, row jobs the tiles: first[i] == first[i + 1] for a row job. */
+typedef struct {
+  uint64_t n_jobs, n_chunks, n_tiles;
+  uint64_t jobs_off;      /* vlm_sphere_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table of the tensor jobs */
+  uint64_t tiles_off;     /* {uint32 job, uint32 first row} [n_tiles]: the row jobs' tiles, as many whole rows as fit in 4096 elements */
+  uint64_t first_off;     /* uint64 [n_jobs + 1]: the first chunk of each job, then n_chunks */
+  uint64_t records_off;   /* double [n_chunks][10]: one record per chunk, sq[4] then dot[6], overwritten by every run */
+  uint64_t results_off;   /* vlm_sphere_result_t [n_jobs]: overwritten by every run */
+} vlm_sphere_header_t;
+
+/* per job after a run; slots of sources and pairs a job does not have are zero */
+typedef struct {
+  double sq[VLM_MERGE_MAX_SRC];         /* step 2 (tensor job) */
+  double dot[6];
+  double coef64[VLM_MERGE_MAX_SRC];     /* step 3 (tensor job) */
+  double rho;
+  double resid;
+  float coef32[VLM_MERGE_MAX_SRC];      /* what step 4 multiplies by */
+  uint32_t status;                      /* VLM_SPHERE_OK | _LINEAR | _ZERO (tensor job; a row job: OK) */
+  uint32_t reserved;
+  uint64_t rows_linear;                 /* row job: rows whose status is LINEAR */
+  uint64_t rows_zero;                   /* row job: rows whose status is ZERO */
+  double resid_max;                     /* row job: the largest resid of its rows */
+} vlm_sphere_result_t;
+
+/* Bytes of device workspace a spherical plan for n_jobs jobs over total_elems elements needs (header, jobs, chunk and tile
+ * tables, first-chunk table, one record per chunk, one result per job).  No reference site. */
+size_t vlm_sphere_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (the checks of vlm_stock_plan_upload, but base may be NULL; coef_out NULL or 16-byte aligned and meeting none of
+ * the job's tensors; every w[m], m < n_src, finite and >= 0 and not all of them zero; row_len == 0, or n_elem % row_len == 0 with
+ * 1 <= row_len <= VLM_DELLA_MAX_ROW; lam == 1 without a base; else VLM_ERR_ARG; a length, chunk, tile or row count past 32 bits
+ * is VLM_ERR_UNSUPPORTED), build both tables on the host and copy header + jobs + tables into `workspace` (16-byte aligned;
+ * VLM_ERR_WORKSPACE if it is too small).  SYNCHRONISES `stream` before it returns (pageable temporary source); it is the last
+ * host synchronisation of a plan.  Implements no step of the rule; no reference site. */
+int vlm_sphere_plan_upload(const vlm_sphere_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: four launches, stream-ordered, and nothing else -- for the tensor jobs Model Stock's three (the reducer,
+ * steps 1-2; the fold, a job's records in chunk order, then step 3 by one lane: the whole result -- it also zeroes the row jobs'
+ * results; the apply pass, steps 1 and 4 with coef32 read from the job's result), for the row jobs ONE launch over their tiles
+ * (steps 1-4: a tile's inputs are read from memory once, its task vectors are kept in LDS for steps 2 and 4, step 3 runs one row per
+ * lane); no host synchronisation.  May be called again on the same workspace and gives the same bytes.  One run at a time per
+ * workspace.  No reference site. */
+int vlm_sphere_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

@@ -230,6 +230,40 @@ class SceResult(ctypes.Structure):
                 ("tot", ctypes.c_double), ("w", c_float * MERGE_MAX_SRC)]
 
 
+SPHERE_OK, SPHERE_LINEAR, SPHERE_ZERO = 0, 1, 2  # VLM_SPHERE_*: the status of a group's step 3
+SPHERE_ITERS = 24                                # VLM_SPHERE_ITERS
+
+
+class SphereJob(ctypes.Structure):
+    """vlm_sphere_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("coef_out", c_void_p),
+        ("w", ctypes.c_double * MERGE_MAX_SRC),
+        ("n_elem", c_u64),
+        ("row_len", ctypes.c_uint32),
+        ("n_src", ctypes.c_int32),
+        ("lam", c_float),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class SphereHeader(ctypes.Structure):
+    """vlm_sphere_header_t: the first bytes of a spherical plan's workspace."""
+    _fields_ = [(n, c_u64) for n in ("n_jobs", "n_chunks", "n_tiles", "jobs_off", "chunks_off", "tiles_off", "first_off",
+                                     "records_off", "results_off")]
+
+
+class SphereResult(ctypes.Structure):
+    """vlm_sphere_result_t: the sums, the coefficients and the status of a tensor job; the row counters of a row job."""
+    _fields_ = [("sq", ctypes.c_double * MERGE_MAX_SRC), ("dot", ctypes.c_double * PAIRSTATS_PAIRS),
+                ("coef64", ctypes.c_double * MERGE_MAX_SRC), ("rho", ctypes.c_double), ("resid", ctypes.c_double),
+                ("coef32", c_float * MERGE_MAX_SRC), ("status", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("rows_linear", c_u64), ("rows_zero", c_u64), ("resid_max", ctypes.c_double)]
+
+
 class ScatterSrc(ctypes.Structure):
     """vlm_scatter_src_t of include/vlm_hip.h."""
     _fields_ = [("g", c_void_p), ("g_is_f32", ctypes.c_int32), ("ld", ctypes.c_int32), ("first_row", ctypes.c_int32),
@@ -342,6 +376,9 @@ SIGNATURES = {
     "vlm_sce_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_sce_plan_upload": (c_int, [ctypes.POINTER(SceJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_sce_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_sphere_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_sphere_plan_upload": (c_int, [ctypes.POINTER(SphereJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_sphere_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_bf16_live": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,

@@ -16,24 +16,19 @@
 //                            result, steps 1 and 4 per element, 16-B non-temporal loads and stores.
 // Three launches, ordered by the stream alone.  No atomics; every record and every result is overwritten by each run, so nothing
 // is cleared.  -ffp-contract=off and the __f*_rn / __d*_rn forms: one rounding per operation, no FMA.
-// This file holds the rules and the workspace layout; the walker, the run loop and the host checks are chunk_walk.h's and
-// chunk_plan.h's, as in dare.hip and pairstats.hip.
+// This file holds step 3, the apply rule and the workspace layout; the reducer's rule, its wave and workgroup folds and the fold
+// of a job's records are gram_reduce.h's (sphere.hip reduces with them too); the walker, the run loop and the host checks are
+// chunk_walk.h's and chunk_plan.h's, as in dare.hip and pairstats.hip.
 #include "vlm_common.h"
 #include "chunk_walk.h"
+#include "gram_reduce.h"
 
-#define STOCK_THREADS CHUNK_THREADS
-#define STOCK_WAVES (STOCK_THREADS / 64)
-#define STOCK_PAIRS VLM_PAIRSTATS_PAIRS
-#define STOCK_SUMS VLM_STOCK_SUMS      // a record: sq[4], then dot[6]
-#define STOCK_FOLD_THREADS 64          // lanes 0 .. 9 add one sum each; lane 0 then does step 3
-#define STOCK_FOLD_BATCH 16            // records whose loads are in flight together in the fold (the additions stay in order)
 // Workgroups per CU of the reducer's grid (132 registers: three are resident, tests/test_stock_cpu.py watches the occupancy; forcing
 // 128 for a fourth spills): measured at 8, 12, 16 and 24, docs/experiments.md, "Model Stock".
 #define STOCK_REDUCE_BLOCKS_PER_CU 12
 // The apply pass's: DARE's 12 per CU was timed against 24, 48 and 96; 96 (vlm_merge_kernel's value) is 5 % of a run faster.
 #define STOCK_APPLY_BLOCKS_PER_CU 96
 
-static_assert(STOCK_PAIRS == VLM_MERGE_MAX_SRC * (VLM_MERGE_MAX_SRC - 1) / 2, "one slot per pair");
 static_assert(STOCK_SUMS == 10 && sizeof(vlm_stock_result_t) == (STOCK_SUMS + STOCK_PAIRS + 2) * 8 + 8,
               "a result is the ten sums, six cosines, cos, t, scale and four reserved bytes");
 static_assert(offsetof(vlm_stock_result_t, dot) == VLM_MERGE_MAX_SRC * 8, "a result begins as a record does");
@@ -58,77 +53,6 @@ __device__ __forceinline__ stock_view_t stock_view(unsigned char* ws) {
   return v;
 }
 
-// A thread's sums over one chunk, for a job of S sources: NP = S (S - 1) / 2 pairs, pair (a, b) at b (b - 1) / 2 + a < NP.
-template <int S>
-struct stock_acc_t {
-  static constexpr int NP = S * (S - 1) / 2;
-  static constexpr int NPA = NP > 0 ? NP : 1;
-  double sq[S], dot[NPA];
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int m = 0; m < S; ++m) sq[m] = 0.0;
-#pragma unroll
-    for (int p = 0; p < NPA; ++p) dot[p] = 0.0;
-  }
-};
-
-// Steps 1-2 as chunk_stream's rule: elem() adds one element to the thread's sums and returns nothing worth storing.
-template <int S>
-struct stock_reduce_rule {
-  stock_acc_t<S>& n;
-  __device__ __forceinline__ chunk_no_prep prep(uint64_t) const { return {}; }
-  __device__ __forceinline__ float elem(const chunk_no_prep&, int, float c, const float* wv) const {
-    double xd[S];
-#pragma unroll
-    for (int m = 0; m < S; ++m) {
-      xd[m] = (double)__fsub_rn(wv[m], c);                                         // step 1
-      n.sq[m] = __dadd_rn(n.sq[m], __dmul_rn(xd[m], xd[m]));                       // step 2
-    }
-#pragma unroll
-    for (int b = 1; b < S; ++b) {
-#pragma unroll
-      for (int a = 0; a < b; ++a) {
-        const int p = b * (b - 1) / 2 + a;
-        n.dot[p] = __dadd_rn(n.dot[p], __dmul_rn(xd[a], xd[b]));
-      }
-    }
-    return 0.0f;
-  }
-};
-
-// the wave fold by halves: lane 0 ends with the pinned tree's value (a + b is commutative, so the butterfly's lane 0 is the tree's)
-__device__ __forceinline__ double stock_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// does a job of S sources have the sum at `slot` (0 .. STOCK_SUMS)?
-__device__ __forceinline__ bool stock_slot_used(int slot, int S) {
-  return slot < VLM_MERGE_MAX_SRC ? slot < S : slot - VLM_MERGE_MAX_SRC < S * (S - 1) / 2;
-}
-
-// one chunk's sums, then their wave sums into red[wave][slot] (lane 0 writes; the slots are a record's order)
-template <int S>
-__device__ __forceinline__ void stock_chunk(const vlm_stock_job_t& j, uint64_t start4, double* red) {
-  stock_acc_t<S> n;
-  n.clear();
-  stock_reduce_rule<S> rule{n};
-  chunk_stream<S, true, false>(j, start4, rule);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double* r = red + wave * STOCK_SUMS;
-#pragma unroll
-  for (int m = 0; m < S; ++m) {
-    const double v = stock_wave_sum(n.sq[m]);
-    if (lane == 0) r[m] = v;
-  }
-#pragma unroll
-  for (int p = 0; p < stock_acc_t<S>::NP; ++p) {
-    const double v = stock_wave_sum(n.dot[p]);
-    if (lane == 0) r[VLM_MERGE_MAX_SRC + p] = v;
-  }
-}
-
 __global__ __launch_bounds__(STOCK_THREADS) void vlm_stock_reduce_kernel(unsigned char* __restrict__ ws) {
   // two buffers, used in turn: a chunk's wave sums are read behind ONE barrier while the next chunk's are written to the other
   __shared__ double red[2][STOCK_WAVES * STOCK_SUMS];
@@ -143,16 +67,7 @@ __global__ __launch_bounds__(STOCK_THREADS) void vlm_stock_reduce_kernel(unsigne
         double* r = red[turn];
         with_nsrc(j.n_src, [&](auto S) { stock_chunk<S()>(j, start4, r); });
         __syncthreads();
-        if (threadIdx.x < STOCK_SUMS) {  // ((w0 + w1) + w2) + w3; the sums the job does not have are zero
-          const int k = threadIdx.x;
-          double t = 0.0;
-          if (stock_slot_used(k, j.n_src)) {
-            t = r[k];
-#pragma unroll
-            for (int wv = 1; wv < STOCK_WAVES; ++wv) t = __dadd_rn(t, r[wv * STOCK_SUMS + k]);
-          }
-          w.records[(first + (start4 / (CHUNK_FLOATS / 4))) * STOCK_SUMS + k] = t;  // the record index is the chunk index
-        }
+        stock_record(r, j.n_src, w.records, first, start4);  // ((w0 + w1) + w2) + w3 per sum, at the chunk's index
         turn ^= 1;
       },
       [&](uint32_t) {});
@@ -202,13 +117,7 @@ __global__ __launch_bounds__(STOCK_FOLD_THREADS) void vlm_stock_fold_kernel(unsi
       const double* rec = w.records + k;
       const uint64_t c0 = w.first[job], c1 = w.first[job + 1];
       double sum = 0.0;
-      for (uint64_t c = c0; c < c1; c += STOCK_FOLD_BATCH) {
-        double v[STOCK_FOLD_BATCH];
-#pragma unroll
-        for (int i = 0; i < STOCK_FOLD_BATCH; ++i) v[i] = c + i < c1 ? rec[(c + i) * STOCK_SUMS] : 0.0;  // +0.0: changes no sum
-#pragma unroll
-        for (int i = 0; i < STOCK_FOLD_BATCH; ++i) sum = __dadd_rn(sum, v[i]);
-      }
+      STOCK_FOLD_RECORDS(sum, rec, c0, c1);  // a missing record adds +0.0: it changes no sum
       sums[k] = sum;
     }
     __syncthreads();

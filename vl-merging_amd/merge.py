@@ -1,4 +1,4 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock, SCE -- and the expert-pair statistics
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock, SCE, SLERP / Karcher mean -- and the expert-pair statistics
 (expert_stats) that say how far apart the experts are before any of them is tried.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
@@ -28,6 +28,10 @@ It has no hyper-parameter; the apply pass reads a scalar the reduction over the 
 sce_merge (SCE, Wan et al. 2024) likewise: no reference site, the rule in include/vlm_hip.h, csrc/sce.hip held to
 tests/sce_restatement.py: a select on the variance across the experts, a reduction that depends on its threshold, an apply pass
 that reads both.
+
+sphere_merge (SLERP and the Karcher mean; mergekit's nuslerp / karcher) likewise: no reference site, the rule in include/vlm_hip.h,
+csrc/sphere.hip held to tests/sphere_restatement.py: one coefficient per source and per group (a tensor or a row), made by an
+iterative solve on the device from the group's Gram matrix.
 """
 import ctypes
 import math
@@ -725,6 +729,129 @@ def sce_merge(state_dict, config, central_weight=None, density=0.1, lam=None, de
     ties_keep_count(density, 1)  # ValueError before any device work
     return _task_vector_merge(ScePlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density=density, lam=lam, name=dst),
                               state_dict, config, central_weight, lam, device, plan_out, report_out)
+
+
+SPHERE_STATUS = {L.SPHERE_OK: "ok", L.SPHERE_LINEAR: "linear", L.SPHERE_ZERO: "zero"}
+
+
+class SpherePlan(_Plan):
+    """The job table of csrc/sphere.hip; run() enqueues the four launches of a spherical merge without a host synchronisation:
+    for the tensor jobs Model Stock's three (the reducer of the Gram sums, the fold that ends in step 3, the apply pass that reads
+    its S coefficients), for the row jobs one launch over tiles of whole rows.  One plan may mix both kinds.  Step 3 -- the
+    weighted Karcher mean of the directions, 24 iterations in f64 -- runs on the device."""
+
+    KIND, GPU_ONLY, JOB = "spherical", "the spherical merge kernels run on the GPU only", L.SphereJob
+    BYTES, UPLOAD, RUN, HEADER = "vlm_sphere_plan_bytes", "vlm_sphere_plan_upload", "vlm_sphere_run", L.SphereHeader
+    PASSES = 2  # a tensor job: the reducer and the apply pass; add() takes one of them back for a row job
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.coefs: List[Optional[torch.Tensor]] = []  # per job: the coef_out tensor, float32 [groups, MERGE_MAX_SRC], or None
+
+    def add(self, srcs, base, weights, lam=1.0, rows=False, row_len=None, coef_out=False, name=None):
+        """One output tensor.  `base`: the central tensor (the sources' task vectors are merged and lam scales the result) or None
+        (the sources themselves; lam must be 1).  `weights`: one non-negative number per source, not all zero.  `rows` (or a
+        `row_len`): one mean per row -- `row_len` defaults to della_row_len of the first source, may not exceed DELLA_MAX_ROW and
+        must divide the tensor.  `coef_out`: keep the float32 coefficients of every group in self.coefs[job]."""
+        ws = [float(w) for w in weights]
+        if len(ws) != len(srcs) or not all(math.isfinite(w) and w >= 0.0 for w in ws) or not sum(ws) > 0.0:
+            raise L.VlmError("a spherical job takes one finite weight >= 0 per source, not all zero; got %r for %d sources" % (weights, len(srcs)))
+        if base is None and float(lam) != 1.0:
+            raise L.VlmError("a spherical job without a base has no lam (got %r)" % (lam,))
+        rl = 0
+        if rows or row_len is not None:
+            rl = della_row_len(srcs[0]) if row_len is None else int(row_len)
+            if not 1 <= rl <= L.DELLA_MAX_ROW:
+                raise L.VlmError("a row of the spherical merge holds 1 .. %d entries, got %d" % (L.DELLA_MAX_ROW, rl))
+            if srcs[0].numel() % rl:
+                raise L.VlmError("row length %d does not divide the tensor's %d entries" % (rl, srcs[0].numel()))
+        groups = srcs[0].numel() // rl if rl else 1
+        coef = torch.zeros((groups, L.MERGE_MAX_SRC), dtype=torch.float32, device=self.device) if coef_out else None
+
+        def fill(job):
+            for k, w in enumerate(ws):
+                job.w[k] = w
+            job.lam = float(lam)
+            job.row_len = rl
+            job.coef_out = 0 if coef is None else coef.data_ptr()
+        out = self._add(fill, srcs, base, name=name)
+        self.coefs.append(coef)
+        if rl:  # a row job reads its inputs once
+            self.bytes_read -= 4 * srcs[0].numel() * (len(srcs) + (0 if base is None else 1))
+        return out
+
+    def results(self):
+        """The raw vlm_sphere_result_t of every job as the device left it (this synchronises)."""
+        if self.ws is None:
+            raise L.VlmError("SpherePlan.report() needs a plan that has run")
+        hdr = self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
+        size = ctypes.sizeof(L.SphereResult)
+        raw = self.ws[hdr.results_off: hdr.results_off + size * hdr.n_jobs].cpu().numpy().tobytes()
+        return [L.SphereResult.from_buffer_copy(raw[i * size: (i + 1) * size]) for i in range(len(self.jobs))]
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): `n`, `row_len` (0: one group, the tensor), `weights`, `lam`; a
+        tensor job: `sq` per source, `dot` per pair in slot order, `coef64`, `coef32` (as floats and as their bits), `rho`,
+        `resid`, `status` ("ok" | "linear" | "zero"); a row job: `rows`, `rows_linear`, `rows_zero`, `resid_max` -- all as the
+        device made them."""
+        out = []
+        for name, job, r in zip(self.names, self.jobs, self.results()):
+            S = job.n_src
+            row = {"dst": name, "n": int(job.n_elem), "row_len": int(job.row_len), "weights": [job.w[m] for m in range(S)],
+                   "lam": float(job.lam)}
+            if job.row_len:
+                row.update(rows=int(job.n_elem) // int(job.row_len), rows_linear=int(r.rows_linear), rows_zero=int(r.rows_zero),
+                           resid_max=r.resid_max)
+            else:
+                row.update(sq=[r.sq[m] for m in range(S)],
+                           pairs=[{"a": a, "b": b, "dot": r.dot[L.pair_slot(a, b)]} for b in range(1, S) for a in range(b)],
+                           coef64=[r.coef64[m] for m in range(S)], coef32=[float(r.coef32[m]) for m in range(S)],
+                           coef32_bits=[float32_bits(r.coef32[m]) for m in range(S)], rho=r.rho, resid=r.resid,
+                           status=SPHERE_STATUS[int(r.status)])
+            out.append(row)
+        return out
+
+
+def sphere_merge(state_dict, config, central_weight=None, on="weights", rows=False, lam=None, device="cuda",
+                 plan_out: Optional[list] = None, report_out: Optional[list] = None):
+    """Spherical merge of the modality experts (no reference site; the rule: include/vlm_hip.h): SLERP for two experts, the
+    weighted Karcher mean of the directions for three, scaled by the weighted mean of the norms -- the counterpart of merge_weights
+    that keeps the norm where the experts point apart.  The weights are merge_weights': interpolation_ratios(modalities,
+    config["merge_ratio"]).  `rows`: one mean per row of a tensor (a vector is one row) instead of one per tensor.
+    `on="weights"` merges the experts' weights themselves: merge_weights' inputs, keys, pass-through and KeyError behaviour; no
+    central checkpoint is needed and none is read; `lam` must be None.  `on="delta"` merges their task vectors `W_m - central` and
+    adds lam times the mean to the central tensor: sum_task_vectors' contract, `lam=None` takes config["sum_lambda"].
+    A layer with ONE source is the job merge_weights or sum_task_vectors issues for it (ratio 1).  `plan_out` receives the
+    SpherePlan FIRST whenever a layer has several sources, then the MergePlan of the single-source layers if there are any;
+    `report_out` receives SpherePlan.report() (reading it back synchronises)."""
+    if on not in ("weights", "delta"):
+        raise ValueError("sphere_merge merges on 'weights' or on 'delta', got %r" % (on,))
+    delta = on == "delta"
+    if not delta and lam is not None:
+        raise ValueError("sphere_merge on the weights has no lambda (got %r)" % (lam,))
+    if delta and lam is None:
+        lam = config["sum_lambda"]
+    plan = SpherePlan(device)
+    single = MergePlan(plan.device)
+    out = _passthrough(state_dict)
+    central = _central(central_weight, config) if delta else None
+    for dst, mods, srcs, through in _walk(state_dict, config, central):
+        if srcs is None:
+            out[dst] = through
+        elif len(mods) == 1:
+            if delta:
+                out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
+            else:
+                out[dst] = single.add(L.MERGE_LERP, _tensors(srcs), [1])
+        else:
+            ratios = interpolation_ratios(mods, config["merge_ratio"])
+            out[dst] = plan.add(_tensors(srcs), central[dst] if delta else None, [ratios[m] for m, _ in srcs],
+                                lam=lam if delta else 1.0, rows=rows, name=dst)
+    for p in (plan, single):
+        _finish(p, plan_out)
+    if report_out is not None:
+        report_out.extend(plan.report() if plan.jobs else [])
+    return out
 
 
 # ------------------------------------------------------------------------------------------------- expert-pair statistics

@@ -1,11 +1,11 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
 sum_task_vectors / regmean on the state_dict it has just read); a merged checkpoint on disk is what one hands on, so this tool
 runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge), DARE (merge.dare_merge), Model
-Breadcrumbs (merge.band_merge), DELLA (merge.della_merge), Model Stock (merge.stock_merge) and SCE (merge.sce_merge; none of the six has a
+Breadcrumbs (merge.band_merge), DELLA (merge.della_merge), Model Stock (merge.stock_merge), SCE (merge.sce_merge) and the spherical merge (merge.sphere_merge; none of the seven has a
 reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
 `vlffn_start_layer_index`, `only_activate_used_experts`, `loss_names`, `merge_ratio`, `sum_lambda`, `central_weight`.
 
@@ -21,12 +21,17 @@ reference site) outside a model.  The words after the options are a config in ru
                                          ignored, as they are for interp)
   --method sce       sce_merge          (--density = the share of elements selected by their variance across the experts;
                                          --lambda, --central as above)
+  --method slerp     sphere_merge       (`karcher` is the same method: SLERP is its two-source case.  --sphere-on weights merges
+                                         the experts' weights as interp does, with --ratio; --sphere-on delta merges their task
+                                         vectors, with --lambda and --central as above; --sphere-rows: one mean per row)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
                      dare: n, keep_below, kept per source, conflict, empty;
                      breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty;
                      della: n, keep_lo, keep_hi, row_len, kept per source, conflict, empty;
                      stock: n, sq per source, dot and cosine per pair, the mean cosine, t, scale and its bits;
-                     sce: n, K, the variance threshold, kept, sq and weight per source, tot, conflict, empty)
+                     sce: n, K, the variance threshold, kept, sq and weight per source, tot, conflict, empty;
+                     slerp: n, row_len, weights, lam and, per tensor, sq, dot per pair, coef64, coef32 and its bits, rho, resid,
+                     status -- per row instead: rows, rows_linear, rows_zero, resid_max)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -41,7 +46,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher")
 
 
 def build_parser():
@@ -49,11 +54,11 @@ def build_parser():
     p.add_argument("--method", choices=METHODS, required=True)
     p.add_argument("--ckpt", required=True, help="all_moe checkpoint (a Lightning .ckpt or a bare state_dict file)")
     p.add_argument("--out", required=True, help="merged checkpoint to write")
-    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs / della / stock / sce; default: central_weight of the config")
+    p.add_argument("--central", default=None, help="central (ufo) checkpoint of taskvec / ties / dare / breadcrumbs / della / stock / sce / slerp on delta; default: central_weight of the config")
     p.add_argument("--density", type=float, default=0.2,
                    help="ties / breadcrumbs: fraction of each task vector kept, in (0, 1]; della: the mean keep probability; "
                         "sce: fraction of the elements selected by their variance across the experts, in (0, 1]")
-    p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare / breadcrumbs / della / sce: overrides sum_lambda")
+    p.add_argument("--lambda", dest="lam", type=float, default=None, help="taskvec / ties / dare / breadcrumbs / della / sce / slerp on delta: overrides sum_lambda")
     p.add_argument("--drop", type=float, default=0.9, help="dare: probability of dropping a task-vector entry, in [0, 1)")
     p.add_argument("--seed", type=int, default=0, help="dare / della: seed of the mask (64 bits)")
     p.add_argument("--dare-mode", dest="dare_mode", choices=("linear", "ties"), default="linear",
@@ -68,7 +73,11 @@ def build_parser():
                         "(its largest); needs 0 < density - epsilon and density + epsilon <= 1")
     p.add_argument("--della-mode", dest="della_mode", choices=("linear", "ties"), default="linear",
                    help="della: sum the rescaled survivors, or elect a sign and average them as TIES does")
-    p.add_argument("--ratio", type=float, default=None, help="interp: overrides merge_ratio")
+    p.add_argument("--ratio", type=float, default=None, help="interp / slerp: overrides merge_ratio")
+    p.add_argument("--sphere-on", dest="sphere_on", choices=("weights", "delta"), default="weights",
+                   help="slerp / karcher: merge the experts' weights themselves (no central checkpoint), or their task vectors")
+    p.add_argument("--sphere-rows", dest="sphere_rows", action="store_true",
+                   help="slerp / karcher: one spherical mean per row of a tensor (a vector is one row) instead of one per tensor")
     p.add_argument("--report", default=None, help="write a JSON report here")
     p.add_argument("config", nargs="*", help="with <named configs> key=value ... (as for run.py)")
     return p
@@ -101,10 +110,10 @@ def parse_args(argv):
     return args, cfg
 
 
-def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None, della=None):
+def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None, della=None, sphere=None):
     """The merged state_dict (device tensors for merged keys, the input's objects for the rest).  `dare`: the keyword arguments of
     merge.dare_merge (drop, seed, mode, rescale); `band`: those of merge.band_merge beside the density (gamma, mode); `della`: those of
-    merge.della_merge beside the density (epsilon, seed, mode, rescale)."""
+    merge.della_merge beside the density (epsilon, seed, mode, rescale); `sphere`: those of merge.sphere_merge (on, rows)."""
     merge = importlib.import_module("vl_merging_amd.merge")
     if method == "interp":
         out = merge.merge_weights(sd, cfg)
@@ -128,6 +137,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
     elif method == "sce":
         rows = []
         out = merge.sce_merge(sd, cfg, central_weight=central, density=density, report_out=rows)
+        if report is not None:
+            report.extend(rows)
+    elif method in ("slerp", "karcher"):
+        rows = []
+        out = merge.sphere_merge(sd, cfg, central_weight=central, report_out=rows, **(sphere or {}))
         if report is not None:
             report.extend(rows)
     elif method == "breadcrumbs":
@@ -156,11 +170,13 @@ def main(argv):
     central = ckpt.load_file(args.central) if args.central else None
     report = [] if args.report else None
     is_dare, is_band, is_della = args.method == "dare", args.method == "breadcrumbs", args.method == "della"
+    is_sphere = args.method in ("slerp", "karcher")
     has_density = args.method in ("ties", "sce") or is_band or is_della
     out = merge_state(args.method, sd, cfg, central=central, density=args.density, report=report,
                       dare=dict(drop=args.drop, seed=args.seed, mode=args.dare_mode, rescale=args.rescale),
                       band=dict(gamma=args.gamma, mode=args.band_mode),
-                      della=dict(epsilon=args.epsilon, seed=args.seed, mode=args.della_mode, rescale=args.rescale))
+                      della=dict(epsilon=args.epsilon, seed=args.seed, mode=args.della_mode, rescale=args.rescale),
+                      sphere=dict(on=args.sphere_on, rows=args.sphere_rows))
     torch.cuda.synchronize()
     torch.save({"state_dict": {k: v.detach().to("cpu") for k, v in out.items()}}, args.out)
     if args.report:
@@ -171,6 +187,7 @@ def main(argv):
                        "gamma": args.gamma if is_band else None, "band_mode": args.band_mode if is_band else None,
                        "epsilon": args.epsilon if is_della else None, "della_mode": args.della_mode if is_della else None,
                        "rescale": args.rescale if is_dare or is_della else None,
+                       "sphere_on": args.sphere_on if is_sphere else None, "sphere_rows": args.sphere_rows if is_sphere else None,
                        "sum_lambda": cfg["sum_lambda"], "merge_ratio": cfg["merge_ratio"], "tensors": report}, f, indent=1)
     print("merge_ckpt: %s -> %s (%s, %d tensors)" % (args.ckpt, args.out, args.method, len(out)))
     return 0

@@ -307,6 +307,11 @@ class ViLTransformerSS(nn.Module):
         wired to a config key and not called from __init__."""
         return merge_ops.sce_merge(state_dict, self.hparams.config, density=density, lam=lam, device=self._merge_device())
 
+    def sphere_merge(self, state_dict, on="weights", rows=False, lam=None):
+        """Spherical merge of the experts (SLERP for two, the Karcher mean for more; no reference site; merge.sphere_merge).  `on`:
+        "weights" has merge_weights' contract, "delta" sum_task_vectors'; not wired to a config key."""
+        return merge_ops.sphere_merge(state_dict, self.hparams.config, on=on, rows=rows, lam=lam, device=self._merge_device())
+
     def expert_stats(self, state_dict, raw=False, trunc_rms=None):
         """How far apart the modality experts of `state_dict` are (no reference site; merge.expert_stats).  Merges nothing; not
         wired to a config key and not called from __init__."""

@@ -703,6 +703,79 @@ int vlm_sphere_plan_upload(const vlm_sphere_job_t* jobs_host, int n_jobs, void* 
 int vlm_sphere_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Consensus merge with TALL masks (Wang et al., "Localizing Task Information for Improved Model Merging and Compression", ICML
+ * 2024), csrc/tall.hip.  NO REFERENCE SITE: the reference has no such merge; the arithmetic below is the specification and is
+ * pinned to a numpy restatement of it (tests/tall_restatement.py), not to the reference.  One VLM_TALL_CONSENSUS job = one output
+ * tensor with central tensor c (base, required), sources W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), tall_lambda >= 0 (fp32), an
+ * integer k in [0, S] and lam (fp32); fp32, one rounding per operation, no FMA, source order:
+ *   1. x_m = W_m - c
+ *   2. d = ((0 + x_0) + x_1) + ...                  (the multi-task vector, in the order of the LINEAR combine)
+ *   3. r_m = d - x_m;  keep_m = |x_m| >= tall_lambda * |r_m|   (the product rounds once; the comparison is >=, so a NaN keeps
+ *      nothing and 0 >= 0 keeps a zero entry, as in the paper)
+ *   4. votes = sum_m keep_m;  sel = votes >= k
+ *   5. dst = c + lam * (sel ? d : +0.0)
+ *   6. if the job has masks: word w of source m's mask has bit b (bit 0 = least significant) equal to keep_m[32 w + b].  A mask
+ *      has ceil(n_elem / 32) 32-bit words; every word is written by every run, and the bits at positions >= n_elem are 0.  On a
+ *      little-endian host the mask reads as numpy.unpackbits(words.view(uint8), bitorder="little")[:n_elem].
+ * k = 0 is plain task arithmetic, c + lam * d; k = 2 drops what only one expert cares about ("selfish") and what none does
+ * ("catastrophic").  S = 1 keeps everything (r_0 = 0).
+ * Counters per job (uint64; integer atomics only, so nothing depends on the order workgroups run in), in the slots of the TIES
+ * counters: kept[0 .. MAX_SRC) = the bits set in mask m, then `selected` = the elements with sel, then `empty` = the elements
+ * with votes == 0.
+ * A VLM_TALL_RESTORE job rebuilds one expert from the unified tensor: n_src = 1, src[0] = u, base = c, mask[0] = a packed mask
+ * (an INPUT), and dst[i] = bit_i ? u[i] : c[i] -- a select, no arithmetic; k, tall_lambda and lam are not read (k in [0, 1] and
+ * tall_lambda >= 0 are still checked).  With u the k = 0, lam = 1 output of the rule above this is float32(c + keep_m * d), the
+ * paper's reconstruction.  Its counters: kept[0] = the elements taken from u; `selected` and `empty` stay 0.  The mask is read
+ * up to word ceil(n_elem / 32) - 1 and no further; bits at positions >= n_elem are ignored.  One job restores one expert: a second
+ * expert is a second job that reads u and c again.
+ * Both ops are elementwise: dst may be EXACTLY base or EXACTLY one of the job's sources; any other overlap of dst's byte range with
+ * an input's is VLM_ERR_ARG, and so is a mask whose 4 ceil(n_elem / 32) bytes meet dst, the base, a source or another mask of the
+ * same job (overlap ACROSS jobs is the caller's to avoid).  Non-finite inputs are outside the contract.  A run leaves the same
+ * bytes, words and counters whatever the grid, the job's place in a plan or the number of runs.
+ */
+#define VLM_TALL_CONSENSUS 0
+#define VLM_TALL_RESTORE 1
+
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each; RESTORE: src[0] = the unified tensor u */
+  void* mask[VLM_MERGE_MAX_SRC];        /* u32 [ceil(n_elem / 32)] each, 16-byte aligned.  CONSENSUS: outputs, all NULL or all
+                                           n_src set; RESTORE: mask[0] is the input */
+  uint64_t n_elem;
+  int32_t n_src;
+  int32_t op;                           /* VLM_TALL_CONSENSUS | VLM_TALL_RESTORE */
+  int32_t k;                            /* step 4: 0 .. n_src */
+  float tall_lambda;                    /* step 3: >= 0 */
+  float lam;                            /* step 5 */
+  uint32_t reserved;
+} vlm_tall_job_t;
+
+/* The workspace of a consensus plan BEGINS with this header (byte offsets from its start); jobs keep their upload order. */
+typedef struct {
+  uint64_t n_jobs, n_chunks;
+  uint64_t jobs_off;      /* vlm_tall_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table */
+  uint64_t counters_off;  /* uint64 [n_jobs][VLM_TALL_COUNTERS]: kept per source, selected, empty */
+} vlm_tall_header_t;
+#define VLM_TALL_COUNTERS (VLM_MERGE_MAX_SRC + 2)
+
+/* Bytes of device workspace a consensus plan for n_jobs jobs over total_elems elements needs (header, jobs, chunk table,
+ * counters).  The masks are the caller's tensors, not part of the workspace.  No reference site. */
+size_t vlm_tall_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (the checks of vlm_dare_plan_upload on dst, base, the sources and the length; a valid op, k in [0, n_src] and
+ * tall_lambda >= 0 and not NaN; a RESTORE job has n_src == 1 and mask[0]; a CONSENSUS job has no mask or one per source; every mask
+ * 16-byte aligned and clear of the job's tensors and other masks; else VLM_ERR_ARG), build the chunk table on the host and copy
+ * header + jobs + table into `workspace` (16-byte aligned; VLM_ERR_WORKSPACE if it is too small).  SYNCHRONISES `stream` before it
+ * returns (pageable temporary source); it is the last host synchronisation of a plan.  Implements no step of the rule; no
+ * reference site. */
+int vlm_tall_plan_upload(const vlm_tall_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: a tiny launch that zeroes the counters, then ONE streaming launch over all jobs of both ops (steps 1-6
+ * and the counters; the select of a RESTORE job); no host synchronisation.  May be called again on the same workspace and gives
+ * the same bytes, mask words and counters.  One run at a time per workspace.  No reference site. */
+int vlm_tall_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

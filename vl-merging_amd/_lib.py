@@ -112,6 +112,32 @@ class DareHeader(ctypes.Structure):
     _fields_ = [(n, c_u64) for n in ("n_jobs", "n_chunks", "jobs_off", "chunks_off", "counters_off")]
 
 
+TALL_CONSENSUS, TALL_RESTORE = 0, 1
+TALL_COUNTERS = MERGE_MAX_SRC + 2  # VLM_TALL_COUNTERS: kept per source, selected, empty
+
+
+class TallJob(ctypes.Structure):
+    """vlm_tall_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("mask", c_void_p * MERGE_MAX_SRC),
+        ("n_elem", c_u64),
+        ("n_src", ctypes.c_int32),
+        ("op", ctypes.c_int32),
+        ("k", ctypes.c_int32),
+        ("tall_lambda", c_float),
+        ("lam", c_float),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class TallHeader(ctypes.Structure):
+    """vlm_tall_header_t: the first bytes of a consensus plan's workspace."""
+    _fields_ = [(n, c_u64) for n in ("n_jobs", "n_chunks", "jobs_off", "chunks_off", "counters_off")]
+
+
 DELLA_LINEAR, DELLA_TIES = 0, 1
 DELLA_COUNTERS = MERGE_MAX_SRC + 2  # VLM_DELLA_COUNTERS: kept per source, conflict, empty
 DELLA_MAX_ROW = 4096                # VLM_DELLA_MAX_ROW: the longest row whose ranks one workgroup makes in LDS
@@ -379,6 +405,9 @@ SIGNATURES = {
     "vlm_sphere_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_sphere_plan_upload": (c_int, [ctypes.POINTER(SphereJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_sphere_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_tall_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_tall_plan_upload": (c_int, [ctypes.POINTER(TallJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_tall_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_bf16_live": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,

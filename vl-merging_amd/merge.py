@@ -1,4 +1,4 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock, SCE, SLERP / Karcher mean -- and the expert-pair statistics
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock, SCE, SLERP / Karcher mean, Consensus merging with TALL masks (and the restore of the experts from them) -- and the expert-pair statistics
 (expert_stats) that say how far apart the experts are before any of them is tried.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
@@ -32,6 +32,18 @@ that reads both.
 sphere_merge (SLERP and the Karcher mean; mergekit's nuslerp / karcher) likewise: no reference site, the rule in include/vlm_hip.h,
 csrc/sphere.hip held to tests/sphere_restatement.py: one coefficient per source and per group (a tensor or a row), made by an
 iterative solve on the device from the group's Gram matrix.
+
+consensus_merge (Consensus merging with TALL masks, Wang et al. 2024) likewise: no reference site, csrc/tall.hip held to
+tests/tall_restatement.py.  Its rule (include/vlm_hip.h), per tensor with central tensor c, sources W_0 .. W_{S-1}, tall_lambda >= 0,
+an integer k in [0, S] and lam; fp32 rounds once, no FMA:
+  1. x_m = W_m - c
+  2. d = ((0 + x_0) + x_1) + ...
+  3. keep_m = |x_m| >= tall_lambda * |d - x_m|
+  4. sel = (sum_m keep_m) >= k
+  5. dst = c + lam * (sel ? d : +0.0)
+  6. the keep_m, packed 32 to a word (bit 0 first), are the TALL masks
+It is the first method that decides per element by comparing an expert with the others, and the first whose streaming pass has a
+bit-packed side output.  tall_restore is the reverse direction: ufo + masks -> all_moe, dst = bit ? unified : central per expert.
 """
 import ctypes
 import math
@@ -729,6 +741,160 @@ def sce_merge(state_dict, config, central_weight=None, density=0.1, lam=None, de
     ties_keep_count(density, 1)  # ValueError before any device work
     return _task_vector_merge(ScePlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density=density, lam=lam, name=dst),
                               state_dict, config, central_weight, lam, device, plan_out, report_out)
+
+
+def tall_threshold(tall_lambda):
+    """tall_lambda of the consensus rule as a python float: a number >= 0 (an expert's entry is relevant to it iff its magnitude is
+    at least tall_lambda times the magnitude of the other experts' sum there)."""
+    if isinstance(tall_lambda, bool) or not isinstance(tall_lambda, (int, float)) or not (tall_lambda >= 0.0):  # also rejects NaN
+        raise ValueError("tall_lambda must be a number >= 0, got %r" % (tall_lambda,))
+    return float(tall_lambda)
+
+
+def consensus_k(k, S=None):
+    """k of the consensus rule for S sources: an integer in [0, S] (an element is kept iff at least k experts find it relevant).
+    S = None: any integer >= 0, for a caller that clamps k per layer (consensus_merge)."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0 or (S is not None and k > S):
+        raise ValueError("consensus k must be an integer in [0, %s], got %r" % ("S" if S is None else S, k))
+    return k
+
+
+def tall_mask_words(n):
+    """32-bit words of a packed mask of n elements."""
+    return (int(n) + 31) // 32
+
+
+TALL_OPS = {L.TALL_CONSENSUS: "consensus", L.TALL_RESTORE: "restore"}
+
+
+class TallPlan(_Plan):
+    """The job table of csrc/tall.hip; run() enqueues the counter reset and the one streaming launch that serves both ops -- the
+    consensus merge (add) and the restore of one expert from the unified tensor, the central tensor and a packed mask
+    (add_restore) -- without a host synchronisation.  self.masks[job] holds a consensus job's mask tensors (int32, ceil(n / 32)
+    words per source; None without masks) or the one mask a restore job reads."""
+
+    KIND, GPU_ONLY, JOB = "consensus", "the consensus kernel runs on the GPU only", L.TallJob
+    BYTES, UPLOAD, RUN, HEADER = "vlm_tall_plan_bytes", "vlm_tall_plan_upload", "vlm_tall_run", L.TallHeader
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.masks: List[Optional[List[torch.Tensor]]] = []
+
+    def add(self, srcs, base, tall_lambda, k, lam=1.0, masks=False, out=None, name=None):
+        """One output tensor.  `out` may be `base` or one of `srcs` (the pass is elementwise) or any tensor that meets none of them.
+        `masks=True` allocates one int32 tensor of ceil(n / 32) words per source, kept in self.masks[job]; every run writes every
+        word of them."""
+        tall_lambda = tall_threshold(tall_lambda)
+        k = consensus_k(k, len(srcs))
+        n = srcs[0].numel()
+        made = [torch.empty(tall_mask_words(n), dtype=torch.int32, device=self.device) for _ in srcs] if masks else None
+
+        def fill(job):
+            job.op = L.TALL_CONSENSUS
+            job.k = k
+            job.tall_lambda = tall_lambda
+            job.lam = float(lam)
+            for m in range(job.n_src if made else 0):
+                job.mask[m] = made[m].data_ptr()
+        out = self._add(fill, srcs, base, out, name)
+        self.masks.append(made)
+        self.bytes_written += 4 * tall_mask_words(n) * len(srcs) if made else 0
+        return out
+
+    def add_restore(self, unified, base, mask, out=None, name=None):
+        """One expert's tensor: out[i] = bit i of `mask` ? unified[i] : base[i].  `mask`: an int32 tensor of ceil(n / 32) words (a CPU
+        tensor is copied to the device)."""
+        n = unified.numel()
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.numel() != tall_mask_words(n):
+            raise L.VlmError("a mask for %d elements is an int32 tensor of %d words, got %s" % (
+                n, tall_mask_words(n), "%s x %d" % (mask.dtype, mask.numel()) if isinstance(mask, torch.Tensor) else type(mask).__name__))
+        mask = mask.detach().reshape(-1)
+        if mask.device != self.device or not mask.is_contiguous() or (mask.data_ptr() & 15):
+            mask = mask.to(self.device, copy=True).contiguous()
+
+        def fill(job):
+            job.op = L.TALL_RESTORE
+            job.k, job.tall_lambda, job.lam = 0, 0.0, 1.0
+            job.mask[0] = mask.data_ptr()
+        out = self._add(fill, [unified], base, out, name)
+        self.masks.append([mask])
+        self.bytes_read += 4 * tall_mask_words(n)
+        return out
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): `op` ("consensus" | "restore"), `k`, `tall_lambda`, `kept` per source
+        (the bits set in its mask; restore: the elements taken from the unified tensor), `selected` (the elements at least k
+        experts find relevant) and `empty` (the elements none does)."""
+        _, rows = self._read()
+        out = []
+        for (head, counts), job in zip(rows, self.jobs):
+            out.append({**head, "op": TALL_OPS[int(job.op)], "k": int(job.k), "tall_lambda": float(job.tall_lambda),
+                        "kept": counts["kept"], "selected": counts["conflict"], "empty": counts["empty"]})
+        return out
+
+
+# dst -> (layer, source template) of every merged tensor name
+_SRC_OF = {dst: (i, src) for i in range(NUM_MERGE_LAYERS) for src, dst in _tensor_names(i)}
+
+
+def consensus_merge(state_dict, config, central_weight=None, tall_lambda=0.4, k=2, lam=None, masks_out: Optional[dict] = None,
+                    device="cuda", plan_out: Optional[list] = None, report_out: Optional[list] = None):
+    """Consensus merge (Wang et al. 2024) of the modality experts' task vectors `W_m - central` (no reference site; the rule:
+    include/vlm_hip.h): an entry of the summed task vector is added to the central tensor only where at least `k` experts find it
+    relevant to themselves -- expert m does where |x_m| >= tall_lambda * |sum of the other experts' entries|.  k = 0 is plain task
+    arithmetic; k = 2 removes what one expert alone cares about and what none does.  `k` is an integer >= 0 and is NOT checked
+    against a layer's source count: a layer with S sources runs with min(k, S), the one explicit rule by which k is clamped (so
+    k = 3 asks for all three experts where there are three and for both where there are two).
+    Same inputs, keys, pass-through and KeyError behaviour as sum_task_vectors, ties_merge and dare_merge; `lam=None` takes
+    config["sum_lambda"].  A layer with ONE source is the task-vector job with ratio 1 that sum_task_vectors issues for it.
+    `masks_out`, if a dict, receives {source key (e.g. transformer.blocks.3.attn.v.qkv.weight): int32 device tensor of
+    ceil(n / 32) words} for every tensor with several sources: the TALL masks, with which tall_restore rebuilds an approximation
+    of every expert from the k = 0 merge.  `plan_out` receives the TallPlan FIRST whenever a layer has several sources, then the
+    MergePlan of the single-source layers if there are any; `report_out` receives TallPlan.report() (reading it back
+    synchronises)."""
+    tall_lambda = tall_threshold(tall_lambda)  # ValueError before any device work
+    consensus_k(k)
+
+    def add(plan, dst, srcs, c, lam):
+        out = plan.add(srcs, c, tall_lambda, min(k, len(srcs)), lam=lam, masks=masks_out is not None, name=dst)
+        if masks_out is not None:
+            i, src = _SRC_OF[dst]
+            for m, t in zip(modalities_for_layer(config, i), plan.masks[-1]):
+                masks_out[src(m)] = t
+        return out
+    return _task_vector_merge(TallPlan, add, state_dict, config, central_weight, lam, device, plan_out, report_out)
+
+
+def tall_restore(unified_state_dict, masks, config, central_weight=None, device="cuda", plan_out: Optional[list] = None):
+    """ufo + TALL masks -> all_moe: rebuilds an approximation of every modality expert from the unified checkpoint (the k = 0,
+    lam = 1 output of consensus_merge: central + the summed task vector), the central checkpoint and the packed masks that
+    consensus_merge(masks_out=...) left (no reference site; the restore rule: include/vlm_hip.h).  Returns an all_moe-keyed
+    state_dict: for every source key in `masks`, the select `bit ? unified : central` of the destination key's tensors (exactly
+    float32(central + mask * task-vector sum), the paper's reconstruction); for a layer with ONE source, the unified tensor itself
+    under the source key; non-block keys pass through by identity.  The unified block keys themselves are not returned.  A key of
+    `masks` that names no source of a multi-source layer under `config` is a KeyError; a mask whose word count does not fit its
+    tensor is a VlmError.  One job per expert and tensor: each re-reads the unified and the central tensor.  `plan_out` receives
+    the TallPlan if it has jobs."""
+    out = _passthrough(unified_state_dict)
+    central = _central(central_weight, config)
+    plan = TallPlan(device)
+    seen = set()
+    for i in range(NUM_MERGE_LAYERS):
+        mods = modalities_for_layer(config, i)
+        for src, dst in _tensor_names(i):
+            if len(mods) == 1:
+                out[src(mods[0])] = unified_state_dict[dst]
+                continue
+            for m in mods:
+                key = src(m)
+                if key in masks:
+                    out[key] = plan.add_restore(unified_state_dict[dst], central[dst], masks[key], name=key)
+                    seen.add(key)
+    missing = [key for key in masks if key not in seen]
+    if missing:
+        raise KeyError("masks name no source of a multi-source layer: %s" % ", ".join(sorted(missing)[:4]))
+    _finish(plan, plan_out)
+    return out
 
 
 SPHERE_STATUS = {L.SPHERE_OK: "ok", L.SPHERE_LINEAR: "linear", L.SPHERE_ZERO: "zero"}

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
 sum_task_vectors / regmean on the state_dict it has just read); a merged checkpoint on disk is what one hands on, so this tool
 runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge), DARE (merge.dare_merge), Model
-Breadcrumbs (merge.band_merge), DELLA (merge.della_merge), Model Stock (merge.stock_merge), SCE (merge.sce_merge) and the spherical merge (merge.sphere_merge; none of the seven has a
-reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
+Breadcrumbs (merge.band_merge), DELLA (merge.della_merge), Model Stock (merge.stock_merge), SCE (merge.sce_merge), the spherical merge (merge.sphere_merge) and
+the consensus merge with TALL masks (merge.consensus_merge; none of the eight has a reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
 `vlffn_start_layer_index`, `only_activate_used_experts`, `loss_names`, `merge_ratio`, `sum_lambda`, `central_weight`.
 
   --method interp    merge_weights      (--ratio overrides merge_ratio)
@@ -24,6 +24,10 @@ reference site) outside a model.  The words after the options are a config in ru
   --method slerp     sphere_merge       (`karcher` is the same method: SLERP is its two-source case.  --sphere-on weights merges
                                          the experts' weights as interp does, with --ratio; --sphere-on delta merges their task
                                          vectors, with --lambda and --central as above; --sphere-rows: one mean per row)
+  --method consensus consensus_merge    (--tall-lambda = how large an expert's entry must be against the other experts' sum to be
+                                         relevant to it, --consensus-k = how many experts must find an element relevant,
+                                         --masks-out M.pt = also write the packed TALL masks, from which tall_restore.py
+                                         rebuilds the experts; --lambda, --central as above)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
                      dare: n, keep_below, kept per source, conflict, empty;
                      breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty;
@@ -31,7 +35,8 @@ reference site) outside a model.  The words after the options are a config in ru
                      stock: n, sq per source, dot and cosine per pair, the mean cosine, t, scale and its bits;
                      sce: n, K, the variance threshold, kept, sq and weight per source, tot, conflict, empty;
                      slerp: n, row_len, weights, lam and, per tensor, sq, dot per pair, coef64, coef32 and its bits, rho, resid,
-                     status -- per row instead: rows, rows_linear, rows_zero, resid_max)
+                     status -- per row instead: rows, rows_linear, rows_zero, resid_max;
+                     consensus: n, op, k, tall_lambda, kept per source, selected, empty)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -46,7 +51,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus")
 
 
 def build_parser():
@@ -78,6 +83,13 @@ def build_parser():
                    help="slerp / karcher: merge the experts' weights themselves (no central checkpoint), or their task vectors")
     p.add_argument("--sphere-rows", dest="sphere_rows", action="store_true",
                    help="slerp / karcher: one spherical mean per row of a tensor (a vector is one row) instead of one per tensor")
+    p.add_argument("--tall-lambda", dest="tall_lambda", type=float, default=0.4,
+                   help="consensus: an expert's entry is relevant to it iff |entry| >= tall_lambda * |the other experts' sum|; >= 0")
+    p.add_argument("--consensus-k", dest="consensus_k", type=int, default=2,
+                   help="consensus: keep an element iff at least k experts find it relevant (a layer with S experts uses min(k, S)); "
+                        "0 is plain task arithmetic")
+    p.add_argument("--masks-out", dest="masks_out", default=None,
+                   help="consensus: write {format: tall-masks-1, tall_lambda, k, masks: {source key: int32 words}} here")
     p.add_argument("--report", default=None, help="write a JSON report here")
     p.add_argument("config", nargs="*", help="with <named configs> key=value ... (as for run.py)")
     return p
@@ -107,13 +119,20 @@ def parse_args(argv):
         importlib.import_module("vl_merging_amd.merge").della_window(args.density, args.epsilon)  # the one statement; ValueError
         if not 0 <= args.seed < 2 ** 64:
             raise ValueError("DELLA seed must fit 64 bits, got %r" % (args.seed,))
+    if args.method == "consensus":
+        merge = importlib.import_module("vl_merging_amd.merge")
+        merge.tall_threshold(args.tall_lambda)  # the one statement of each rule; ValueError
+        merge.consensus_k(args.consensus_k)
+    elif args.masks_out is not None:
+        raise ValueError("--masks-out belongs to --method consensus (got %s)" % args.method)
     return args, cfg
 
 
-def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None, della=None, sphere=None):
+def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None, della=None, sphere=None,
+                consensus=None):
     """The merged state_dict (device tensors for merged keys, the input's objects for the rest).  `dare`: the keyword arguments of
     merge.dare_merge (drop, seed, mode, rescale); `band`: those of merge.band_merge beside the density (gamma, mode); `della`: those of
-    merge.della_merge beside the density (epsilon, seed, mode, rescale); `sphere`: those of merge.sphere_merge (on, rows)."""
+    merge.della_merge beside the density (epsilon, seed, mode, rescale); `sphere`: those of merge.sphere_merge (on, rows); `consensus`: those of merge.consensus_merge (tall_lambda, k, masks_out)."""
     merge = importlib.import_module("vl_merging_amd.merge")
     if method == "interp":
         out = merge.merge_weights(sd, cfg)
@@ -144,6 +163,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
         out = merge.sphere_merge(sd, cfg, central_weight=central, report_out=rows, **(sphere or {}))
         if report is not None:
             report.extend(rows)
+    elif method == "consensus":
+        rows = []
+        out = merge.consensus_merge(sd, cfg, central_weight=central, report_out=rows, **(consensus or {}))
+        if report is not None:
+            report.extend(rows)
     elif method == "breadcrumbs":
         rows = []
         out = merge.band_merge(sd, cfg, central_weight=central, density=density, report_out=rows, **(band or {}))
@@ -171,14 +195,20 @@ def main(argv):
     report = [] if args.report else None
     is_dare, is_band, is_della = args.method == "dare", args.method == "breadcrumbs", args.method == "della"
     is_sphere = args.method in ("slerp", "karcher")
+    is_tall = args.method == "consensus"
+    masks = {} if is_tall and args.masks_out else None
     has_density = args.method in ("ties", "sce") or is_band or is_della
     out = merge_state(args.method, sd, cfg, central=central, density=args.density, report=report,
                       dare=dict(drop=args.drop, seed=args.seed, mode=args.dare_mode, rescale=args.rescale),
                       band=dict(gamma=args.gamma, mode=args.band_mode),
                       della=dict(epsilon=args.epsilon, seed=args.seed, mode=args.della_mode, rescale=args.rescale),
-                      sphere=dict(on=args.sphere_on, rows=args.sphere_rows))
+                      sphere=dict(on=args.sphere_on, rows=args.sphere_rows),
+                      consensus=dict(tall_lambda=args.tall_lambda, k=args.consensus_k, masks_out=masks))
     torch.cuda.synchronize()
     torch.save({"state_dict": {k: v.detach().to("cpu") for k, v in out.items()}}, args.out)
+    if masks is not None:
+        torch.save({"format": "tall-masks-1", "tall_lambda": args.tall_lambda, "k": args.consensus_k,
+                    "masks": {k: v.to("cpu") for k, v in masks.items()}}, args.masks_out)
     if args.report:
         with open(args.report, "w") as f:
             json.dump({"method": args.method, "density": args.density if has_density else None,
@@ -188,6 +218,7 @@ def main(argv):
                        "epsilon": args.epsilon if is_della else None, "della_mode": args.della_mode if is_della else None,
                        "rescale": args.rescale if is_dare or is_della else None,
                        "sphere_on": args.sphere_on if is_sphere else None, "sphere_rows": args.sphere_rows if is_sphere else None,
+                       "tall_lambda": args.tall_lambda if is_tall else None, "consensus_k": args.consensus_k if is_tall else None,
                        "sum_lambda": cfg["sum_lambda"], "merge_ratio": cfg["merge_ratio"], "tensors": report}, f, indent=1)
     print("merge_ckpt: %s -> %s (%s, %d tensors)" % (args.ckpt, args.out, args.method, len(out)))
     return 0

@@ -285,6 +285,12 @@ class ViLTransformerSS(nn.Module):
         return merge_ops.dare_merge(state_dict, self.hparams.config, drop=drop, lam=lam, seed=seed, mode=mode, rescale=rescale,
                                     device=self._merge_device())
 
+    def consensus_merge(self, state_dict, tall_lambda=0.4, k=2, lam=None, masks_out=None):
+        """Consensus merge with TALL masks of the experts' task vectors (no reference site; merge.consensus_merge).  Same contract
+        as sum_task_vectors; not wired to a config key and not called from __init__."""
+        return merge_ops.consensus_merge(state_dict, self.hparams.config, tall_lambda=tall_lambda, k=k, lam=lam, masks_out=masks_out,
+                                         device=self._merge_device())
+
     def band_merge(self, state_dict, density=0.9, gamma=0.01, mode="linear", lam=None):
         """Model Breadcrumbs merge of the experts' task vectors (no reference site; merge.band_merge).  Same contract as
         sum_task_vectors; not wired to a config key and not called from __init__."""

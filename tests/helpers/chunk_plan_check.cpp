@@ -1,6 +1,7 @@
 // Host-only check of csrc/chunk_plan.h (no HIP, no GPU): the chunk table of the merge family for the ragged sizes of
 // tests/test_merge_gpu.py and for the 156 tensor lengths of a base-size all_moe -> ufo merge, the host image built around it,
-// and the per-job checks under each overlap policy.  Built with
+// the per-job checks under each overlap policy, and what the methods share whole: chunk_first_fill, chunk_jobs_check and the
+// layouts of the counter plan (dare.hip, tall.hip) and the record plan (pairstats.hip, stock.hip; sphere.hip's parts).  Built with
 // -fsanitize=address,undefined and run as a child process by tests/test_chunk_plan_cpu.py; exit status 0 = every check held.
 #include "chunk_plan.h"
 
@@ -147,10 +148,114 @@ static void check_job_checks() {
   }
 }
 
+struct counts_header_t {  // vlm_dare_header_t's and vlm_tall_header_t's fields
+  uint64_t n_jobs, n_chunks, jobs_off, chunks_off, counters_off;
+};
+struct records_header_t {  // vlm_stock_header_t's and vlm_pairstats_header_t's fields
+  uint64_t n_jobs, n_chunks, jobs_off, chunks_off, first_off, records_off, results_off;
+};
+
+// offs: every part's offset in the order taken, then the total.  256-aligned, the header at 0, and part i ends (its bytes[i],
+// rounded up) exactly where part i + 1 begins: disjoint, no gap beyond the rounding.
+static void check_parts(const char* what, const std::vector<size_t>& offs, const std::vector<size_t>& bytes) {
+  CHECK(offs[0] == 0, "%s: the header is not at 0", what);
+  for (size_t i = 0; i + 1 < offs.size(); ++i) {
+    CHECK(offs[i] % 256 == 0, "%s: part %zu at %zu is not 256-aligned", what, i, offs[i]);
+    CHECK(offs[i] + bytes[i] <= offs[i + 1], "%s: part %zu runs into part %zu", what, i, i + 1);
+    CHECK(offs[i + 1] == offs[i] + (bytes[i] + 255) / 256 * 256, "%s: part %zu begins at %zu", what, i + 1, offs[i + 1]);
+  }
+}
+
+// chunk_first_fill and the two shared layouts against the formulas each method's own *_layout had
+static void check_shared_plans(const char* what, const std::vector<job_t>& jobs) {
+  const int n = (int)jobs.size();
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  std::vector<uint64_t> first(jobs.size() + 1);  // exactly n + 1: the sanitizer sees a fill that runs past it
+  const uint64_t c = chunk_first_fill(jobs.data(), n, first.data());
+  uint64_t before = 0;
+  for (int i = 0; i < n; ++i) {
+    CHECK(first[i] == before, "%s: first[%d] = %llu, expected %llu", what, i, (unsigned long long)first[i], (unsigned long long)before);
+    before += chunks_of(jobs[i].n_elem);
+  }
+  CHECK(first[n] == before && c == before, "%s: first[n] = %llu, returned %llu, expected %llu", what, (unsigned long long)first[n],
+        (unsigned long long)c, (unsigned long long)before);
+  std::vector<chunk_t> ck(c);
+  chunk_table_fill(ck.data(), jobs.data(), n);
+  for (int i = 0; i < n; ++i)  // a job's records are its chunks: the chunk at first[i] + k is chunk k of job i
+    for (uint64_t k = first[i]; k < first[i + 1]; ++k)
+      CHECK(ck[k].job == (uint32_t)i && ck[k].start4 == (k - first[i]) * (CHUNK_FLOATS / 4), "%s: record %llu is not job %d's", what,
+            (unsigned long long)k, i);
+  // a plan whose odd jobs have no chunks (sphere_plan.h: row jobs)
+  const uint64_t ce = chunk_first_fill(jobs.data(), n, first.data(),
+                                       [&](const job_t& j) { return (&j - jobs.data()) % 2 ? (uint64_t)0 : chunks_of(j.n_elem); });
+  before = 0;
+  for (int i = 0; i < n; ++i) {
+    CHECK(first[i] == before, "%s: first[%d] with empty odd jobs", what, i);
+    before += i % 2 ? 0 : chunks_of(jobs[i].n_elem);
+  }
+  CHECK(first[n] == before && ce == before, "%s: first[n] with empty odd jobs", what);
+
+  const size_t head = 256 + up(n * sizeof(job_t)) + up(c * sizeof(chunk_t));  // header, jobs, chunk table
+  for (int counters : {6, 10}) {  // VLM_DARE_COUNTERS == VLM_TALL_COUNTERS, and a wider set
+    counts_header_t h;
+    const size_t total = counts_layout<counts_header_t, job_t>(&h, n, c, counters);
+    CHECK(h.n_jobs == (uint64_t)n && h.n_chunks == c, "%s: counter plan counts", what);
+    check_parts(what, {0, h.jobs_off, h.chunks_off, h.counters_off, total},
+                {sizeof(h), n * sizeof(job_t), c * sizeof(chunk_t), (size_t)n * counters * 8});
+    CHECK(total == head + up((size_t)n * counters * 8), "%s: counter plan of %zu bytes", what, total);  // dare_layout, tall_layout
+  }
+  const size_t shapes[][2] = {{80, 152}, {448, 448}};  // (record, result) bytes of stock.hip and pairstats.hip
+  for (const auto& rr : shapes) {
+    records_header_t h;
+    const size_t total = records_layout<records_header_t, job_t>(&h, n, c, rr[0], rr[1]);
+    CHECK(h.n_jobs == (uint64_t)n && h.n_chunks == c, "%s: record plan counts", what);
+    check_parts(what, {0, h.jobs_off, h.chunks_off, h.first_off, h.records_off, h.results_off, total},
+                {sizeof(h), n * sizeof(job_t), c * sizeof(chunk_t), (size_t)(n + 1) * 8, c * rr[0], n * rr[1]});
+    CHECK(total == head + up((size_t)(n + 1) * 8) + up(c * rr[0]) + up(n * rr[1]), "%s: record plan of %zu bytes", what, total);  // stock_layout, ps_layout
+    // sphere.hip: the same three parts behind a tile table of its own
+    records_header_t g;
+    chunk_layout_t at = chunk_layout_head<records_header_t, job_t>(&g, n, c);
+    const size_t tiles_off = at.take(40 * sizeof(chunk_t));
+    records_parts(at, &g, rr[0], rr[1]);
+    CHECK(tiles_off == h.first_off && g.first_off == h.first_off + 512 && g.records_off - g.first_off == h.records_off - h.first_off &&
+              g.results_off - g.first_off == h.results_off - h.first_off && at.off == total + 512, "%s: record parts behind tiles", what);
+    uint64_t elems = 0;
+    for (const job_t& j : jobs) elems += j.n_elem;
+    CHECK((records_plan_bytes<records_header_t, job_t>(n, elems, rr[0], rr[1]) >= total), "%s: records_plan_bytes is below the plan", what);
+    CHECK((records_plan_bytes<records_header_t, job_t>(-1, elems, rr[0], rr[1]) == 0), "%s: records_plan_bytes of no plan", what);
+  }
+  uint64_t elems = 0;
+  for (const job_t& j : jobs) elems += j.n_elem;
+  counts_header_t h;
+  CHECK((counts_plan_bytes<counts_header_t, job_t>(n, elems, 6) >= counts_layout<counts_header_t, job_t>(&h, n, c, 6)),
+        "%s: counts_plan_bytes is below the plan", what);
+  CHECK((counts_plan_bytes<counts_header_t, job_t>(-1, elems, 6) == 0), "%s: counts_plan_bytes of no plan", what);
+}
+
+// chunk_jobs_check: the arguments first, then per job "n_elem > 0" before the method's check; the first failing job decides
+static void check_jobs_check() {
+  alignas(16) static char ws[32];
+  std::vector<job_t> jobs = {{8}, {8}, {8}};
+  int asked = 0;
+  auto ok = [&](const job_t&) { return ++asked, (int)VLM_OK; };
+  CHECK(chunk_jobs_check(jobs.data(), 3, ws, ok) == VLM_OK && asked == 3, "jobs check: three good jobs");
+  CHECK(chunk_jobs_check((const job_t*)nullptr, 3, ws, ok) == VLM_ERR_ARG, "jobs check: no jobs");
+  CHECK(chunk_jobs_check(jobs.data(), 0, ws, ok) == VLM_ERR_ARG, "jobs check: n_jobs = 0");
+  CHECK(chunk_jobs_check(jobs.data(), 3, ws + 4, ok) == VLM_ERR_ARG && chunk_jobs_check(jobs.data(), 3, nullptr, ok) == VLM_ERR_ARG,
+        "jobs check: workspace pointer");
+  asked = 0;
+  auto second_unsupported = [&](const job_t& j) { return ++asked, &j == &jobs[1] ? (int)VLM_ERR_UNSUPPORTED : (int)VLM_OK; };
+  CHECK(chunk_jobs_check(jobs.data(), 3, ws, second_unsupported) == VLM_ERR_UNSUPPORTED && asked == 2, "jobs check: the first failing job decides");
+  jobs[0].n_elem = 0;  // an empty job is refused before its own check is asked
+  asked = 0;
+  CHECK(chunk_jobs_check(jobs.data(), 3, ws, second_unsupported) == VLM_ERR_ARG && asked == 0, "jobs check: n_elem = 0");
+}
+
 int main() {
   std::vector<job_t> ragged;
   for (uint64_t n : {1, 3, 5, 4095, 4096, 4097, 8195, 12289}) ragged.push_back({n});
   check_table("ragged", ragged);
+  check_shared_plans("ragged", ragged);
 
   // base size (hidden 768, MLP 3072): the 13 output tensors of a block, 12 blocks
   const uint64_t D = 768, F = 3072;
@@ -159,8 +264,10 @@ int main() {
     for (uint64_t n : {3 * D * D, D * D, D, D, D, F * D, F, D * F, D, D, D, D, D}) base.push_back({n});
   CHECK(base.size() == 156, "base table has %zu jobs", base.size());
   check_table("base", base);
+  check_shared_plans("base", base);
 
   check_job_checks();
+  check_jobs_check();
 
   // the common checks
   alignas(16) static char buf[32];

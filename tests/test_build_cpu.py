@@ -157,8 +157,9 @@ def test_one_fold_kernel(resources):
 
 def test_merge_family_keeps_the_occupancy_its_grids_count_on(resources):
     """The chunk walkers of merge.hip, ties.hip, dare.hip, pairstats.hip, band.hip and della.hip are one template
-    (csrc/chunk_walk.h) around each method's rule, and the radix select of ties.hip (one rank) and band.hip (two ranks) is one
-    pair of kernel templates (csrc/ties_select.h); the grids are sized from resident workgroups (one wave per SIMD each).
+    (csrc/chunk_walk.h) around each method's rule, the radix select of ties.hip (one rank) and band.hip (two ranks) is one
+    pair of kernel templates (csrc/ties_select.h), and the reducers of stock.hip, sphere.hip and sce.hip are one run
+    (csrc/chunk_records.h); the grids are sized from resident workgroups (one wave per SIMD each).
     TIES_HIST_BLOCKS_PER_CU = 4 counts on exactly four histogram workgroups per CU (registers allow four, and four times 32 KiB of
     LDS fit), with one rank and with two; TIES_APPLY_BLOCKS_PER_CU = DARE_APPLY_BLOCKS_PER_CU = 12 is four rounds of three, for
     vlm_band_apply_kernel too; vlm_merge_run's 96 per CU strides the table with at least five resident; DELLA_BLOCKS_PER_CU = 12

@@ -27,6 +27,9 @@ from pairstats_restatement import bits
 from oracle import merge_oracle as mo
 import sphere_restatement as R
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from merge_inputs import one_buffer, tiny_jobs  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -202,6 +205,34 @@ def test_sphere_same_sums_as_model_stock(merge):
     for mine, theirs in zip(results, stock.results()):
         assert bytes(mine)[:80] == bytes(theirs)[:80]  # sq[4], dot[6]
     check_jobs(jobs[:4], outs[:4], results[:4], plan)
+
+
+def test_sphere_runs_of_chunks_cross_job_boundaries(merge):
+    """2 x 12 x CUs + 7 one- and two-chunk tensor jobs of 1 .. 4099 elements and 1 .. 4 sources (helpers/merge_inputs.tiny_jobs), in
+    turn with and without a base, every input a 16-byte aligned view into one device buffer, used unstaged: every workgroup's run
+    of chunks in the reducer holds several jobs, so it loads a new first-record index at nearly every step (and the apply pass new
+    coefficients).  tiny_jobs is handed this file's `sources` as its generator, not test_ties_gpu's `planted`: planted data is
+    ill-posed for a spherical mean (its one-element jobs are exactly opposite one-dimensional sources, where the restatement's own
+    coefficients move by their whole size under a 4-ulp change of acos and its last step is 4e-3), and the coefficients are
+    compared on well-posed inputs only.  With `sources` the restatement moves by 2^-49.4 at most over these jobs."""
+    n_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    # not through tiny_jobs' one-entry cache: the planted jobs of the other files stay in it
+    data = tiny_jobs.__wrapped__(n_cus, lambda n, S, seed: sources(n, S, seed, base=seed % 2 == 0))
+    jobs = [job(c, srcs) for c, srcs in data]
+    assert [j["c"] is None for j in jobs[:4]] == [False, True, False, True]
+    views = iter(one_buffer([a for j in jobs for a in ([] if j["c"] is None else [j["c"]]) + j["srcs"]]))
+    tensors = []
+    for j in jobs:
+        base = None if j["c"] is None else next(views)
+        tensors.append((base, [next(views) for _ in j["srcs"]]))
+    outs, results, plan = run_plan(merge, jobs, tensors)
+    for pj, (base, srcs) in zip(plan.jobs, tensors):  # the views themselves, not staged copies
+        assert (pj.base or 0) == (0 if base is None else base.data_ptr())
+        assert [pj.src[m] for m in range(len(srcs))] == [s.data_ptr() for s in srcs]
+    hdr = plan.HEADER.from_buffer_copy(plan.ws[:72].cpu().numpy().tobytes())
+    assert hdr.n_tiles == 0 and hdr.n_chunks == sum(max(1, -(-(j["srcs"][0].size // 4) // 1024)) for j in jobs) > 2 * 12 * n_cus
+    check_jobs(jobs, outs, results, plan)
+    assert len({bits(r.sq[0]) for r in results}) > len(jobs) // 2  # neighbours differ in their sums: a record at a stale index would show
 
 
 def test_sphere_planted_zero_sources_and_opposite_pairs(merge):

@@ -1,11 +1,14 @@
-// The chunk plan of the merge family (merge.hip, ties.hip, dare.hip, pairstats.hip, band.hip; della.hip takes its checks, layout
-// cursor and upload and lists tiles of rows instead): every job (one tensor) is cut into 16-KiB chunks
-// listed in a device-resident table, so that ONE grid covers all tensors of a plan.  A chunk is what one 256-thread workgroup
-// moves as 4 float4 per thread; a job's ragged end (n_elem % 4 floats) rides with exactly one of its chunks.
-// This is the family's host side, stated once: the chunk table, the checks every job passes (chunk_job_check), the host image
-// "header, jobs, chunk table" (chunk_layout_t, chunk_image), its upload and the grid rule.  The device side -- the chunk walker,
-// a workgroup's run loop, the source-count dispatch -- is chunk_walk.h.
-// Everything but the upload and the grid compiles without HIP (tests/helpers/chunk_plan_check.cpp does so).
+// The chunk plan of the merge family (merge.hip, ties.hip, dare.hip, pairstats.hip, band.hip, stock.hip, sce.hip, sphere.hip,
+// tall.hip; della.hip takes its checks, layout cursor, upload and run and lists tiles of rows instead): every job (one tensor) is
+// cut into 16-KiB chunks listed in a device-resident table, so that ONE grid covers all tensors of a plan.  A chunk is what one
+// 256-thread workgroup moves as 4 float4 per thread; a job's ragged end (n_elem % 4 floats) rides with exactly one of its chunks.
+// This is the family's host side, stated once: the chunk table, the checks every job passes (chunk_job_check, chunk_jobs_check),
+// the host image "header, jobs, chunk table" (chunk_layout_t, chunk_image), its upload and the grid rule -- and the two plans
+// that several methods share whole: the COUNTER plan (header, jobs, chunks, counters per job: dare.hip, tall.hip) and the RECORD
+// plan (header, jobs, chunks, first[], one record per chunk, one result per job: pairstats.hip, stock.hip; sphere.hip puts its
+// tiles between).  The device side -- the chunk walker, a workgroup's run loop, the source-count dispatch, the counter plan's
+// view -- is chunk_walk.h; the record plan's reducer is chunk_records.h.
+// Everything but the uploads, the grid and the runs compiles without HIP (tests/helpers/chunk_plan_check.cpp does so).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -92,6 +95,37 @@ static inline uint64_t chunk_table_fill(chunk_t* ck, const Job* jobs, int n_jobs
   return c;
 }
 
+// first[i] = the chunks before job i, first[n_jobs] = the plan's chunks, which is returned: a reducer writes one record per chunk
+// at the chunk's index, and a job's records are first[i] .. first[i + 1].  `chunks(job)`: a job's chunk count (sphere_plan.h: a
+// row job has none).
+template <class Job, class Chunks>
+static inline uint64_t chunk_first_fill(const Job* jobs, int n_jobs, uint64_t* first, Chunks&& chunks) {
+  uint64_t c = 0;
+  for (int i = 0; i < n_jobs; ++i) {
+    first[i] = c;
+    c += chunks(jobs[i]);
+  }
+  first[n_jobs] = c;
+  return c;
+}
+template <class Job>
+static inline uint64_t chunk_first_fill(const Job* jobs, int n_jobs, uint64_t* first) {
+  return chunk_first_fill(jobs, n_jobs, first, [](const Job& j) { return chunks_of(j.n_elem); });
+}
+
+// The head of an upload: the arguments, then per job, in job order, "n_elem > 0" and the method's own `check(job)` (VLM_OK or
+// the code to return).  The first job that fails decides.
+template <class Job, class Check>
+static inline int chunk_jobs_check(const Job* jobs, int n_jobs, const void* workspace, Check&& check) {
+  if (!jobs || n_jobs <= 0 || !chunk_ptr_ok(workspace)) return VLM_ERR_ARG;
+  for (int i = 0; i < n_jobs; ++i) {
+    if (jobs[i].n_elem == 0) return VLM_ERR_ARG;
+    const int rc = check(jobs[i]);
+    if (rc != VLM_OK) return rc;
+  }
+  return VLM_OK;
+}
+
 // A workspace is laid out as 256-byte aligned parts, the header first: take() gives the next part's offset.
 struct chunk_layout_t {
   size_t off = 0;
@@ -101,6 +135,58 @@ struct chunk_layout_t {
     return at;
   }
 };
+
+// The parts every chunk plan begins with: the header, the jobs, the chunk table.  Returns the cursor behind them.
+template <class Hdr, class Job>
+static inline chunk_layout_t chunk_layout_head(Hdr* h, uint64_t n_jobs, uint64_t n_chunks) {
+  chunk_layout_t at;
+  at.take(sizeof(Hdr));
+  h->n_jobs = n_jobs;
+  h->n_chunks = n_chunks;
+  h->jobs_off = at.take(n_jobs * sizeof(Job));
+  h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
+  return at;
+}
+
+// The counter plan: `counters` 64-bit counters per job behind the chunk table (device-made: every run zeroes them first).
+// Fills every offset of `h`; returns the total size.
+template <class Hdr, class Job>
+static inline size_t counts_layout(Hdr* h, uint64_t n_jobs, uint64_t n_chunks, int counters) {
+  chunk_layout_t at = chunk_layout_head<Hdr, Job>(h, n_jobs, n_chunks);
+  h->counters_off = at.take(n_jobs * counters * sizeof(uint64_t));
+  return at.off;
+}
+
+template <class Hdr, class Job>
+static inline size_t counts_plan_bytes(int n_jobs, uint64_t total_elems, int counters) {
+  if (n_jobs < 0) return 0;
+  Hdr h;
+  return counts_layout<Hdr, Job>(&h, (uint64_t)n_jobs, chunks_bound(n_jobs, total_elems), counters);
+}
+
+// The record plan's own parts, appended at `at` to a header whose n_jobs and n_chunks are set: first[n_jobs + 1] (host-made),
+// then one record per chunk and one result per job (device-made: every run overwrites all of them).
+template <class Hdr>
+static inline void records_parts(chunk_layout_t& at, Hdr* h, size_t record_bytes, size_t result_bytes) {
+  h->first_off = at.take((h->n_jobs + 1) * sizeof(uint64_t));
+  h->records_off = at.take(h->n_chunks * record_bytes);
+  h->results_off = at.take(h->n_jobs * result_bytes);
+}
+
+// The record plan.  Fills every offset of `h`; returns the total size.
+template <class Hdr, class Job>
+static inline size_t records_layout(Hdr* h, uint64_t n_jobs, uint64_t n_chunks, size_t record_bytes, size_t result_bytes) {
+  chunk_layout_t at = chunk_layout_head<Hdr, Job>(h, n_jobs, n_chunks);
+  records_parts(at, h, record_bytes, result_bytes);
+  return at.off;
+}
+
+template <class Hdr, class Job>
+static inline size_t records_plan_bytes(int n_jobs, uint64_t total_elems, size_t record_bytes, size_t result_bytes) {
+  if (n_jobs < 0) return 0;
+  Hdr h;
+  return records_layout<Hdr, Job>(&h, (uint64_t)n_jobs, chunks_bound(n_jobs, total_elems), record_bytes, result_bytes);
+}
 
 // The host image of a plan: `hdr` at 0, the jobs at hdr.jobs_off, their chunk table at hdr.chunks_off, zeros up to img_bytes
 // (where a method appends tables of its own).  What lies behind img_bytes in the workspace is device-made.
@@ -142,5 +228,49 @@ static inline int chunk_upload(void* dst, const std::vector<unsigned char>& img,
 static inline dim3 chunk_grid(int per_cu) {
   const int cus = vlm_device_cus();
   return dim3((cus <= 0 ? 256 : cus) * per_cu);
+}
+
+// The counter plan's upload: chunk_jobs_check with the method's `check`, the chunk count, the workspace size, the image.
+template <class Hdr, int COUNTERS, class Job, class Check>
+static inline int counts_plan_upload(const Job* jobs, int n_jobs, void* workspace, size_t workspace_bytes, void* stream,
+                                     Check&& check) {
+  const int rc = chunk_jobs_check(jobs, n_jobs, workspace, check);
+  if (rc != VLM_OK) return rc;
+  uint64_t n_chunks = 0;
+  for (int i = 0; i < n_jobs; ++i) n_chunks += chunks_of(jobs[i].n_elem);
+  if (!chunk_count_ok(n_chunks)) return VLM_ERR_UNSUPPORTED;
+  Hdr hdr;
+  if (counts_layout<Hdr, Job>(&hdr, (uint64_t)n_jobs, n_chunks, COUNTERS) > workspace_bytes) return VLM_ERR_WORKSPACE;
+  // the host image ends where the counters begin
+  return chunk_upload(workspace, chunk_image(hdr, jobs, n_jobs, hdr.counters_off), 0, (hipStream_t)stream);
+}
+
+// The counter plan's run (della.hip's too): the clear and the apply pass, two launches, stream-ordered, no host
+// synchronisation -- the sizes of the plan live in the workspace header.
+static inline int counts_run(void* workspace, void* stream, void (*clear_kernel)(unsigned char*),
+                             void (*apply_kernel)(unsigned char*), dim3 apply_grid) {
+  if (!workspace) return VLM_ERR_ARG;
+  unsigned char* ws = (unsigned char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(clear_kernel, dim3(64), dim3(CHUNK_THREADS), 0, s, ws);
+  hipLaunchKernelGGL(apply_kernel, apply_grid, dim3(CHUNK_THREADS), 0, s, ws);
+  if (hipGetLastError() != hipSuccess) return VLM_ERR_LAUNCH;
+  return VLM_OK;
+}
+
+// The record plan's upload: as the counter plan's, with first[] in the image, which ends where the records begin.
+template <class Hdr, class Job, class Check>
+static inline int records_plan_upload(const Job* jobs, int n_jobs, void* workspace, size_t workspace_bytes, void* stream,
+                                      size_t record_bytes, size_t result_bytes, Check&& check) {
+  const int rc = chunk_jobs_check(jobs, n_jobs, workspace, check);
+  if (rc != VLM_OK) return rc;
+  std::vector<uint64_t> first((size_t)n_jobs + 1);
+  const uint64_t n_chunks = chunk_first_fill(jobs, n_jobs, first.data());
+  if (!chunk_count_ok(n_chunks)) return VLM_ERR_UNSUPPORTED;
+  Hdr hdr;
+  if (records_layout<Hdr, Job>(&hdr, (uint64_t)n_jobs, n_chunks, record_bytes, result_bytes) > workspace_bytes) return VLM_ERR_WORKSPACE;
+  std::vector<unsigned char> img = chunk_image(hdr, jobs, n_jobs, hdr.records_off);
+  memcpy(img.data() + hdr.first_off, first.data(), first.size() * sizeof(uint64_t));
+  return chunk_upload(workspace, img, 0, (hipStream_t)stream);
 }
 #endif

@@ -5,7 +5,8 @@
 //   chunk_run      the contiguous run of chunks a workgroup owns, with "entering job" / "leaving job" callbacks
 // and what ties.hip, dare.hip, band.hip and della.hip share per element and per workgroup: the combine rule (LINEAR: the sum;
 // TIES: steps 3-5 of the TIES rule, include/vlm_hip.h) on entries tt_m that a kernel has already trimmed (TIES, band: by
-// magnitude; DARE, DELLA: by their Philox masks), the per-thread counters, their flush (integer atomics only) and their clear.
+// magnitude; DARE, DELLA: by their Philox masks), the per-thread counters, their flush (integer atomics only) and their clear,
+// and the view of a counter plan's workspace (dare.hip, tall.hip).  What the reducers share is chunk_records.h.
 // Device code only.
 #pragma once
 #include "vlm_common.h"
@@ -183,7 +184,26 @@ __device__ __forceinline__ float combine(float c, const float* tt, int any, floa
   return __fadd_rn(c, __fmul_rn(lam, d));
 }
 
-// the body of DARE's and DELLA's clear launch: the counters of every job start the run at zero
+// A counter plan's workspace (chunk_plan.h: counts_layout) as the kernels of dare.hip and tall.hip see it.
+template <class Hdr, class Job>
+struct counts_view_t {
+  const Hdr* hdr;
+  const Job* jobs;
+  const chunk_t* chunks;
+  u64_t* counters;
+};
+
+template <class Hdr, class Job>
+__device__ __forceinline__ counts_view_t<Hdr, Job> counts_view(unsigned char* ws) {
+  counts_view_t<Hdr, Job> v;
+  v.hdr = reinterpret_cast<const Hdr*>(ws);
+  v.jobs = reinterpret_cast<const Job*>(ws + v.hdr->jobs_off);
+  v.chunks = reinterpret_cast<const chunk_t*>(ws + v.hdr->chunks_off);
+  v.counters = reinterpret_cast<u64_t*>(ws + v.hdr->counters_off);
+  return v;
+}
+
+// the body of DARE's, TALL's and DELLA's clear launch: the counters of every job start the run at zero
 __device__ __forceinline__ void chunk_clear_counts(u64_t* counters, uint64_t total) {
   for (uint64_t i = (uint64_t)blockIdx.x * CHUNK_THREADS + threadIdx.x; i < total; i += (uint64_t)gridDim.x * CHUNK_THREADS)
     counters[i] = 0;

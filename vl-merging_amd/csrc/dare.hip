@@ -11,8 +11,8 @@
 //                           rule, and the per-job counters flushed (64-bit integer atomics) when the run leaves a job.
 // Steps 4-5 (both modes) are chunk_walk.h's combine rule, shared with ties.hip, band.hip and della.hip.  Integer counters
 // only, so nothing depends on the order workgroups run in.  -ffp-contract=off and __f*_rn: one rounding per operation, no FMA.
-// This file holds the rule (dare_elem, the draws) and the workspace layout; the walker, the run loop and the host checks are
-// chunk_walk.h's and chunk_plan.h's, as in ties.hip.
+// This file holds the rule (dare_elem, the draws) and its own per-job check; the walker, the run loop and the workspace's view
+// are chunk_walk.h's, the counter plan (layout, upload, the two-launch run) and the family's host checks chunk_plan.h's.
 #include "vlm_common.h"
 #include "philox.h"
 #include "chunk_walk.h"  // the chunk walker, the run loop, the combine rule and the counters: the whole family's
@@ -22,21 +22,7 @@
 
 static_assert(VLM_DARE_COUNTERS == VLM_TIES_COUNTERS, "dare.hip counts into chunk_walk.h's ties_counts_t");
 
-struct dare_view_t {
-  const vlm_dare_header_t* hdr;
-  const vlm_dare_job_t* jobs;
-  const chunk_t* chunks;
-  u64_t* counters;
-};
-
-__device__ __forceinline__ dare_view_t dare_view(unsigned char* ws) {
-  dare_view_t v;
-  v.hdr = reinterpret_cast<const vlm_dare_header_t*>(ws);
-  v.jobs = reinterpret_cast<const vlm_dare_job_t*>(ws + v.hdr->jobs_off);
-  v.chunks = reinterpret_cast<const chunk_t*>(ws + v.hdr->chunks_off);
-  v.counters = reinterpret_cast<u64_t*>(ws + v.hdr->counters_off);
-  return v;
-}
+typedef counts_view_t<vlm_dare_header_t, vlm_dare_job_t> dare_view_t;
 
 // what a job's scalars come to, workgroup-uniform
 struct dare_param_t {
@@ -87,13 +73,13 @@ struct dare_rule {
 };
 
 __global__ __launch_bounds__(DARE_THREADS) void vlm_dare_clear_kernel(unsigned char* __restrict__ ws) {
-  const dare_view_t w = dare_view(ws);
+  const dare_view_t w = counts_view<vlm_dare_header_t, vlm_dare_job_t>(ws);
   chunk_clear_counts(w.counters, w.hdr->n_jobs * VLM_DARE_COUNTERS);
 }
 
 __global__ __launch_bounds__(DARE_THREADS) void vlm_dare_apply_kernel(unsigned char* __restrict__ ws) {
   __shared__ u64_t red[(DARE_THREADS / 64) * VLM_DARE_COUNTERS];
-  const dare_view_t w = dare_view(ws);
+  const dare_view_t w = counts_view<vlm_dare_header_t, vlm_dare_job_t>(ws);
   uint64_t c0, c1;
   if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
   ties_counts_t n;
@@ -125,51 +111,19 @@ __global__ __launch_bounds__(DARE_THREADS) void vlm_dare_apply_kernel(unsigned c
       [&](uint32_t cur) { chunk_flush_counts(n.c, red, w.counters + (uint64_t)cur * VLM_DARE_COUNTERS); });
 }
 
-// fills every offset of `h` for n_jobs jobs and n_chunks chunks; returns the total size
-static size_t dare_layout(vlm_dare_header_t* h, uint64_t n_jobs, uint64_t n_chunks) {
-  chunk_layout_t at;
-  at.take(sizeof(vlm_dare_header_t));
-  h->n_jobs = n_jobs;
-  h->n_chunks = n_chunks;
-  h->jobs_off = at.take(n_jobs * sizeof(vlm_dare_job_t));
-  h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
-  h->counters_off = at.take(n_jobs * VLM_DARE_COUNTERS * sizeof(uint64_t));
-  return at.off;
-}
-
 extern "C" size_t vlm_dare_plan_bytes(int n_jobs, uint64_t total_elems) {
-  if (n_jobs < 0) return 0;
-  vlm_dare_header_t h;
-  return dare_layout(&h, (uint64_t)n_jobs, chunks_bound(n_jobs, total_elems));
+  return counts_plan_bytes<vlm_dare_header_t, vlm_dare_job_t>(n_jobs, total_elems, VLM_DARE_COUNTERS);
 }
 
 extern "C" int vlm_dare_plan_upload(const vlm_dare_job_t* jobs, int n_jobs, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-  if (!jobs || n_jobs <= 0 || !chunk_ptr_ok(workspace)) return VLM_ERR_ARG;
-  uint64_t n_chunks = 0;
-  for (int i = 0; i < n_jobs; ++i) {
-    const vlm_dare_job_t& j = jobs[i];
-    if (j.n_elem == 0 || (j.mode != VLM_DARE_LINEAR && j.mode != VLM_DARE_TIES)) return VLM_ERR_ARG;
+  return counts_plan_upload<vlm_dare_header_t, VLM_DARE_COUNTERS>(jobs, n_jobs, workspace, workspace_bytes, stream, [](const vlm_dare_job_t& j) {
+    if (j.mode != VLM_DARE_LINEAR && j.mode != VLM_DARE_TIES) return VLM_ERR_ARG;
     if (j.keep_below < 1 || j.keep_below > (1ull << 32)) return VLM_ERR_ARG;
-    const int rc = chunk_job_check(j, CHUNK_OVERLAP_EXACT, true);
-    if (rc != VLM_OK) return rc;
-    n_chunks += chunks_of(j.n_elem);
-  }
-  if (!chunk_count_ok(n_chunks)) return VLM_ERR_UNSUPPORTED;
-  vlm_dare_header_t hdr;
-  const size_t total = dare_layout(&hdr, (uint64_t)n_jobs, n_chunks);
-  if (total > workspace_bytes) return VLM_ERR_WORKSPACE;
-  // the host image ends where the counters begin: they are device-made (every run zeroes them first)
-  return chunk_upload(workspace, chunk_image(hdr, jobs, n_jobs, hdr.counters_off), 0, (hipStream_t)stream);
+    return chunk_job_check(j, CHUNK_OVERLAP_EXACT, true);
+  });
 }
 
 extern "C" int vlm_dare_run(void* workspace, void* stream) {
-  if (!workspace) return VLM_ERR_ARG;
-  unsigned char* ws = (unsigned char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  // two launches, stream-ordered, no host synchronisation: the sizes of the plan live in the workspace header
-  hipLaunchKernelGGL(vlm_dare_clear_kernel, dim3(64), dim3(DARE_THREADS), 0, s, ws);
-  hipLaunchKernelGGL(vlm_dare_apply_kernel, chunk_grid(DARE_APPLY_BLOCKS_PER_CU), dim3(DARE_THREADS), 0, s, ws);
-  VLM_CHECK_LAUNCH();
-  return VLM_OK;
+  return counts_run(workspace, stream, vlm_dare_clear_kernel, vlm_dare_apply_kernel, chunk_grid(DARE_APPLY_BLOCKS_PER_CU));
 }

@@ -20,7 +20,9 @@
 // a Philox block, so the scalar path draws the block of each element's own flat index.
 // Integer counters only, so nothing depends on the order workgroups run in.  -ffp-contract=off and __f*_rn: one rounding per
 // operation, no FMA.  The source-count dispatch, the combine rule (steps 6-7), the run loop, the counter flush and clear are
-// chunk_walk.h's, the per-job checks, the layout cursor and the upload chunk_plan.h's.
+// chunk_walk.h's, the per-job checks, the layout cursor, the upload and the two-launch run chunk_plan.h's.  The workspace's view and
+// layout stay this file's own: its header names tiles (n_tiles, tiles_off) where the counter plan of dare.hip and tall.hip names
+// chunks, and the shared forms would need a parameter that exists for this file alone.
 #include "vlm_common.h"
 #include "philox.h"
 #include "chunk_walk.h"
@@ -353,12 +355,5 @@ extern "C" int vlm_della_plan_upload(const vlm_della_job_t* jobs, int n_jobs, vo
 }
 
 extern "C" int vlm_della_run(void* workspace, void* stream) {
-  if (!workspace) return VLM_ERR_ARG;
-  unsigned char* ws = (unsigned char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  // two launches, stream-ordered, no host synchronisation: the sizes of the plan live in the workspace header
-  hipLaunchKernelGGL(vlm_della_clear_kernel, dim3(64), dim3(DELLA_THREADS), 0, s, ws);
-  hipLaunchKernelGGL(vlm_della_apply_kernel, chunk_grid(DELLA_BLOCKS_PER_CU), dim3(DELLA_THREADS), 0, s, ws);
-  VLM_CHECK_LAUNCH();
-  return VLM_OK;
+  return counts_run(workspace, stream, vlm_della_clear_kernel, vlm_della_apply_kernel, chunk_grid(DELLA_BLOCKS_PER_CU));
 }

@@ -1,19 +1,18 @@
-// The Gram reducer that Model Stock (stock.hip) and the spherical merge (sphere.hip) share: per job of S sources the sums
-// sq[S] and dot[S (S - 1) / 2] of the task vectors, in the pinned order of step 2 of the Model Stock rule (include/vlm_hip.h):
-// thread, wave by halves, ((w0 + w1) + w2) + w3, one record per chunk at the chunk's index, the records added in chunk order,
-// every sum from +0.0.  Generic over the job type (fields base, src, n_src, n_elem) and over whether the job has a base: without
-// one, chunk_stream hands elem() c = +0.0 and W - (+0.0) is W, bit for bit.
+// The Gram rule that Model Stock (stock.hip) and the spherical merge (sphere.hip) reduce with: per job of S sources the sums
+// sq[S] and dot[S (S - 1) / 2] of the task vectors, step 2 of the Model Stock rule (include/vlm_hip.h).  This file holds what a
+// thread adds per element and what a chunk leaves per wave; the pinned order behind that -- the wave fold, the record per chunk,
+// the run of chunks, the fold of a job's records -- is chunk_records.h's.  Generic over the job type (fields base, src, n_src,
+// n_elem) and over whether the job has a base: without one, chunk_stream hands elem() c = +0.0 and W - (+0.0) is W, bit for bit.
 // Device code only.  -ffp-contract=off and the __d*_rn forms: one rounding per operation, no FMA.
 #pragma once
 #include "vlm_common.h"
 #include "chunk_walk.h"
+#include "chunk_records.h"
 
 #define STOCK_THREADS CHUNK_THREADS
-#define STOCK_WAVES (STOCK_THREADS / 64)
 #define STOCK_PAIRS VLM_PAIRSTATS_PAIRS
 #define STOCK_SUMS VLM_STOCK_SUMS      // a record: sq[4], then dot[6]
 #define STOCK_FOLD_THREADS 64          // lanes 0 .. 9 add one sum each; lane 0 then does step 3
-#define STOCK_FOLD_BATCH 16            // records whose loads are in flight together in the fold (the additions stay in order)
 
 static_assert(STOCK_PAIRS == VLM_MERGE_MAX_SRC * (VLM_MERGE_MAX_SRC - 1) / 2, "one slot per pair");
 static_assert(STOCK_SUMS == 10, "a record is four squared norms and six dot products");
@@ -56,14 +55,6 @@ struct stock_reduce_rule {
   }
 };
 
-// the wave fold by halves: lane 0 ends with the pinned tree's value (a + b is commutative, so the butterfly's lane 0 is the tree's
-// -- and every other lane's: all 64 end with the same bytes)
-__device__ __forceinline__ double stock_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 // does a job of S sources have the sum at `slot` (0 .. STOCK_SUMS)?
 __device__ __forceinline__ bool stock_slot_used(int slot, int S) {
   return slot < VLM_MERGE_MAX_SRC ? slot < S : slot - VLM_MERGE_MAX_SRC < S * (S - 1) / 2;
@@ -80,37 +71,12 @@ __device__ __forceinline__ void stock_chunk(const Job& j, uint64_t start4, doubl
   double* r = red + wave * STOCK_SUMS;
 #pragma unroll
   for (int m = 0; m < S; ++m) {
-    const double v = stock_wave_sum(n.sq[m]);
+    const double v = chunk_wave_sum(n.sq[m]);
     if (lane == 0) r[m] = v;
   }
 #pragma unroll
   for (int p = 0; p < stock_acc_t<S>::NP; ++p) {
-    const double v = stock_wave_sum(n.dot[p]);
+    const double v = chunk_wave_sum(n.dot[p]);
     if (lane == 0) r[VLM_MERGE_MAX_SRC + p] = v;
   }
 }
-
-// The record of the chunk at start4 of a job whose first record is `first`, from the wave sums r[wave][slot] (behind a barrier):
-// threads 0 .. 9 add ((w0 + w1) + w2) + w3; the sums the job does not have are zero.  The record index is the chunk index.
-__device__ __forceinline__ void stock_record(const double* r, int n_src, double* records, uint64_t first, uint64_t start4) {
-  if (threadIdx.x < STOCK_SUMS) {
-    const int k = threadIdx.x;
-    double t = 0.0;
-    if (stock_slot_used(k, n_src)) {
-      t = r[k];
-#pragma unroll
-      for (int wv = 1; wv < STOCK_WAVES; ++wv) t = __dadd_rn(t, r[wv * STOCK_SUMS + k]);
-    }
-    records[(first + (start4 / (CHUNK_FLOATS / 4))) * STOCK_SUMS + k] = t;
-  }
-}
-
-// A job's sum at one slot: `sum` (a double at +0.0) receives the records c0 .. c1 added in chunk order.  `rec`: the slot's place in
-// record 0.  A macro, not a function: as an inlined function the loop is rotated otherwise, and vlm_stock_fold_kernel keeps the
-// instructions it had when the loop stood in it.
-#define STOCK_FOLD_RECORDS(sum, rec, c0, c1)                                                                                   \
-  for (uint64_t c = (c0); c < (c1); c += STOCK_FOLD_BATCH) {                                                                   \
-    double v[STOCK_FOLD_BATCH];                                                                                                \
-    _Pragma("unroll") for (int i = 0; i < STOCK_FOLD_BATCH; ++i) v[i] = c + i < (c1) ? (rec)[(c + i) * STOCK_SUMS] : 0.0;      \
-    _Pragma("unroll") for (int i = 0; i < STOCK_FOLD_BATCH; ++i) sum = __dadd_rn(sum, v[i]);                                   \
-  }

@@ -12,18 +12,17 @@
 //   vlm_pairstats_fold_kernel    one workgroup per job at a time, one thread per statistic: the job's records added in chunk order.
 // No atomics; every record and every result is overwritten by each run, so nothing is cleared.  -ffp-contract=off and the
 // __f*_rn / __d*_rn forms: one rounding per operation, no FMA.
-// This file holds the rule (pairstats_rule), the two reductions and the workspace layout; the walker, the run loop and the
-// host checks are chunk_walk.h's and chunk_plan.h's, as in dare.hip.
+// This file holds the rule (pairstats_rule) and the two reductions; the walker and the run loop are chunk_walk.h's, the wave fold
+// and the workspace's view chunk_records.h's, the record plan (layout, upload) and the host checks chunk_plan.h's.
 #include "vlm_common.h"
 #include "chunk_walk.h"
+#include "chunk_records.h"  // the view and the wave fold (the record writer and the fold are this file's own: see below)
 
 #define PS_THREADS CHUNK_THREADS
-#define PS_WAVES (PS_THREADS / 64)
 #define PS_PAIRS VLM_PAIRSTATS_PAIRS
 #define PS_HALF (VLM_MERGE_MAX_SRC + 4 * PS_PAIRS)  // 28 doubles, then 28 counts: vlm_pairstats_result_t as 56 8-byte slots
 #define PS_SLOTS (2 * PS_HALF)
 #define PS_FOLD_THREADS 128           // wave 0: the doubles, wave 1: the counts
-#define PS_FOLD_BATCH 16              // records whose loads are in flight together in the fold (the additions stay in order)
 // Just under 256 registers: two workgroups per CU are resident (tests/test_pairstats_cpu.py watches the occupancy); six rounds of
 // them keep the runs short enough to even out their ends.  Measured against 2, 4, 8 and 16: docs/experiments.md, "Pair statistics".
 #define PS_BLOCKS_PER_CU 12
@@ -31,24 +30,10 @@
 static_assert(sizeof(vlm_pairstats_result_t) == PS_SLOTS * 8, "a result is 56 8-byte slots");
 static_assert(PS_PAIRS == VLM_MERGE_MAX_SRC * (VLM_MERGE_MAX_SRC - 1) / 2, "one slot per pair");
 
-struct ps_view_t {
-  const vlm_pairstats_header_t* hdr;
-  const vlm_pairstats_job_t* jobs;
-  const chunk_t* chunks;
-  const uint64_t* first;
-  u64_t* records;  // [n_chunks][PS_SLOTS], doubles as their bits
-  u64_t* results;  // [n_jobs][PS_SLOTS]
-};
-
+// records: [n_chunks][PS_SLOTS], results: [n_jobs][PS_SLOTS], doubles as their bits
+typedef records_view_t<vlm_pairstats_header_t, vlm_pairstats_job_t, u64_t, u64_t> ps_view_t;
 __device__ __forceinline__ ps_view_t ps_view(unsigned char* ws) {
-  ps_view_t v;
-  v.hdr = reinterpret_cast<const vlm_pairstats_header_t*>(ws);
-  v.jobs = reinterpret_cast<const vlm_pairstats_job_t*>(ws + v.hdr->jobs_off);
-  v.chunks = reinterpret_cast<const chunk_t*>(ws + v.hdr->chunks_off);
-  v.first = reinterpret_cast<const uint64_t*>(ws + v.hdr->first_off);
-  v.records = reinterpret_cast<u64_t*>(ws + v.hdr->records_off);
-  v.results = reinterpret_cast<u64_t*>(ws + v.hdr->results_off);
-  return v;
+  return records_view<vlm_pairstats_header_t, vlm_pairstats_job_t, u64_t, u64_t>(ws);
 }
 
 // A thread's sums over one chunk, for a job of S sources: NP = S (S - 1) / 2 pairs, pair (a, b) at b (b - 1) / 2 + a < NP.
@@ -116,18 +101,6 @@ struct pairstats_rule {
   }
 };
 
-// the wave fold by halves: lane 0 ends with the pinned tree's value (a + b is commutative, so the butterfly's lane 0 is the tree's)
-__device__ __forceinline__ double ps_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ uint32_t ps_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // Wave sums of the thread's statistics into red[wave][slot] (lane 0 writes; the slots are vlm_pairstats_result_t's order).
 template <int S>
 __device__ __forceinline__ void ps_wave_fold(const ps_acc_t<S>& n, u64_t* red) {
@@ -135,11 +108,11 @@ __device__ __forceinline__ void ps_wave_fold(const ps_acc_t<S>& n, u64_t* red) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   u64_t* r = red + wave * PS_SLOTS;
   auto put_d = [&](int slot, double v) {
-    v = ps_wave_sum(v);
+    v = chunk_wave_sum(v);
     if (lane == 0) r[slot] = (u64_t)__double_as_longlong(v);
   };
   auto put_n = [&](int slot, uint32_t v) {
-    v = ps_wave_sum(v);
+    v = chunk_wave_sum(v);
     if (lane == 0) r[PS_HALF + slot] = v;
   };
 #pragma unroll
@@ -177,7 +150,7 @@ __device__ __forceinline__ void ps_chunk(const vlm_pairstats_job_t& j, uint64_t 
 
 __global__ __launch_bounds__(PS_THREADS) void vlm_pairstats_stream_kernel(unsigned char* __restrict__ ws) {
   // two buffers, used in turn: a chunk's wave sums are read behind ONE barrier while the next chunk's are written to the other
-  __shared__ u64_t red[2][PS_WAVES * PS_SLOTS];
+  __shared__ u64_t red[2][RECORD_WAVES * PS_SLOTS];
   const ps_view_t w = ps_view(ws);
   uint64_t c0, c1;
   if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
@@ -199,6 +172,8 @@ __global__ __launch_bounds__(PS_THREADS) void vlm_pairstats_stream_kernel(unsign
           else ps_chunk<S(), false>(j, start4, tkey, r);
         });
         __syncthreads();
+        // This record writer (and the run around it) stays this file's own beside chunk_records.h's chunk_record and
+        // chunk_reduce_run: a record here mixes doubles (as their bits) and counts in 8-byte slots, and the shared writer adds doubles.
         if (threadIdx.x < PS_SLOTS) {  // ((w0 + w1) + w2) + w3; the statistics the job does not have are zero
           const int k = threadIdx.x;
           u64_t out = 0;
@@ -206,11 +181,11 @@ __global__ __launch_bounds__(PS_THREADS) void vlm_pairstats_stream_kernel(unsign
             if (k < PS_HALF) {
               double t = __longlong_as_double((long long)r[k]);
 #pragma unroll
-              for (int wv = 1; wv < PS_WAVES; ++wv) t = __dadd_rn(t, __longlong_as_double((long long)r[wv * PS_SLOTS + k]));
+              for (int wv = 1; wv < RECORD_WAVES; ++wv) t = __dadd_rn(t, __longlong_as_double((long long)r[wv * PS_SLOTS + k]));
               out = (u64_t)__double_as_longlong(t);
             } else {
 #pragma unroll
-              for (int wv = 0; wv < PS_WAVES; ++wv) out += r[wv * PS_SLOTS + k];
+              for (int wv = 0; wv < RECORD_WAVES; ++wv) out += r[wv * PS_SLOTS + k];
             }
           }
           w.records[(first + (start4 / (CHUNK_FLOATS / 4))) * PS_SLOTS + k] = out;  // the record index is the chunk index
@@ -231,12 +206,12 @@ __global__ __launch_bounds__(PS_FOLD_THREADS) void vlm_pairstats_fold_kernel(uns
     const uint64_t c0 = w.first[job], c1 = w.first[job + 1];
     double sum = 0.0;
     u64_t cnt = 0;
-    for (uint64_t c = c0; c < c1; c += PS_FOLD_BATCH) {
-      u64_t v[PS_FOLD_BATCH];
+    for (uint64_t c = c0; c < c1; c += RECORD_FOLD_BATCH) {
+      u64_t v[RECORD_FOLD_BATCH];
 #pragma unroll
-      for (int i = 0; i < PS_FOLD_BATCH; ++i) v[i] = c + i < c1 ? rec[(c + i) * PS_SLOTS] : 0;  // +0.0 or 0: changes no sum
+      for (int i = 0; i < RECORD_FOLD_BATCH; ++i) v[i] = c + i < c1 ? rec[(c + i) * PS_SLOTS] : 0;  // +0.0 or 0: changes no sum
 #pragma unroll
-      for (int i = 0; i < PS_FOLD_BATCH; ++i) {
+      for (int i = 0; i < RECORD_FOLD_BATCH; ++i) {
         if (wave == 0) sum = __dadd_rn(sum, __longlong_as_double((long long)v[i]));
         else cnt += v[i];
       }
@@ -245,48 +220,16 @@ __global__ __launch_bounds__(PS_FOLD_THREADS) void vlm_pairstats_fold_kernel(uns
   }
 }
 
-// fills every offset of `h` for n_jobs jobs and n_chunks chunks; returns the total size
-static size_t ps_layout(vlm_pairstats_header_t* h, uint64_t n_jobs, uint64_t n_chunks) {
-  chunk_layout_t at;
-  at.take(sizeof(vlm_pairstats_header_t));
-  h->n_jobs = n_jobs;
-  h->n_chunks = n_chunks;
-  h->jobs_off = at.take(n_jobs * sizeof(vlm_pairstats_job_t));
-  h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
-  h->first_off = at.take((n_jobs + 1) * sizeof(uint64_t));
-  h->records_off = at.take(n_chunks * sizeof(vlm_pairstats_result_t));
-  h->results_off = at.take(n_jobs * sizeof(vlm_pairstats_result_t));
-  return at.off;
-}
-
 extern "C" size_t vlm_pairstats_plan_bytes(int n_jobs, uint64_t total_elems) {
-  if (n_jobs < 0) return 0;
-  vlm_pairstats_header_t h;
-  return ps_layout(&h, (uint64_t)n_jobs, chunks_bound(n_jobs, total_elems));
+  return records_plan_bytes<vlm_pairstats_header_t, vlm_pairstats_job_t>(n_jobs, total_elems, sizeof(vlm_pairstats_result_t),
+                                                                         sizeof(vlm_pairstats_result_t));
 }
 
 extern "C" int vlm_pairstats_plan_upload(const vlm_pairstats_job_t* jobs, int n_jobs, void* workspace, size_t workspace_bytes,
                                          void* stream) {
-  if (!jobs || n_jobs <= 0 || !chunk_ptr_ok(workspace)) return VLM_ERR_ARG;
-  std::vector<uint64_t> first((size_t)n_jobs + 1);
-  uint64_t n_chunks = 0;
-  for (int i = 0; i < n_jobs; ++i) {
-    const vlm_pairstats_job_t& j = jobs[i];
-    if (j.n_elem == 0) return VLM_ERR_ARG;
-    const int rc = chunk_job_check<false>(j, CHUNK_OVERLAP_UNCHECKED, false);  // no dst: nothing for an input to overlap
-    if (rc != VLM_OK) return rc;
-    first[i] = n_chunks;
-    n_chunks += chunks_of(j.n_elem);
-  }
-  first[n_jobs] = n_chunks;
-  if (!chunk_count_ok(n_chunks)) return VLM_ERR_UNSUPPORTED;
-  vlm_pairstats_header_t hdr;
-  const size_t total = ps_layout(&hdr, (uint64_t)n_jobs, n_chunks);
-  if (total > workspace_bytes) return VLM_ERR_WORKSPACE;
-  // the host image ends where the records begin: they and the results are device-made (every run overwrites all of them)
-  std::vector<unsigned char> img = chunk_image(hdr, jobs, n_jobs, hdr.records_off);
-  memcpy(img.data() + hdr.first_off, first.data(), first.size() * sizeof(uint64_t));
-  return chunk_upload(workspace, img, 0, (hipStream_t)stream);
+  return records_plan_upload<vlm_pairstats_header_t>(
+      jobs, n_jobs, workspace, workspace_bytes, stream, sizeof(vlm_pairstats_result_t), sizeof(vlm_pairstats_result_t),
+      [](const vlm_pairstats_job_t& j) { return chunk_job_check<false>(j, CHUNK_OVERLAP_UNCHECKED, false); });  // no dst: nothing for an input to overlap
 }
 
 extern "C" int vlm_pairstats_run(void* workspace, void* stream) {

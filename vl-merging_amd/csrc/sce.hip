@@ -19,18 +19,19 @@
 // a run streams the inputs FIVE times, 4 (S + 1) B per element and pass, and writes 4 B per element once: that is the bound.
 // -ffp-contract=off and the __f*_rn / __d*_rn forms: one rounding per operation, no FMA.
 // This file holds what is SCE's own: what the select needs to know of its job and state (sce_sel), the variance key, the three
-// kernels and the run.  The select, the workspace layout and the upload are ties_select.h's (shared with ties.hip and band.hip);
-// the chunk walker, the run loop and the counter flush are chunk_walk.h's; the chunk table, the family's per-job checks, the host
-// image, the upload and the grid rule are chunk_plan.h's.
+// kernels and the run.  The select, its six launches, the workspace layout and the upload are ties_select.h's (shared with ties.hip
+// and band.hip); the reducer's wave and workgroup folds, its run and the fold of a job's records are chunk_records.h's (shared with
+// stock.hip and sphere.hip); the chunk walker, the run loop and the counter flush are chunk_walk.h's; the chunk table, the family's
+// per-job checks, the host image, the upload and the grid rule are chunk_plan.h's.
 #include "vlm_common.h"
 #include "chunk_walk.h"
+#include "chunk_records.h"
 #include "ties_select.h"
 
 #define SCE_THREADS CHUNK_THREADS
 #define SCE_WAVES (SCE_THREADS / 64)
 #define SCE_SUMS VLM_MERGE_MAX_SRC  // a record: sq[4]
 #define SCE_FOLD_THREADS 64         // lanes 0 .. 3 add one sum each; lane 0 then does step 5
-#define SCE_FOLD_BATCH 16           // records whose loads are in flight together in the fold (the additions stay in order)
 // Workgroups per CU of the three grids.  Each starts from the kernel's resident-workgroup count as the build records it
 // (tests/test_sce_cpu.py watches the registers and the LDS these counts assume) times a whole number of rounds, and each was then timed
 // against its neighbours at base size, two alternating rounds in one visit (docs/experiments.md, "SCE merge"; a run is 1.057 ms):
@@ -126,13 +127,6 @@ struct sce_reduce_rule {
   }
 };
 
-// the wave fold by halves: lane 0 ends with the pinned tree's value (a + b is commutative, so the butterfly's lane 0 is the tree's)
-__device__ __forceinline__ double sce_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 // one chunk's sums, then their wave sums into red[wave][m] (lane 0 writes)
 template <int S>
 __device__ __forceinline__ void sce_chunk(const vlm_sce_job_t& j, uint64_t start4, const uint32_t& thr, double* red) {
@@ -144,43 +138,18 @@ __device__ __forceinline__ void sce_chunk(const vlm_sce_job_t& j, uint64_t start
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int m = 0; m < S; ++m) {
-    const double v = sce_wave_sum(sq[m]);
+    const double v = chunk_wave_sum(sq[m]);
     if (lane == 0) red[wave * SCE_SUMS + m] = v;
   }
 }
 
 __global__ __launch_bounds__(SCE_THREADS) void vlm_sce_reduce_kernel(unsigned char* __restrict__ ws) {
-  // two buffers, used in turn: a chunk's wave sums are read behind ONE barrier while the next chunk's are written to the other
-  __shared__ double red[2][SCE_WAVES * SCE_SUMS];
   const sce_view_t w = sce_view(ws);
-  uint64_t c0, c1;
-  if (!chunk_my_run(w.s.hdr->n_chunks, &c0, &c1)) return;
-  uint64_t first = 0;
-  uint32_t thr = 0;
-  int turn = 0;
-  chunk_run(
-      w.s.chunks, w.s.jobs, c0, c1,
-      [&](uint32_t cur) {
-        first = w.first[cur];
-        thr = w.s.state[w.s.unit0[cur]].key;
-      },
-      [&](const vlm_sce_job_t& j, uint64_t start4) {
-        double* r = red[turn];
-        with_nsrc(j.n_src, [&](auto S) { sce_chunk<S()>(j, start4, thr, r); });
-        __syncthreads();
-        if (threadIdx.x < SCE_SUMS) {  // ((w0 + w1) + w2) + w3; the sums the job does not have are zero
-          const int k = threadIdx.x;
-          double t = 0.0;
-          if (k < j.n_src) {
-            t = r[k];
-#pragma unroll
-            for (int wv = 1; wv < SCE_WAVES; ++wv) t = __dadd_rn(t, r[wv * SCE_SUMS + k]);
-          }
-          w.records[(first + (start4 / (CHUNK_FLOATS / 4))) * SCE_SUMS + k] = t;  // the record index is the chunk index
-        }
-        turn ^= 1;
-      },
-      [&](uint32_t) {});
+  uint32_t thr = 0;  // the job's threshold, loaded on entering it
+  chunk_reduce_run<SCE_SUMS>(
+      w.s.chunks, w.s.jobs, w.s.hdr->n_chunks, w.first, w.records, [&](uint32_t cur) { thr = w.s.state[w.s.unit0[cur]].key; },
+      [&](const vlm_sce_job_t& j, uint64_t start4, double* r) { with_nsrc(j.n_src, [&](auto S) { sce_chunk<S()>(j, start4, thr, r); }); },
+      [](const vlm_sce_job_t& j, int k) { return k < j.n_src; });
 }
 
 __global__ __launch_bounds__(SCE_FOLD_THREADS) void vlm_sce_fold_kernel(unsigned char* __restrict__ ws) {
@@ -193,13 +162,7 @@ __global__ __launch_bounds__(SCE_FOLD_THREADS) void vlm_sce_fold_kernel(unsigned
       const double* rec = w.records + k;
       const uint64_t c0 = w.first[job], c1 = w.first[job + 1];
       double sum = 0.0;
-      for (uint64_t c = c0; c < c1; c += SCE_FOLD_BATCH) {
-        double v[SCE_FOLD_BATCH];
-#pragma unroll
-        for (int i = 0; i < SCE_FOLD_BATCH; ++i) v[i] = c + i < c1 ? rec[(c + i) * SCE_SUMS] : 0.0;  // +0.0: changes no sum
-#pragma unroll
-        for (int i = 0; i < SCE_FOLD_BATCH; ++i) sum = __dadd_rn(sum, v[i]);
-      }
+      CHUNK_FOLD_RECORDS(sum, rec, SCE_SUMS, c0, c1);
       sums[k] = sum;
     }
     __syncthreads();
@@ -308,13 +271,8 @@ extern "C" int vlm_sce_run(void* workspace, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   // nine launches, stream-ordered, no host synchronisation: the sizes of the plan live in the workspace header, the threshold the
   // reducer reads in the state the last bin pick has written, the weights the apply pass reads in the result the fold has written
-  const dim3 block(SCE_THREADS), hist_grid = chunk_grid(SCE_HIST_BLOCKS_PER_CU), scan_grid(TIES_SCAN_BLOCKS);
-  hipLaunchKernelGGL((vlm_select_hist_kernel<sce_sel, 0>), hist_grid, block, 0, s, ws);
-  hipLaunchKernelGGL((vlm_select_scan_kernel<sce_sel, 0>), scan_grid, block, 0, s, ws);
-  hipLaunchKernelGGL((vlm_select_hist_kernel<sce_sel, 1>), hist_grid, block, 0, s, ws);
-  hipLaunchKernelGGL((vlm_select_scan_kernel<sce_sel, 1>), scan_grid, block, 0, s, ws);
-  hipLaunchKernelGGL((vlm_select_hist_kernel<sce_sel, 2>), hist_grid, block, 0, s, ws);
-  hipLaunchKernelGGL((vlm_select_scan_kernel<sce_sel, 2>), scan_grid, block, 0, s, ws);
+  const dim3 block(SCE_THREADS);
+  select_launches<sce_sel>(ws, s, chunk_grid(SCE_HIST_BLOCKS_PER_CU));
   hipLaunchKernelGGL(vlm_sce_reduce_kernel, chunk_grid(SCE_REDUCE_BLOCKS_PER_CU), block, 0, s, ws);
   hipLaunchKernelGGL(vlm_sce_fold_kernel, chunk_grid(1), dim3(SCE_FOLD_THREADS), 0, s, ws);
   hipLaunchKernelGGL(vlm_sce_apply_kernel, chunk_grid(SCE_APPLY_BLOCKS_PER_CU), block, 0, s, ws);

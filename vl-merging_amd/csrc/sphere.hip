@@ -7,8 +7,9 @@
 //
 // The first method of the family whose coefficients are one scalar PER SOURCE and per group (a tensor or a row), made by a small
 // iterative solve on the device from the group's S x S Gram matrix:
-//   tensor groups   Model Stock's three launches (stock.hip): vlm_sphere_reduce_kernel is its reducer (gram_reduce.h, the same
-//                   sums byte for byte; a job without a base streams without one), vlm_sphere_fold_kernel adds a job's records in
+//   tensor groups   Model Stock's three launches (stock.hip): vlm_sphere_reduce_kernel is its reducer (gram_reduce.h's rule in
+//                   chunk_records.h's run, the same sums byte for byte; a job without a base streams without one),
+//                   vlm_sphere_fold_kernel adds a job's records in
 //                   chunk order and has one lane do step 3, vlm_sphere_apply_kernel is the chunk table again with S coefficients
 //                   loaded on entering a job where Model Stock loads one scale.
 //   row groups      ONE launch, vlm_sphere_rows_kernel, over tiles of whole rows (della_tiles.h).  Per tile: every load of the base
@@ -199,26 +200,17 @@ __device__ __forceinline__ void sphere_solve(const stock_acc_t<S>& g, const doub
 
 // ------------------------------------------------------------------------------------------------------------ tensor groups
 __global__ __launch_bounds__(STOCK_THREADS) void vlm_sphere_reduce_kernel(unsigned char* __restrict__ ws) {
-  // vlm_stock_reduce_kernel over this plan's tables: two buffers, used in turn, ONE barrier per chunk
-  __shared__ double red[2][STOCK_WAVES * STOCK_SUMS];
+  // vlm_stock_reduce_kernel over this plan's tables; a job without a base streams without one
   const sphere_view_t w = sphere_view(ws);
-  uint64_t c0, c1;
-  if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
-  uint64_t first = 0;
-  int turn = 0;
-  chunk_run(
-      w.chunks, w.jobs, c0, c1, [&](uint32_t cur) { first = w.first[cur]; },
-      [&](const vlm_sphere_job_t& j, uint64_t start4) {
-        double* r = red[turn];
+  chunk_reduce_run<STOCK_SUMS>(
+      w.chunks, w.jobs, w.hdr->n_chunks, w.first, w.records, [](uint32_t) {},
+      [](const vlm_sphere_job_t& j, uint64_t start4, double* r) {
         with_nsrc(j.n_src, [&](auto S) {
           if (j.base) stock_chunk<S(), true>(j, start4, r);
           else stock_chunk<S(), false>(j, start4, r);
         });
-        __syncthreads();
-        stock_record(r, j.n_src, w.records, first, start4);
-        turn ^= 1;
       },
-      [&](uint32_t) {});
+      [](const vlm_sphere_job_t& j, int k) { return stock_slot_used(k, j.n_src); });
 }
 
 __global__ __launch_bounds__(STOCK_FOLD_THREADS) void vlm_sphere_fold_kernel(unsigned char* __restrict__ ws) {
@@ -237,7 +229,7 @@ __global__ __launch_bounds__(STOCK_FOLD_THREADS) void vlm_sphere_fold_kernel(uns
       const double* rec = w.records + k;
       const uint64_t c0 = w.first[job], c1 = w.first[job + 1];
       double sum = 0.0;
-      STOCK_FOLD_RECORDS(sum, rec, c0, c1);
+      CHUNK_FOLD_RECORDS(sum, rec, STOCK_SUMS, c0, c1);
       sums[k] = sum;
     }
     __syncthreads();
@@ -416,12 +408,12 @@ __device__ __forceinline__ void sphere_tile(const vlm_sphere_job_t& j, const dou
       }
 #pragma unroll
       for (int m = 0; m < S; ++m) {
-        const double t = stock_wave_sum(acc.sq[m]);
+        const double t = chunk_wave_sum(acc.sq[m]);
         if ((uint32_t)lane == i) mine.sq[m] = t;
       }
 #pragma unroll
       for (int p = 0; p < stock_acc_t<S>::NP; ++p) {
-        const double t = stock_wave_sum(acc.dot[p]);
+        const double t = chunk_wave_sum(acc.dot[p]);
         if ((uint32_t)lane == i) mine.dot[p] = t;
       }
     }
@@ -525,17 +517,10 @@ __global__ __launch_bounds__(SPHERE_THREADS, 2) void vlm_sphere_rows_kernel(unsi
 // --------------------------------------------------------------------------------------------------------------------- host
 // fills every offset of `h`; returns the total size
 static size_t sphere_layout(vlm_sphere_header_t* h, uint64_t n_jobs, uint64_t n_chunks, uint64_t n_tiles) {
-  chunk_layout_t at;
-  at.take(sizeof(vlm_sphere_header_t));
-  h->n_jobs = n_jobs;
-  h->n_chunks = n_chunks;
+  chunk_layout_t at = chunk_layout_head<vlm_sphere_header_t, vlm_sphere_job_t>(h, n_jobs, n_chunks);
   h->n_tiles = n_tiles;
-  h->jobs_off = at.take(n_jobs * sizeof(vlm_sphere_job_t));
-  h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
   h->tiles_off = at.take(n_tiles * sizeof(della_tile_t));
-  h->first_off = at.take((n_jobs + 1) * sizeof(uint64_t));
-  h->records_off = at.take(n_chunks * STOCK_SUMS * sizeof(double));
-  h->results_off = at.take(n_jobs * sizeof(vlm_sphere_result_t));
+  records_parts(at, h, STOCK_SUMS * sizeof(double), sizeof(vlm_sphere_result_t));  // the record plan's, behind the tiles
   return at.off;
 }
 

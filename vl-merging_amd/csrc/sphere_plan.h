@@ -43,15 +43,11 @@ static inline int sphere_job_check(const vlm_sphere_job_t& j) {
 // first[i] = the first chunk of job i (a row job has none: first[i] == first[i + 1]), first[n_jobs] = *n_chunks; *n_tiles = the
 // row jobs' tiles.  The jobs have passed sphere_job_check.
 static inline void sphere_count(const vlm_sphere_job_t* jobs, int n_jobs, uint64_t* first, uint64_t* n_chunks, uint64_t* n_tiles) {
-  uint64_t c = 0, t = 0;
-  for (int i = 0; i < n_jobs; ++i) {
-    first[i] = c;
-    if (jobs[i].row_len == 0) c += chunks_of(jobs[i].n_elem);
-    else t += della_tiles_of(jobs[i].n_elem, jobs[i].row_len);
-  }
-  first[n_jobs] = c;
-  *n_chunks = c;
-  *n_tiles = t;
+  *n_chunks = chunk_first_fill(jobs, n_jobs, first,
+                               [](const vlm_sphere_job_t& j) { return j.row_len == 0 ? chunks_of(j.n_elem) : (uint64_t)0; });
+  *n_tiles = 0;
+  for (int i = 0; i < n_jobs; ++i)
+    if (jobs[i].row_len != 0) *n_tiles += della_tiles_of(jobs[i].n_elem, jobs[i].row_len);
 }
 
 // chunk_table_fill's records for the tensor jobs into `ck`, della_tile_fill's for the row jobs into `tl`, each in job order

@@ -16,9 +16,9 @@
 //                            result, steps 1 and 4 per element, 16-B non-temporal loads and stores.
 // Three launches, ordered by the stream alone.  No atomics; every record and every result is overwritten by each run, so nothing
 // is cleared.  -ffp-contract=off and the __f*_rn / __d*_rn forms: one rounding per operation, no FMA.
-// This file holds step 3, the apply rule and the workspace layout; the reducer's rule, its wave and workgroup folds and the fold
-// of a job's records are gram_reduce.h's (sphere.hip reduces with them too); the walker, the run loop and the host checks are
-// chunk_walk.h's and chunk_plan.h's, as in dare.hip and pairstats.hip.
+// This file holds step 3 and the apply rule; the reducer's rule is gram_reduce.h's (sphere.hip reduces with
+// it too), its wave and workgroup folds, its run and the fold of a job's records chunk_records.h's; the walker and the run loop are
+// chunk_walk.h's, the record plan (layout, upload; its view: chunk_records.h) and the host checks chunk_plan.h's, as in pairstats.hip.
 #include "vlm_common.h"
 #include "chunk_walk.h"
 #include "gram_reduce.h"
@@ -33,44 +33,18 @@ static_assert(STOCK_SUMS == 10 && sizeof(vlm_stock_result_t) == (STOCK_SUMS + ST
               "a result is the ten sums, six cosines, cos, t, scale and four reserved bytes");
 static_assert(offsetof(vlm_stock_result_t, dot) == VLM_MERGE_MAX_SRC * 8, "a result begins as a record does");
 
-struct stock_view_t {
-  const vlm_stock_header_t* hdr;
-  const vlm_stock_job_t* jobs;
-  const chunk_t* chunks;
-  const uint64_t* first;
-  double* records;              // [n_chunks][STOCK_SUMS]
-  vlm_stock_result_t* results;  // [n_jobs]
-};
-
+// records: [n_chunks][STOCK_SUMS] doubles
+typedef records_view_t<vlm_stock_header_t, vlm_stock_job_t, double, vlm_stock_result_t> stock_view_t;
 __device__ __forceinline__ stock_view_t stock_view(unsigned char* ws) {
-  stock_view_t v;
-  v.hdr = reinterpret_cast<const vlm_stock_header_t*>(ws);
-  v.jobs = reinterpret_cast<const vlm_stock_job_t*>(ws + v.hdr->jobs_off);
-  v.chunks = reinterpret_cast<const chunk_t*>(ws + v.hdr->chunks_off);
-  v.first = reinterpret_cast<const uint64_t*>(ws + v.hdr->first_off);
-  v.records = reinterpret_cast<double*>(ws + v.hdr->records_off);
-  v.results = reinterpret_cast<vlm_stock_result_t*>(ws + v.hdr->results_off);
-  return v;
+  return records_view<vlm_stock_header_t, vlm_stock_job_t, double, vlm_stock_result_t>(ws);
 }
 
 __global__ __launch_bounds__(STOCK_THREADS) void vlm_stock_reduce_kernel(unsigned char* __restrict__ ws) {
-  // two buffers, used in turn: a chunk's wave sums are read behind ONE barrier while the next chunk's are written to the other
-  __shared__ double red[2][STOCK_WAVES * STOCK_SUMS];
   const stock_view_t w = stock_view(ws);
-  uint64_t c0, c1;
-  if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
-  uint64_t first = 0;
-  int turn = 0;
-  chunk_run(
-      w.chunks, w.jobs, c0, c1, [&](uint32_t cur) { first = w.first[cur]; },
-      [&](const vlm_stock_job_t& j, uint64_t start4) {
-        double* r = red[turn];
-        with_nsrc(j.n_src, [&](auto S) { stock_chunk<S()>(j, start4, r); });
-        __syncthreads();
-        stock_record(r, j.n_src, w.records, first, start4);  // ((w0 + w1) + w2) + w3 per sum, at the chunk's index
-        turn ^= 1;
-      },
-      [&](uint32_t) {});
+  chunk_reduce_run<STOCK_SUMS>(
+      w.chunks, w.jobs, w.hdr->n_chunks, w.first, w.records, [](uint32_t) {},
+      [](const vlm_stock_job_t& j, uint64_t start4, double* r) { with_nsrc(j.n_src, [&](auto S) { stock_chunk<S()>(j, start4, r); }); },
+      [](const vlm_stock_job_t& j, int k) { return stock_slot_used(k, j.n_src); });
 }
 
 // Step 3 for a job of S sources whose folded sums are s[0 .. STOCK_SUMS) (LDS): the whole result, written field by field (the
@@ -117,7 +91,7 @@ __global__ __launch_bounds__(STOCK_FOLD_THREADS) void vlm_stock_fold_kernel(unsi
       const double* rec = w.records + k;
       const uint64_t c0 = w.first[job], c1 = w.first[job + 1];
       double sum = 0.0;
-      STOCK_FOLD_RECORDS(sum, rec, c0, c1);  // a missing record adds +0.0: it changes no sum
+      CHUNK_FOLD_RECORDS(sum, rec, STOCK_SUMS, c0, c1);
       sums[k] = sum;
     }
     __syncthreads();
@@ -155,48 +129,15 @@ __global__ __launch_bounds__(STOCK_THREADS) void vlm_stock_apply_kernel(unsigned
       [&](uint32_t) {});
 }
 
-// fills every offset of `h` for n_jobs jobs and n_chunks chunks; returns the total size
-static size_t stock_layout(vlm_stock_header_t* h, uint64_t n_jobs, uint64_t n_chunks) {
-  chunk_layout_t at;
-  at.take(sizeof(vlm_stock_header_t));
-  h->n_jobs = n_jobs;
-  h->n_chunks = n_chunks;
-  h->jobs_off = at.take(n_jobs * sizeof(vlm_stock_job_t));
-  h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
-  h->first_off = at.take((n_jobs + 1) * sizeof(uint64_t));
-  h->records_off = at.take(n_chunks * STOCK_SUMS * sizeof(double));
-  h->results_off = at.take(n_jobs * sizeof(vlm_stock_result_t));
-  return at.off;
-}
-
 extern "C" size_t vlm_stock_plan_bytes(int n_jobs, uint64_t total_elems) {
-  if (n_jobs < 0) return 0;
-  vlm_stock_header_t h;
-  return stock_layout(&h, (uint64_t)n_jobs, chunks_bound(n_jobs, total_elems));
+  return records_plan_bytes<vlm_stock_header_t, vlm_stock_job_t>(n_jobs, total_elems, STOCK_SUMS * sizeof(double), sizeof(vlm_stock_result_t));
 }
 
 extern "C" int vlm_stock_plan_upload(const vlm_stock_job_t* jobs, int n_jobs, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-  if (!jobs || n_jobs <= 0 || !chunk_ptr_ok(workspace)) return VLM_ERR_ARG;
-  std::vector<uint64_t> first((size_t)n_jobs + 1);
-  uint64_t n_chunks = 0;
-  for (int i = 0; i < n_jobs; ++i) {
-    const vlm_stock_job_t& j = jobs[i];
-    if (j.n_elem == 0) return VLM_ERR_ARG;
-    const int rc = chunk_job_check(j, CHUNK_OVERLAP_NONE, true);  // two passes read the inputs: dst may meet none of them
-    if (rc != VLM_OK) return rc;
-    first[i] = n_chunks;
-    n_chunks += chunks_of(j.n_elem);
-  }
-  first[n_jobs] = n_chunks;
-  if (!chunk_count_ok(n_chunks)) return VLM_ERR_UNSUPPORTED;
-  vlm_stock_header_t hdr;
-  const size_t total = stock_layout(&hdr, (uint64_t)n_jobs, n_chunks);
-  if (total > workspace_bytes) return VLM_ERR_WORKSPACE;
-  // the host image ends where the records begin: they and the results are device-made (every run overwrites all of them)
-  std::vector<unsigned char> img = chunk_image(hdr, jobs, n_jobs, hdr.records_off);
-  memcpy(img.data() + hdr.first_off, first.data(), first.size() * sizeof(uint64_t));
-  return chunk_upload(workspace, img, 0, (hipStream_t)stream);
+  return records_plan_upload<vlm_stock_header_t>(
+      jobs, n_jobs, workspace, workspace_bytes, stream, STOCK_SUMS * sizeof(double), sizeof(vlm_stock_result_t),
+      [](const vlm_stock_job_t& j) { return chunk_job_check(j, CHUNK_OVERLAP_NONE, true); });  // two passes read the inputs: dst may meet none of them
 }
 
 extern "C" int vlm_stock_run(void* workspace, void* stream) {

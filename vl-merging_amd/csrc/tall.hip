@@ -18,7 +18,8 @@
 // neighbours' and the tensor's last word -- float4 lanes, tail bits, zero padding -- is written once, by one lane.  Where n4 lies
 // just behind the tail chunk's last float4 the chunk walks a fifth slot for it (tall_has_tail_slot).
 // Integer counters only, so nothing depends on the order workgroups run in.  -ffp-contract=off and __f*_rn: one rounding per
-// operation, no FMA.  The run loop and the host checks are chunk_walk.h's and chunk_plan.h's, as in dare.hip.
+// operation, no FMA.  The run loop and the workspace's view are chunk_walk.h's, the counter plan (layout, upload, the two-launch
+// run) and the family's host checks chunk_plan.h's, as in dare.hip.
 #include "vlm_common.h"
 #include "chunk_walk.h"  // the run loop, the source-count dispatch and the counters: the whole family's
 #include "tall_mask.h"   // where an element's bit lives; the checks on a job's masks
@@ -34,21 +35,7 @@ static_assert(VLM_TALL_COUNTERS == VLM_TIES_COUNTERS, "tall.hip counts into chun
 #define TALL_MASKS 1     // CONSENSUS, one mask per source written
 #define TALL_RESTORE 2   // RESTORE: one mask read
 
-struct tall_view_t {
-  const vlm_tall_header_t* hdr;
-  const vlm_tall_job_t* jobs;
-  const chunk_t* chunks;
-  u64_t* counters;
-};
-
-__device__ __forceinline__ tall_view_t tall_view(unsigned char* ws) {
-  tall_view_t v;
-  v.hdr = reinterpret_cast<const vlm_tall_header_t*>(ws);
-  v.jobs = reinterpret_cast<const vlm_tall_job_t*>(ws + v.hdr->jobs_off);
-  v.chunks = reinterpret_cast<const chunk_t*>(ws + v.hdr->chunks_off);
-  v.counters = reinterpret_cast<u64_t*>(ws + v.hdr->counters_off);
-  return v;
-}
+typedef counts_view_t<vlm_tall_header_t, vlm_tall_job_t> tall_view_t;
 
 // a job's scalars, workgroup-uniform
 struct tall_param_t {
@@ -191,13 +178,13 @@ __device__ __forceinline__ void tall_chunk(const vlm_tall_job_t& j, uint64_t sta
 }
 
 __global__ __launch_bounds__(TALL_THREADS) void vlm_tall_clear_kernel(unsigned char* __restrict__ ws) {
-  const tall_view_t w = tall_view(ws);
+  const tall_view_t w = counts_view<vlm_tall_header_t, vlm_tall_job_t>(ws);
   chunk_clear_counts(w.counters, w.hdr->n_jobs * VLM_TALL_COUNTERS);
 }
 
 __global__ __launch_bounds__(TALL_THREADS) void vlm_tall_apply_kernel(unsigned char* __restrict__ ws) {
   __shared__ u64_t red[(TALL_THREADS / 64) * VLM_TALL_COUNTERS];
-  const tall_view_t w = tall_view(ws);
+  const tall_view_t w = counts_view<vlm_tall_header_t, vlm_tall_job_t>(ws);
   uint64_t c0, c1;
   if (!chunk_my_run(w.hdr->n_chunks, &c0, &c1)) return;
   ties_counts_t n;
@@ -225,51 +212,18 @@ __global__ __launch_bounds__(TALL_THREADS) void vlm_tall_apply_kernel(unsigned c
       [&](uint32_t cur) { chunk_flush_counts(n.c, red, w.counters + (uint64_t)cur * VLM_TALL_COUNTERS); });
 }
 
-// fills every offset of `h` for n_jobs jobs and n_chunks chunks; returns the total size
-static size_t tall_layout(vlm_tall_header_t* h, uint64_t n_jobs, uint64_t n_chunks) {
-  chunk_layout_t at;
-  at.take(sizeof(vlm_tall_header_t));
-  h->n_jobs = n_jobs;
-  h->n_chunks = n_chunks;
-  h->jobs_off = at.take(n_jobs * sizeof(vlm_tall_job_t));
-  h->chunks_off = at.take(n_chunks * sizeof(chunk_t));
-  h->counters_off = at.take(n_jobs * VLM_TALL_COUNTERS * sizeof(uint64_t));
-  return at.off;
-}
-
 extern "C" size_t vlm_tall_plan_bytes(int n_jobs, uint64_t total_elems) {
-  if (n_jobs < 0) return 0;
-  vlm_tall_header_t h;
-  return tall_layout(&h, (uint64_t)n_jobs, chunks_bound(n_jobs, total_elems));
+  return counts_plan_bytes<vlm_tall_header_t, vlm_tall_job_t>(n_jobs, total_elems, VLM_TALL_COUNTERS);
 }
 
 extern "C" int vlm_tall_plan_upload(const vlm_tall_job_t* jobs, int n_jobs, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-  if (!jobs || n_jobs <= 0 || !chunk_ptr_ok(workspace)) return VLM_ERR_ARG;
-  uint64_t n_chunks = 0;
-  for (int i = 0; i < n_jobs; ++i) {
-    const vlm_tall_job_t& j = jobs[i];
-    if (j.n_elem == 0) return VLM_ERR_ARG;
-    int rc = chunk_job_check(j, CHUNK_OVERLAP_EXACT, true);
-    if (rc == VLM_OK) rc = tall_job_check(j);
-    if (rc != VLM_OK) return rc;
-    n_chunks += chunks_of(j.n_elem);
-  }
-  if (!chunk_count_ok(n_chunks)) return VLM_ERR_UNSUPPORTED;
-  vlm_tall_header_t hdr;
-  const size_t total = tall_layout(&hdr, (uint64_t)n_jobs, n_chunks);
-  if (total > workspace_bytes) return VLM_ERR_WORKSPACE;
-  // the host image ends where the counters begin: they are device-made (every run zeroes them first)
-  return chunk_upload(workspace, chunk_image(hdr, jobs, n_jobs, hdr.counters_off), 0, (hipStream_t)stream);
+  return counts_plan_upload<vlm_tall_header_t, VLM_TALL_COUNTERS>(jobs, n_jobs, workspace, workspace_bytes, stream, [](const vlm_tall_job_t& j) {
+    const int rc = chunk_job_check(j, CHUNK_OVERLAP_EXACT, true);
+    return rc == VLM_OK ? tall_job_check(j) : rc;
+  });
 }
 
 extern "C" int vlm_tall_run(void* workspace, void* stream) {
-  if (!workspace) return VLM_ERR_ARG;
-  unsigned char* ws = (unsigned char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  // two launches, stream-ordered, no host synchronisation: the sizes of the plan live in the workspace header
-  hipLaunchKernelGGL(vlm_tall_clear_kernel, dim3(64), dim3(TALL_THREADS), 0, s, ws);
-  hipLaunchKernelGGL(vlm_tall_apply_kernel, chunk_grid(TALL_APPLY_BLOCKS_PER_CU), dim3(TALL_THREADS), 0, s, ws);
-  VLM_CHECK_LAUNCH();
-  return VLM_OK;
+  return counts_run(workspace, stream, vlm_tall_clear_kernel, vlm_tall_apply_kernel, chunk_grid(TALL_APPLY_BLOCKS_PER_CU));
 }

@@ -315,8 +315,8 @@ static int select_plan_upload(const typename Sel::job_t* jobs, int n_jobs, void*
   std::vector<unsigned char> img = chunk_image(hdr, jobs, n_jobs, hdr.state_off);
   uint32_t* unit0 = reinterpret_cast<uint32_t*>(img.data() + hdr.unit0_off);
   ties_unit_t* units = reinterpret_cast<ties_unit_t*>(img.data() + hdr.units_off);
+  if constexpr (Sel::RECORD_DOUBLES > 0) chunk_first_fill(jobs, n_jobs, reinterpret_cast<uint64_t*>(img.data() + hdr.first_off));
   uint64_t u = 0;
-  [[maybe_unused]] uint64_t c = 0;  // chunks before job i
   for (int i = 0; i < n_jobs; ++i) {
     unit0[i] = (uint32_t)u;
     for (int m = 0; m < select_units<Sel>(jobs[i]); ++m) {
@@ -324,32 +324,32 @@ static int select_plan_upload(const typename Sel::job_t* jobs, int n_jobs, void*
       units[u].m = (uint32_t)m;
       ++u;
     }
-    if constexpr (Sel::RECORD_DOUBLES > 0) {
-      uint64_t* first = reinterpret_cast<uint64_t*>(img.data() + hdr.first_off);
-      first[i] = c;
-      c += chunks_of(jobs[i].n_elem);
-      first[i + 1] = c;
-    }
   }
   // the histograms start at zero; every scan launch leaves them at zero again
   return chunk_upload(workspace, img, total - hdr.state_off, (hipStream_t)stream);
 }
 
-// seven launches, stream-ordered, no host synchronisation: the sizes of the plan live in the workspace header
+// The select itself: three histogram passes, a bin pick after each.  Six launches, stream-ordered.
 template <class Sel>
-static int select_run(void* workspace, void* stream, void (*apply_kernel)(unsigned char*)) {
-  if (!workspace) return VLM_ERR_ARG;
-  unsigned char* ws = (unsigned char*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 block(TIES_THREADS), hist_grid = chunk_grid(TIES_HIST_BLOCKS_PER_CU), scan_grid(TIES_SCAN_BLOCKS),
-             apply_grid = chunk_grid(TIES_APPLY_BLOCKS_PER_CU);
+static void select_launches(unsigned char* ws, hipStream_t s, dim3 hist_grid) {
+  const dim3 block(TIES_THREADS), scan_grid(TIES_SCAN_BLOCKS);
   hipLaunchKernelGGL((vlm_select_hist_kernel<Sel, 0>), hist_grid, block, 0, s, ws);
   hipLaunchKernelGGL((vlm_select_scan_kernel<Sel, 0>), scan_grid, block, 0, s, ws);
   hipLaunchKernelGGL((vlm_select_hist_kernel<Sel, 1>), hist_grid, block, 0, s, ws);
   hipLaunchKernelGGL((vlm_select_scan_kernel<Sel, 1>), scan_grid, block, 0, s, ws);
   hipLaunchKernelGGL((vlm_select_hist_kernel<Sel, 2>), hist_grid, block, 0, s, ws);
   hipLaunchKernelGGL((vlm_select_scan_kernel<Sel, 2>), scan_grid, block, 0, s, ws);
-  hipLaunchKernelGGL(apply_kernel, apply_grid, block, 0, s, ws);
+}
+
+// the select, then the method's apply pass: seven launches, no host synchronisation -- the sizes of the plan live in the workspace
+// header
+template <class Sel>
+static int select_run(void* workspace, void* stream, void (*apply_kernel)(unsigned char*)) {
+  if (!workspace) return VLM_ERR_ARG;
+  unsigned char* ws = (unsigned char*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  select_launches<Sel>(ws, s, chunk_grid(TIES_HIST_BLOCKS_PER_CU));
+  hipLaunchKernelGGL(apply_kernel, chunk_grid(TIES_APPLY_BLOCKS_PER_CU), dim3(TIES_THREADS), 0, s, ws);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }

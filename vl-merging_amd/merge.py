@@ -196,14 +196,24 @@ class _Plan:
         with torch.cuda.device(self.device):
             L.check(getattr(L.get_lib(), self.RUN)(L.ptr(self.ws), L.stream_ptr()), self.RUN)
 
+    def _header(self):
+        """The workspace header after a run (this synchronises)."""
+        if self.ws is None:
+            raise L.VlmError("%s.report() needs a plan that has run" % type(self).__name__)
+        return self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
+
+    def _structs(self, TYPE, offset, count):
+        """`count` structs of the ctypes TYPE at `offset` of the workspace, as the device left them (this synchronises)."""
+        size = ctypes.sizeof(TYPE)
+        raw = self.ws[offset: offset + size * count].cpu().numpy().tobytes()
+        return [TYPE.from_buffer_copy(raw[i * size: (i + 1) * size]) for i in range(count)]
+
     def _read(self):
         """The workspace header after a run (this synchronises) and, per job, the start of its report row and the counters TIES,
         DARE, DELLA and the band merge share: per group of GROUPS one count per source (how many entries each source kept; band
         merge: how many it lost as outliers), then the elements whose kept entries disagree in sign and the elements nothing
         contributes to."""
-        if self.ws is None:
-            raise L.VlmError("%s.report() needs a plan that has run" % type(self).__name__)
-        hdr = self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
+        hdr = self._header()
         width = len(self.GROUPS) * L.MERGE_MAX_SRC + 2
         counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * width * hdr.n_jobs].cpu().numpy().view("<u8").reshape(-1, width)
         rows = []
@@ -360,24 +370,26 @@ class TiesPlan(_Plan):
         return out
 
 
-def _task_vector_merge(plan_type, add, state_dict, config, central_weight, lam, device, plan_out, report_out):
-    """The driver ties_merge, dare_merge, band_merge and della_merge share: sum_task_vectors' dictionary logic,
-    `add(plan, dst, tensors, central, lam)` into a `plan_type(device)` for a tensor with several sources (`lam=None` takes
-    config["sum_lambda"]), the task-vector job with ratio 1 for a layer with ONE source.  `plan_out` receives the plan first, then
-    the MergePlan of the single-source layers (each only if it has jobs); `report_out` receives the plan's report()."""
+def _task_vector_merge(plan_type, add, state_dict, config, central_weight, lam, device, plan_out, report_out, delta=True):
+    """The driver every method after sum_task_vectors shares: sum_task_vectors' dictionary logic,
+    `add(plan, dst, tensors, central, lam, mods)` into a `plan_type(device)` for a tensor with several sources (`lam=None` takes
+    config["sum_lambda"]; `mods`: the sources' modality names), the task-vector job with ratio 1 for a layer with ONE source.
+    `delta=False` (sphere_merge on the weights) is merge_weights' logic instead: no central checkpoint is read, `add` gets None
+    for it, and a layer with ONE source is the LERP job with ratio 1.  `plan_out` receives the plan first, then the MergePlan of
+    the single-source layers (each only if it has jobs); `report_out` receives the plan's report()."""
     if lam is None:
         lam = config["sum_lambda"]
     plan = plan_type(device)
     single = MergePlan(plan.device)
     out = _passthrough(state_dict)
-    central = _central(central_weight, config)
+    central = _central(central_weight, config) if delta else None
     for dst, mods, srcs, through in _walk(state_dict, config, central):
         if srcs is None:
             out[dst] = through
         elif len(mods) == 1:
-            out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
+            out[dst] = single.add(L.MERGE_TASKVEC if delta else L.MERGE_LERP, _tensors(srcs), [1], base=central[dst] if delta else None)
         else:
-            out[dst] = add(plan, dst, _tensors(srcs), central[dst], lam)
+            out[dst] = add(plan, dst, _tensors(srcs), central[dst] if delta else None, lam, [m for m, _ in srcs])
     for p in (plan, single):
         _finish(p, plan_out)
     if report_out is not None:
@@ -394,7 +406,7 @@ def ties_merge(state_dict, config, central_weight=None, density=0.2, lam=None, d
     there are any (the order is part of the contract: callers index [0] for the TiesPlan);
     `report_out` receives TiesPlan.report() (reading it back synchronises)."""
     ties_keep_count(density, 1)  # ValueError before any device work
-    return _task_vector_merge(TiesPlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density=density, lam=lam, name=dst),
+    return _task_vector_merge(TiesPlan, lambda plan, dst, srcs, c, lam, mods: plan.add(srcs, c, density=density, lam=lam, name=dst),
                               state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
@@ -486,7 +498,7 @@ def dare_merge(state_dict, config, central_weight=None, drop=0.9, lam=None, seed
     dare_keep_below(drop)  # ValueError before any device work
     mode = _mode(DarePlan.KIND, mode)
     return _task_vector_merge(
-        DarePlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
+        DarePlan, lambda plan, dst, srcs, c, lam, mods: plan.add(srcs, c, drop, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
         state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
@@ -554,7 +566,7 @@ def band_merge(state_dict, config, central_weight=None, density=0.9, gamma=0.01,
     band_ranks(1, density, gamma)  # ValueError before any device work
     mode = _mode(BandPlan.KIND, mode)
     return _task_vector_merge(
-        BandPlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density=density, gamma=gamma, lam=lam, mode=mode, name=dst),
+        BandPlan, lambda plan, dst, srcs, c, lam, mods: plan.add(srcs, c, density=density, gamma=gamma, lam=lam, mode=mode, name=dst),
         state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
@@ -633,7 +645,7 @@ def della_merge(state_dict, config, central_weight=None, density=0.2, epsilon=0.
     mode = _mode(DellaPlan.KIND, mode)
     return _task_vector_merge(
         DellaPlan,
-        lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density, epsilon, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
+        lambda plan, dst, srcs, c, lam, mods: plan.add(srcs, c, density, epsilon, lam, seed, dare_stream(dst), mode, rescale=rescale, name=dst),
         state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
@@ -652,12 +664,7 @@ class StockPlan(_Plan):
 
     def results(self):
         """The raw vlm_stock_result_t of every job as the device left it (this synchronises)."""
-        if self.ws is None:
-            raise L.VlmError("StockPlan.report() needs a plan that has run")
-        hdr = self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
-        size = ctypes.sizeof(L.StockResult)
-        raw = self.ws[hdr.results_off: hdr.results_off + size * hdr.n_jobs].cpu().numpy().tobytes()
-        return [L.StockResult.from_buffer_copy(raw[i * size: (i + 1) * size]) for i in range(len(self.jobs))]
+        return self._structs(L.StockResult, self._header().results_off, len(self.jobs))
 
     def report(self):
         """Per job, read back after a run (this synchronises): `sq` per source; per pair (a, b), a < b, in the order of their
@@ -683,7 +690,7 @@ def stock_merge(state_dict, config, central_weight=None, device="cuda", plan_out
     sum_task_vectors issues for it (t = 1).  `plan_out` receives the StockPlan FIRST whenever a layer has several sources, then
     the MergePlan of the single-source layers if there are any; `report_out` receives StockPlan.report() (reading it back
     synchronises)."""
-    return _task_vector_merge(StockPlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, name=dst),
+    return _task_vector_merge(StockPlan, lambda plan, dst, srcs, c, lam, mods: plan.add(srcs, c, name=dst),
                               state_dict, config, central_weight, 1.0, device, plan_out, report_out)
 
 
@@ -705,13 +712,9 @@ class ScePlan(_Plan):
 
     def results(self):
         """(the raw vlm_sce_result_t, the three counters) of every job as the device left them (this synchronises)."""
-        if self.ws is None:
-            raise L.VlmError("ScePlan.report() needs a plan that has run")
-        hdr = self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
-        size, n = ctypes.sizeof(L.SceResult), len(self.jobs)
-        raw = self.ws[hdr.state_off: hdr.state_off + size * n].cpu().numpy().tobytes()
+        hdr, n = self._header(), len(self.jobs)
         counters = self.ws[hdr.counters_off: hdr.counters_off + 8 * L.SCE_COUNTERS * n].cpu().numpy().view("<u8").reshape(n, L.SCE_COUNTERS)
-        return [(L.SceResult.from_buffer_copy(raw[i * size: (i + 1) * size]), [int(v) for v in counters[i]]) for i in range(n)]
+        return [(r, [int(v) for v in counters[i]]) for i, r in enumerate(self._structs(L.SceResult, hdr.state_off, n))]
 
     def report(self):
         """Per job, read back after a run (this synchronises): K, the variance threshold as a float and as its key, how many
@@ -739,7 +742,7 @@ def sce_merge(state_dict, config, central_weight=None, density=0.1, lam=None, de
     the MergePlan of the single-source layers if there are any; `report_out` receives ScePlan.report() (reading it back
     synchronises)."""
     ties_keep_count(density, 1)  # ValueError before any device work
-    return _task_vector_merge(ScePlan, lambda plan, dst, srcs, c, lam: plan.add(srcs, c, density=density, lam=lam, name=dst),
+    return _task_vector_merge(ScePlan, lambda plan, dst, srcs, c, lam, mods: plan.add(srcs, c, density=density, lam=lam, name=dst),
                               state_dict, config, central_weight, lam, device, plan_out, report_out)
 
 
@@ -833,8 +836,8 @@ class TallPlan(_Plan):
         return out
 
 
-# dst -> (layer, source template) of every merged tensor name
-_SRC_OF = {dst: (i, src) for i in range(NUM_MERGE_LAYERS) for src, dst in _tensor_names(i)}
+# dst -> source template of every merged tensor name
+_SRC_OF = {dst: src for i in range(NUM_MERGE_LAYERS) for src, dst in _tensor_names(i)}
 
 
 def consensus_merge(state_dict, config, central_weight=None, tall_lambda=0.4, k=2, lam=None, masks_out: Optional[dict] = None,
@@ -855,12 +858,11 @@ def consensus_merge(state_dict, config, central_weight=None, tall_lambda=0.4, k=
     tall_lambda = tall_threshold(tall_lambda)  # ValueError before any device work
     consensus_k(k)
 
-    def add(plan, dst, srcs, c, lam):
+    def add(plan, dst, srcs, c, lam, mods):
         out = plan.add(srcs, c, tall_lambda, min(k, len(srcs)), lam=lam, masks=masks_out is not None, name=dst)
         if masks_out is not None:
-            i, src = _SRC_OF[dst]
-            for m, t in zip(modalities_for_layer(config, i), plan.masks[-1]):
-                masks_out[src(m)] = t
+            for m, t in zip(mods, plan.masks[-1]):
+                masks_out[_SRC_OF[dst](m)] = t
         return out
     return _task_vector_merge(TallPlan, add, state_dict, config, central_weight, lam, device, plan_out, report_out)
 
@@ -948,12 +950,7 @@ class SpherePlan(_Plan):
 
     def results(self):
         """The raw vlm_sphere_result_t of every job as the device left it (this synchronises)."""
-        if self.ws is None:
-            raise L.VlmError("SpherePlan.report() needs a plan that has run")
-        hdr = self.HEADER.from_buffer_copy(self.ws[: ctypes.sizeof(self.HEADER)].cpu().numpy().tobytes())
-        size = ctypes.sizeof(L.SphereResult)
-        raw = self.ws[hdr.results_off: hdr.results_off + size * hdr.n_jobs].cpu().numpy().tobytes()
-        return [L.SphereResult.from_buffer_copy(raw[i * size: (i + 1) * size]) for i in range(len(self.jobs))]
+        return self._structs(L.SphereResult, self._header().results_off, len(self.jobs))
 
     def report(self):
         """Per job, read back after a run (this synchronises): `n`, `row_len` (0: one group, the tensor), `weights`, `lam`; a
@@ -995,29 +992,12 @@ def sphere_merge(state_dict, config, central_weight=None, on="weights", rows=Fal
     delta = on == "delta"
     if not delta and lam is not None:
         raise ValueError("sphere_merge on the weights has no lambda (got %r)" % (lam,))
-    if delta and lam is None:
-        lam = config["sum_lambda"]
-    plan = SpherePlan(device)
-    single = MergePlan(plan.device)
-    out = _passthrough(state_dict)
-    central = _central(central_weight, config) if delta else None
-    for dst, mods, srcs, through in _walk(state_dict, config, central):
-        if srcs is None:
-            out[dst] = through
-        elif len(mods) == 1:
-            if delta:
-                out[dst] = single.add(L.MERGE_TASKVEC, _tensors(srcs), [1], base=central[dst])
-            else:
-                out[dst] = single.add(L.MERGE_LERP, _tensors(srcs), [1])
-        else:
-            ratios = interpolation_ratios(mods, config["merge_ratio"])
-            out[dst] = plan.add(_tensors(srcs), central[dst] if delta else None, [ratios[m] for m, _ in srcs],
-                                lam=lam if delta else 1.0, rows=rows, name=dst)
-    for p in (plan, single):
-        _finish(p, plan_out)
-    if report_out is not None:
-        report_out.extend(plan.report() if plan.jobs else [])
-    return out
+
+    def add(plan, dst, srcs, c, lam, mods):
+        ratios = interpolation_ratios(mods, config["merge_ratio"])
+        return plan.add(srcs, c, [ratios[m] for m in mods], lam=lam, rows=rows, name=dst)
+    return _task_vector_merge(SpherePlan, add, state_dict, config, central_weight, lam if delta else 1.0, device, plan_out,
+                              report_out, delta=delta)
 
 
 # ------------------------------------------------------------------------------------------------- expert-pair statistics
@@ -1045,7 +1025,7 @@ class PairStatsPlan(_Plan):
     A job reads its sources (and its base) and writes no tensor: add() allocates nothing."""
 
     KIND, GPU_ONLY, JOB = "pair-statistics", "the pair-statistics kernels run on the GPU only", L.PairStatsJob
-    BYTES, UPLOAD, RUN = "vlm_pairstats_plan_bytes", "vlm_pairstats_plan_upload", "vlm_pairstats_run"
+    BYTES, UPLOAD, RUN, HEADER = "vlm_pairstats_plan_bytes", "vlm_pairstats_plan_upload", "vlm_pairstats_run", L.PairStatsHeader
     HAS_DST = False
 
     @staticmethod
@@ -1074,14 +1054,8 @@ class PairStatsPlan(_Plan):
         """Per job, read back after a run (this synchronises): the raw sums as the device left them -- `sq`, `nnz` per source;
         per pair (a, b), a < b, in the order of their slots, the sums of the rule (include/vlm_hip.h) with both sides' `sq` --
         and the derived measures (pair_derived)."""
-        if self.ws is None:
-            raise L.VlmError("PairStatsPlan.report() needs a plan that has run")
-        hdr = L.PairStatsHeader.from_buffer_copy(self.ws[: ctypes.sizeof(L.PairStatsHeader)].cpu().numpy().tobytes())
-        size = ctypes.sizeof(L.PairStatsResult)
-        raw = self.ws[hdr.results_off: hdr.results_off + size * hdr.n_jobs].cpu().numpy().tobytes()
         rows = []
-        for i, job in enumerate(self.jobs):
-            r = L.PairStatsResult.from_buffer_copy(raw[i * size: (i + 1) * size])
+        for i, (job, r) in enumerate(zip(self.jobs, self._structs(L.PairStatsResult, self._header().results_off, len(self.jobs)))):
             S = job.n_src
             pairs = []
             for b in range(1, S):

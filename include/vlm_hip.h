@@ -776,6 +776,104 @@ int vlm_tall_plan_upload(const vlm_tall_job_t* jobs_host, int n_jobs, void* work
 int vlm_tall_run(void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * EMR-Merging (Huang et al., "EMR-Merging: Tuning-Free High-Performance Model Merging", NeurIPS 2024: elect, mask and rescale),
+ * csrc/emr.hip.  NO REFERENCE SITE: the reference has no such merge; the arithmetic below is the specification and is pinned to a
+ * numpy restatement of it (tests/emr_restatement.py), not to the reference.  One VLM_EMR_MERGE job = one output tensor with central
+ * tensor c (base, required), sources W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), a scale lam (fp32) and either no mask pointers
+ * or one per source.  fp32 operations round once, no FMA; "f64" = the operand widened exactly and the operation done in double,
+ * one rounding:
+ *   1. x_m = W_m - c
+ *   2. s = ((+0.0 + x_0) + x_1) + ... in source order; its sign is taken by comparison (s > 0, s < 0): -0.0 and NaN count as zero
+ *      (step 3 of the TIES rule)
+ *   3. agree_m = (s > 0 and x_m > 0) or (s < 0 and x_m < 0)
+ *      e = max over the agreeing m of |x_m|, from +0.0 (exact: the order does not matter)
+ *      u = s > 0 ? e : (s < 0 ? -e : +0.0)             (the unified task vector; where s != 0 a source agrees, so u != 0 there)
+ *   4. dst = c + lam * u
+ *   5. if the job has masks: bit i of mask m is agree_m at element i, in the packed layout of the consensus merge above, without
+ *      change: ceil(n_elem / 32) little-endian 32-bit words, element i is bit i & 31 of word i >> 5, the bits at positions >=
+ *      n_elem are 0, every word is written exactly once by every run.
+ *   6. per job and source, in f64:  a[m] = sum f64(|x_m|);  b[m] = sum (agree_m ? f64(e) : +0.0).  The order of summation is the
+ *      family's (thread, wave by halves, ((w0 + w1) + w2) + w3, the records of a job in chunk order, every sum from +0.0): a thread
+ *      adds its float4s u = 0 .. 3 in order and in each the components in order.  THE RAGGED TAIL DIFFERS FROM THE PAIR
+ *      STATISTICS': the n_elem & 3 tail elements belong to the ONE thread that stands at the partial float4 n4 = n_elem >> 2 --
+ *      thread n4 & 255 of the chunk that owns the tail (thread 0, in a fifth slot, when n4 is a positive multiple of 1024) -- and
+ *      their addends enter that thread's sums after its float4s, in element order.
+ *   7. rescale[m] = b[m] > 0 ? f32(a[m] / b[m]) : +0.0f: f64 division, then one rounding to fp32, on the device.
+ * Exact integer counts per job: kept[m] = the bits set in mask m (counted with or without masks), zero = the elements with s
+ * neither > 0 nor < 0, conflict = the elements whose x_m hold both a positive and a negative entry.  A chunk's record holds a[4],
+ * b[4] and these six counts AS DOUBLES (14 doubles; integers are exact in a double below 2^53, and a job has fewer than 2^34
+ * elements), so one record writer and one fold serve sums and counts; the result holds the counts as uint64.
+ * A VLM_EMR_RESTORE job rebuilds one expert: n_src = 1, src[0] = uni (a unified tensor), base = c, mask[0] = a packed mask (an
+ * INPUT) and the job scalar rescale, finite and >= 0:  t = uni - c;  y = bit_i ? t : +0.0;  dst = c + rescale * y -- three fp32
+ * roundings.  Its only count is kept[0], the bits set among the first n_elem; lam is not read.  The mask is read up to word
+ * ceil(n_elem / 32) - 1 and no further; bits at positions >= n_elem are ignored.  With uni the lam = 1 output of the rule above
+ * this is the paper's W_pre + lambda_t * M_t * tau_uni UP TO THE ROUNDING OF c + u: uni - c is not u bit for bit, and the restore
+ * rule is defined on what the checkpoint holds, not on u.
+ * Two deliberate departures from the paper's code: (i) rescalers are per tensor (per job), not per model -- layers here have
+ * different expert sets, so a per-model sum over tensors has no meaning; (ii) an element with s == 0 contributes nothing (u = 0,
+ * no bit set), where the paper's code gives it a negative sign.
+ * Both ops are one elementwise pass in which every load of a float4 precedes its store: dst may be EXACTLY base or EXACTLY one of
+ * the job's sources; any other overlap of dst's byte range with an input's is VLM_ERR_ARG, and so is a mask that is not 16-byte
+ * aligned or whose 4 ceil(n_elem / 32) bytes meet dst, the base, a source or another mask of the same job (overlap ACROSS jobs is
+ * the caller's to avoid).  Non-finite inputs are outside the contract.  A run has no atomics and nothing to clear: it leaves the
+ * same bytes, words and results whatever the grid, the job's place in a plan or the number of runs.
+ */
+#define VLM_EMR_MERGE 0
+#define VLM_EMR_RESTORE 1
+
+typedef struct {
+  void* dst;                            /* f32 [n_elem] */
+  const void* base;                     /* f32 [n_elem]: the central tensor c */
+  const void* src[VLM_MERGE_MAX_SRC];   /* f32 [n_elem] each; RESTORE: src[0] = the unified tensor */
+  void* mask[VLM_MERGE_MAX_SRC];        /* u32 [ceil(n_elem / 32)] each, 16-byte aligned.  MERGE: outputs, all NULL or all n_src
+                                           set; RESTORE: mask[0] is the input */
+  uint64_t n_elem;
+  int32_t n_src;
+  int32_t op;                           /* VLM_EMR_MERGE | VLM_EMR_RESTORE */
+  float lam;                            /* MERGE, step 4 */
+  float rescale;                        /* RESTORE: finite, >= 0 (MERGE: not read) */
+} vlm_emr_job_t;
+
+/* The workspace of an EMR plan BEGINS with this header (byte offsets from its start); jobs keep their upload order. */
+typedef struct {
+  uint64_t n_jobs, n_chunks;
+  uint64_t jobs_off;      /* vlm_emr_job_t [n_jobs] */
+  uint64_t chunks_off;    /* the 16-KiB chunk table */
+  uint64_t first_off;     /* uint64 [n_jobs + 1]: the first chunk of each job, then n_chunks */
+  uint64_t records_off;   /* double [n_chunks][14]: one record per chunk, a[4], b[4], kept[4], zero, conflict, overwritten by every run */
+  uint64_t results_off;   /* vlm_emr_result_t [n_jobs]: overwritten by every run */
+} vlm_emr_header_t;
+#define VLM_EMR_SUMS (3 * VLM_MERGE_MAX_SRC + 2)   /* the doubles of a record */
+
+/* per job after a run; slots a job does not have (sources past n_src; for RESTORE everything but kept[0]) are zero */
+typedef struct {
+  double abs_sum[VLM_MERGE_MAX_SRC];    /* step 6: a[m] */
+  double uni_sum[VLM_MERGE_MAX_SRC];    /* step 6: b[m] */
+  uint64_t kept[VLM_MERGE_MAX_SRC];
+  uint64_t zero;
+  uint64_t conflict;
+  float rescale[VLM_MERGE_MAX_SRC];     /* step 7 */
+} vlm_emr_result_t;
+
+/* Bytes of device workspace an EMR plan for n_jobs jobs over total_elems elements needs (header, jobs, chunk table, first-chunk
+ * table, one record per chunk, one result per job).  The masks are the caller's tensors, not part of the workspace.  No reference
+ * site. */
+size_t vlm_emr_plan_bytes(int n_jobs, uint64_t total_elems);
+/* Check the jobs (the checks of vlm_dare_plan_upload on dst, base, the sources and the length: pointers non-NULL and 16-byte
+ * aligned, base required, 1 <= n_src <= VLM_MERGE_MAX_SRC and n_elem > 0, dst's byte range meets an input's only where it is that
+ * input exactly; a valid op; a RESTORE job has n_src == 1, mask[0] and a finite rescale >= 0; a MERGE job has no mask or one per
+ * source; every mask 16-byte aligned and clear of the job's tensors and other masks; else VLM_ERR_ARG; a length or chunk count past
+ * 32 bits of float4s is VLM_ERR_UNSUPPORTED), build the chunk table on the host and copy header + jobs + tables into `workspace`
+ * (16-byte aligned; VLM_ERR_WORKSPACE if it is too small).  SYNCHRONISES `stream` before it returns (pageable temporary source);
+ * it is the last host synchronisation of a plan.  Implements no step of the rule; no reference site. */
+int vlm_emr_plan_upload(const vlm_emr_job_t* jobs_host, int n_jobs, void* workspace, size_t workspace_bytes, void* stream);
+/* Run an uploaded plan: ONE streaming launch over all jobs of both ops (steps 1-6 and the counts, one record per chunk; the rule
+ * of a RESTORE job), then the fold of every job's records in chunk order, which ends in step 7 and writes every job's whole
+ * vlm_emr_result_t; no host synchronisation.  May be called again on the same workspace and gives the same bytes, mask words and
+ * results.  One run at a time per workspace.  No reference site. */
+int vlm_emr_run(void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue (K1/K6/K8/K9/K10): replaces F.linear at
  * modules/vision_transformer.py:335 (qkv + cat(q_bias,0,v_bias)), :360 (proj), :291/:295 (fc1/fc2),
  * LayerScale + residual at :586/:603 (x + drop_path(gamma * branch)), heads.py:14,27,36,49, and the

@@ -229,6 +229,36 @@ class StockResult(ctypes.Structure):
                 ("scale", c_float), ("reserved", ctypes.c_uint32)]
 
 
+EMR_MERGE, EMR_RESTORE = 0, 1
+EMR_SUMS = 3 * MERGE_MAX_SRC + 2  # VLM_EMR_SUMS: the doubles of a chunk's record
+
+
+class EmrJob(ctypes.Structure):
+    """vlm_emr_job_t of include/vlm_hip.h."""
+    _fields_ = [
+        ("dst", c_void_p),
+        ("base", c_void_p),
+        ("src", c_void_p * MERGE_MAX_SRC),
+        ("mask", c_void_p * MERGE_MAX_SRC),
+        ("n_elem", c_u64),
+        ("n_src", ctypes.c_int32),
+        ("op", ctypes.c_int32),
+        ("lam", c_float),
+        ("rescale", c_float),
+    ]
+
+
+class EmrHeader(ctypes.Structure):
+    """vlm_emr_header_t: the first bytes of an EMR plan's workspace (vlm_pairstats_header_t's fields)."""
+    _fields_ = list(PairStatsHeader._fields_)
+
+
+class EmrResult(ctypes.Structure):
+    """vlm_emr_result_t: the sums, the counts and the rescalers of one job."""
+    _fields_ = [("abs_sum", ctypes.c_double * MERGE_MAX_SRC), ("uni_sum", ctypes.c_double * MERGE_MAX_SRC),
+                ("kept", c_u64 * MERGE_MAX_SRC), ("zero", c_u64), ("conflict", c_u64), ("rescale", c_float * MERGE_MAX_SRC)]
+
+
 SCE_COUNTERS = 3  # VLM_SCE_COUNTERS: kept, conflict, empty
 
 
@@ -408,6 +438,9 @@ SIGNATURES = {
     "vlm_tall_plan_bytes": (c_size_t, [c_int, c_u64]),
     "vlm_tall_plan_upload": (c_int, [ctypes.POINTER(TallJob), c_int, c_void_p, c_size_t, c_void_p]),
     "vlm_tall_run": (c_int, [c_void_p, c_void_p]),
+    "vlm_emr_plan_bytes": (c_size_t, [c_int, c_u64]),
+    "vlm_emr_plan_upload": (c_int, [ctypes.POINTER(EmrJob), c_int, c_void_p, c_size_t, c_void_p]),
+    "vlm_emr_run": (c_int, [c_void_p, c_void_p]),
     "vlm_gemm_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                               c_int, ctypes.POINTER(Epilogue), c_void_p]),
     "vlm_gemm_bf16_live": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,

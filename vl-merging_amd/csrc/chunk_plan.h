@@ -5,7 +5,7 @@
 // This is the family's host side, stated once: the chunk table, the checks every job passes (chunk_job_check, chunk_jobs_check),
 // the host image "header, jobs, chunk table" (chunk_layout_t, chunk_image), its upload and the grid rule -- and the two plans
 // that several methods share whole: the COUNTER plan (header, jobs, chunks, counters per job: dare.hip, tall.hip) and the RECORD
-// plan (header, jobs, chunks, first[], one record per chunk, one result per job: pairstats.hip, stock.hip; sphere.hip puts its
+// plan (header, jobs, chunks, first[], one record per chunk, one result per job: pairstats.hip, stock.hip, emr.hip; sphere.hip puts its
 // tiles between).  The device side -- the chunk walker, a workgroup's run loop, the source-count dispatch, the counter plan's
 // view -- is chunk_walk.h; the record plan's reducer is chunk_records.h.
 // Everything but the uploads, the grid and the runs compiles without HIP (tests/helpers/chunk_plan_check.cpp does so).

@@ -1,4 +1,4 @@
-// The record reducer of the merge family (pairstats.hip, stock.hip and sphere.hip through gram_reduce.h, sce.hip), stated once:
+// The record reducer of the merge family (pairstats.hip, stock.hip and sphere.hip through gram_reduce.h, sce.hip, emr.hip), stated once:
 // a pass over the chunk table that leaves ONE record of f64 sums per chunk, at the chunk's index, so that how the chunks were
 // dealt to workgroups cannot show in a result.  The pinned order of every sum (include/vlm_hip.h): thread, wave by halves,
 // ((w0 + w1) + w2) + w3, the records of a job added in chunk order, every sum from +0.0.

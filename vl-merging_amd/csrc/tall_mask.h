@@ -1,5 +1,5 @@
-// The packed masks of the consensus merge (tall.hip): where an element's bit lives, and the checks vlm_tall_plan_upload makes on a
-// job's op, scalars and mask pointers.  A mask of n elements is ceil(n / 32) 32-bit words; element i is bit (i & 31) of word
+// The packed masks of the consensus merge (tall.hip) and of EMR-Merging (emr.hip): where an element's bit lives, and the checks
+// vlm_tall_plan_upload and vlm_emr_plan_upload make on a job's op, scalars and mask pointers.  A mask of n elements is ceil(n / 32) 32-bit words; element i is bit (i & 31) of word
 // i >> 5, bit 0 the least significant; the bits at positions >= n of the last word are zero.
 // The streaming pass moves float4s, so it sees a mask as nibbles: float4 idx4 (elements 4 idx4 .. 4 idx4 + 3) is nibble idx4 & 7 of
 // word idx4 >> 3.  A 16-KiB chunk starts at a multiple of 1024 float4s and thread t takes float4 start4 + t + 256 u, so the eight
@@ -25,17 +25,15 @@ static inline bool tall_bytes_meet(const void* a, uint64_t na, const void* b, ui
   return x < y ? (y - x) < na : (x - y) < nb;
 }
 
-// What vlm_tall_plan_upload asks of a job beyond chunk_job_check: a valid op, k in [0, n_src], tall_lambda >= 0 (a NaN fails the
-// comparison); RESTORE: one source and its mask; CONSENSUS: no mask or one per source; every mask 16-byte aligned and its
-// 4 ceil(n / 32) bytes clear of dst, the base, every source and every other mask of the job.  Call it after chunk_job_check:
-// the length is known to be in range.
+// What a job with packed masks (fields dst, base, src, mask, n_src, n_elem: tall.hip's and emr.hip's) is asked about them.
+// `restore`: the job reads ONE mask -- one source and its mask; otherwise it writes them -- no mask or one per source.  Every mask
+// 16-byte aligned and its 4 ceil(n / 32) bytes clear of dst, the base, every source and every other mask of the job.  Call it
+// after chunk_job_check: the length is known to be in range.
 template <class Job>
-static inline int tall_job_check(const Job& j) {
-  if (j.op != VLM_TALL_CONSENSUS && j.op != VLM_TALL_RESTORE) return VLM_ERR_ARG;
-  if (j.k < 0 || j.k > j.n_src || !(j.tall_lambda >= 0.0f)) return VLM_ERR_ARG;
+static inline int tall_masks_check(const Job& j, bool restore) {
   int n_mask = 0;
   for (int m = 0; m < j.n_src; ++m) n_mask += j.mask[m] ? 1 : 0;
-  if (j.op == VLM_TALL_RESTORE ? (j.n_src != 1 || n_mask != 1) : (n_mask != 0 && n_mask != j.n_src)) return VLM_ERR_ARG;
+  if (restore ? (j.n_src != 1 || n_mask != 1) : (n_mask != 0 && n_mask != j.n_src)) return VLM_ERR_ARG;
   const uint64_t mb = 4 * tall_mask_words(j.n_elem), tb = 4 * j.n_elem;
   for (int m = 0; m < j.n_src && n_mask; ++m) {
     const void* p = j.mask[m];
@@ -47,4 +45,22 @@ static inline int tall_job_check(const Job& j) {
       if (tall_bytes_meet(p, mb, j.mask[o], mb)) return VLM_ERR_ARG;
   }
   return VLM_OK;
+}
+
+// What vlm_tall_plan_upload asks of a job beyond chunk_job_check: a valid op, k in [0, n_src], tall_lambda >= 0 (a NaN fails the
+// comparison), then tall_masks_check.
+template <class Job>
+static inline int tall_job_check(const Job& j) {
+  if (j.op != VLM_TALL_CONSENSUS && j.op != VLM_TALL_RESTORE) return VLM_ERR_ARG;
+  if (j.k < 0 || j.k > j.n_src || !(j.tall_lambda >= 0.0f)) return VLM_ERR_ARG;
+  return tall_masks_check(j, j.op == VLM_TALL_RESTORE);
+}
+
+// What vlm_emr_plan_upload asks of a job beyond chunk_job_check: a valid op; RESTORE: a rescale that is finite and >= 0 (a NaN
+// fails both comparisons); then tall_masks_check.
+template <class Job>
+static inline int emr_job_check(const Job& j) {
+  if (j.op != VLM_EMR_MERGE && j.op != VLM_EMR_RESTORE) return VLM_ERR_ARG;
+  if (j.op == VLM_EMR_RESTORE && !(j.rescale >= 0.0f && j.rescale <= 3.402823466e+38f)) return VLM_ERR_ARG;
+  return tall_masks_check(j, j.op == VLM_EMR_RESTORE);
 }

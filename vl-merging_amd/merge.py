@@ -44,6 +44,17 @@ an integer k in [0, S] and lam; fp32 rounds once, no FMA:
   6. the keep_m, packed 32 to a word (bit 0 first), are the TALL masks
 It is the first method that decides per element by comparing an expert with the others, and the first whose streaming pass has a
 bit-packed side output.  tall_restore is the reverse direction: ufo + masks -> all_moe, dst = bit ? unified : central per expert.
+
+emr_merge (EMR-Merging: elect, mask, rescale; Huang et al. 2024) likewise: no reference site, csrc/emr.hip held to
+tests/emr_restatement.py.  Its rule (include/vlm_hip.h), per tensor with central tensor c, sources W_0 .. W_{S-1} and lam:
+  1. x_m = W_m - c
+  2. s = ((0 + x_0) + x_1) + ...; its sign by comparison
+  3. agree_m = x_m has the sign of s;  e = max over the agreeing m of |x_m|;  u = sign(s) * e
+  4. dst = c + lam * u
+  5. the agree_m, packed as the TALL masks are
+  6. a[m] = sum f64(|x_m|), b[m] = sum (agree_m ? f64(e) : 0) in the family's pinned order;  rescale[m] = f32(a[m] / b[m])
+emr_restore is the way back: dst = central + rescale * (bit ? unified - central : 0) per expert.  Rescalers are per tensor, not per
+model, and an element with s == 0 contributes nothing: the two departures from the paper's code.
 """
 import ctypes
 import math
@@ -808,12 +819,7 @@ class TallPlan(_Plan):
         """One expert's tensor: out[i] = bit i of `mask` ? unified[i] : base[i].  `mask`: an int32 tensor of ceil(n / 32) words (a CPU
         tensor is copied to the device)."""
         n = unified.numel()
-        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.numel() != tall_mask_words(n):
-            raise L.VlmError("a mask for %d elements is an int32 tensor of %d words, got %s" % (
-                n, tall_mask_words(n), "%s x %d" % (mask.dtype, mask.numel()) if isinstance(mask, torch.Tensor) else type(mask).__name__))
-        mask = mask.detach().reshape(-1)
-        if mask.device != self.device or not mask.is_contiguous() or (mask.data_ptr() & 15):
-            mask = mask.to(self.device, copy=True).contiguous()
+        mask = _packed_mask(mask, n, self.device)
 
         def fill(job):
             job.op = L.TALL_RESTORE
@@ -899,7 +905,159 @@ def tall_restore(unified_state_dict, masks, config, central_weight=None, device=
     return out
 
 
-SPHERE_STATUS = {L.SPHERE_OK: "ok", L.SPHERE_LINEAR: "linear", L.SPHERE_ZERO: "zero"}
+EMR_OPS = {L.EMR_MERGE: "emr", L.EMR_RESTORE: "restore"}
+
+
+def emr_rescale(rescale):
+    """The rescaler of an EMR restore job as a python float: a finite number >= 0."""
+    if isinstance(rescale, bool) or not isinstance(rescale, (int, float)) or not (0.0 <= rescale < float("inf")):  # also rejects NaN
+        raise ValueError("an EMR rescaler must be a finite number >= 0, got %r" % (rescale,))
+    return float(rescale)
+
+
+def _packed_mask(mask, n, device):
+    """`mask` as a restore job reads it: an int32 tensor of ceil(n / 32) words, flat, contiguous and 16-byte aligned on `device` (a
+    CPU tensor is copied there); VlmError if it is not a mask of n elements."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.numel() != tall_mask_words(n):
+        raise L.VlmError("a mask for %d elements is an int32 tensor of %d words, got %s" % (
+            n, tall_mask_words(n), "%s x %d" % (mask.dtype, mask.numel()) if isinstance(mask, torch.Tensor) else type(mask).__name__))
+    mask = mask.detach().reshape(-1)
+    if mask.device != device or not mask.is_contiguous() or (mask.data_ptr() & 15):
+        mask = mask.to(device, copy=True).contiguous()
+    return mask
+
+
+class EmrPlan(_Plan):
+    """The job table of csrc/emr.hip; run() enqueues the one streaming launch that serves both ops -- the EMR merge (add) and the
+    restore of one expert from the unified tensor, the central tensor, a packed mask and a rescaler (add_restore) -- and the fold
+    that ends in the rescalers, without a host synchronisation.  self.masks[job] holds a merge job's mask tensors (int32,
+    ceil(n / 32) words per source; None without masks) or the one mask a restore job reads."""
+
+    KIND, GPU_ONLY, JOB = "EMR", "the EMR kernels run on the GPU only", L.EmrJob
+    BYTES, UPLOAD, RUN, HEADER = "vlm_emr_plan_bytes", "vlm_emr_plan_upload", "vlm_emr_run", L.EmrHeader
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.masks: List[Optional[List[torch.Tensor]]] = []
+
+    def add(self, srcs, base, lam=1.0, masks=False, out=None, name=None):
+        """One output tensor.  `out` may be `base` or one of `srcs` (the pass is elementwise) or any tensor that meets none of them.
+        `masks=True` allocates one int32 tensor of ceil(n / 32) words per source, kept in self.masks[job]; every run writes every
+        word of them."""
+        n = srcs[0].numel()
+        made = [torch.empty(tall_mask_words(n), dtype=torch.int32, device=self.device) for _ in srcs] if masks else None
+
+        def fill(job):
+            job.op = L.EMR_MERGE
+            job.lam, job.rescale = float(lam), 0.0
+            for m in range(job.n_src if made else 0):
+                job.mask[m] = made[m].data_ptr()
+        out = self._add(fill, srcs, base, out, name)
+        self.masks.append(made)
+        self.bytes_written += 4 * tall_mask_words(n) * len(srcs) if made else 0
+        return out
+
+    def add_restore(self, unified, base, mask, rescale, out=None, name=None):
+        """One expert's tensor: out[i] = base[i] + rescale * (bit i of `mask` ? unified[i] - base[i] : 0).  `mask`: an int32 tensor
+        of ceil(n / 32) words (a CPU tensor is copied to the device); `rescale`: a finite number >= 0."""
+        rescale = emr_rescale(rescale)
+        n = unified.numel()
+        mask = _packed_mask(mask, n, self.device)
+
+        def fill(job):
+            job.op = L.EMR_RESTORE
+            job.lam, job.rescale = 1.0, rescale
+            job.mask[0] = mask.data_ptr()
+        out = self._add(fill, [unified], base, out, name)
+        self.masks.append([mask])
+        self.bytes_read += 4 * tall_mask_words(n)
+        return out
+
+    def results(self):
+        """The raw vlm_emr_result_t of every job as the device left it (this synchronises)."""
+        return self._structs(L.EmrResult, self._header().results_off, len(self.jobs))
+
+    def report(self):
+        """Per job, read back after a run (this synchronises): `op` ("emr" | "restore"), `kept` per source (the bits set in its
+        mask; restore: the elements taken from the unified tensor), `zero` (the elements whose task vectors sum to zero: nothing is
+        elected there), `conflict` (the elements whose task vectors disagree in sign), per source `abs_sum` (the L1 mass of its
+        task vector) and `uni_sum` (that of the masked unified task vector), and `rescale` = float32(abs_sum / uni_sum) as python
+        floats that print the fp32 values exactly -- all as the device made them.  A restore job has one `kept` and empty lists."""
+        rows = []
+        for name, job, r in zip(self.names, self.jobs, self.results()):
+            S = job.n_src if job.op == L.EMR_MERGE else 0
+            rows.append({"dst": name, "n": int(job.n_elem), "op": EMR_OPS[int(job.op)], "kept": [int(r.kept[m]) for m in range(job.n_src)],
+                         "zero": int(r.zero), "conflict": int(r.conflict), "abs_sum": [r.abs_sum[m] for m in range(S)],
+                         "uni_sum": [r.uni_sum[m] for m in range(S)], "rescale": [float(r.rescale[m]) for m in range(S)]})
+        return rows
+
+
+def emr_merge(state_dict, config, central_weight=None, lam=None, masks_out: Optional[dict] = None, rescalers_out: Optional[dict] = None,
+              device="cuda", plan_out: Optional[list] = None, report_out: Optional[list] = None):
+    """EMR-Merging (Huang et al. 2024: elect, mask, rescale) of the modality experts' task vectors `W_m - central` (no reference
+    site; the rule: include/vlm_hip.h): per element the sign of the summed task vectors is elected, the unified task vector takes
+    the largest magnitude among the experts that agree with it, and central + lam * that is the merged tensor.  Per expert the
+    method also leaves an agreement mask (one bit per element) and one scalar per tensor, the rescaler, which gives the masked
+    unified task vector the L1 mass of the expert's own: with them emr_restore rebuilds an approximation of every expert from the
+    lam = 1 merge.  Tuning-free: there is no parameter beside lam.  Two departures from the paper's code: rescalers are per tensor,
+    not per model (layers have different expert sets), and an element whose task vectors sum to zero contributes nothing.
+    Same inputs, keys, pass-through and KeyError behaviour as sum_task_vectors, ties_merge and consensus_merge; `lam=None` takes
+    config["sum_lambda"].  A layer with ONE source is the task-vector job with ratio 1 that sum_task_vectors issues for it.
+    `masks_out`, if a dict, receives {source key (e.g. transformer.blocks.3.attn.v.qkv.weight): int32 device tensor of
+    ceil(n / 32) words} for every tensor with several sources; `rescalers_out`, if a dict, {source key: python float, the fp32
+    rescaler exactly} (reading it back synchronises).  `plan_out` receives the EmrPlan FIRST whenever a layer has several sources,
+    then the MergePlan of the single-source layers if there are any; `report_out` receives EmrPlan.report() (reading it back
+    synchronises)."""
+    keys = []
+
+    def add(plan, dst, srcs, c, lam, mods):
+        out = plan.add(srcs, c, lam=lam, masks=masks_out is not None, name=dst)
+        keys.append([_SRC_OF[dst](m) for m in mods])
+        if masks_out is not None:
+            masks_out.update(zip(keys[-1], plan.masks[-1]))
+        return out
+    plans = []
+    out = _task_vector_merge(EmrPlan, add, state_dict, config, central_weight, lam, device, plans, report_out)
+    if plan_out is not None:
+        plan_out.extend(plans)
+    if rescalers_out is not None and keys:
+        for ks, r in zip(keys, plans[0].results()):
+            rescalers_out.update((key, float(r.rescale[m])) for m, key in enumerate(ks))
+    return out
+
+
+def emr_restore(unified_state_dict, masks, rescalers, config, central_weight=None, device="cuda", plan_out: Optional[list] = None):
+    """ufo + EMR masks and rescalers -> all_moe: rebuilds an approximation of every modality expert from the unified checkpoint
+    (the lam = 1 output of emr_merge), the central checkpoint and what emr_merge(masks_out=..., rescalers_out=...) left (no
+    reference site; the restore rule: include/vlm_hip.h).  Returns an all_moe-keyed state_dict: for every source key in `masks`,
+    central + rescaler * (bit ? unified - central : 0) of the destination key's tensors; for a layer with ONE source, the unified
+    tensor itself under the source key; non-block keys pass through by identity.  The unified block keys themselves are not
+    returned.  A key of `masks` that names no source of a multi-source layer under `config` is a KeyError, and so is a key that has
+    a mask but no rescaler; a mask whose word count does not fit its tensor is a VlmError.  One job per expert and tensor: each
+    re-reads the unified and the central tensor.  `plan_out` receives the EmrPlan if it has jobs."""
+    out = _passthrough(unified_state_dict)
+    central = _central(central_weight, config)
+    plan = EmrPlan(device)
+    seen = set()
+    for i in range(NUM_MERGE_LAYERS):
+        mods = modalities_for_layer(config, i)
+        for src, dst in _tensor_names(i):
+            if len(mods) == 1:
+                out[src(mods[0])] = unified_state_dict[dst]
+                continue
+            for m in mods:
+                key = src(m)
+                if key in masks:
+                    out[key] = plan.add_restore(unified_state_dict[dst], central[dst], masks[key], rescalers[key], name=key)
+                    seen.add(key)
+    missing = [key for key in masks if key not in seen]
+    if missing:
+        raise KeyError("masks name no source of a multi-source layer: %s" % ", ".join(sorted(missing)[:4]))
+    _finish(plan, plan_out)
+    return out
+
+
+SPHERE_STATUS ={L.SPHERE_OK: "ok", L.SPHERE_LINEAR: "linear", L.SPHERE_ZERO: "zero"}
 
 
 class SpherePlan(_Plan):

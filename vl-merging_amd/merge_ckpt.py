@@ -1,12 +1,12 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus,emr} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
 sum_task_vectors / regmean on the state_dict it has just read); a merged checkpoint on disk is what one hands on, so this tool
 runs the same merges (merge.merge_weights, merge.sum_task_vectors), TIES (merge.ties_merge), DARE (merge.dare_merge), Model
 Breadcrumbs (merge.band_merge), DELLA (merge.della_merge), Model Stock (merge.stock_merge), SCE (merge.sce_merge), the spherical merge (merge.sphere_merge) and
-the consensus merge with TALL masks (merge.consensus_merge; none of the eight has a reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
+the consensus merge with TALL masks (merge.consensus_merge) and EMR-Merging (merge.emr_merge; none of the nine has a reference site) outside a model.  The words after the options are a config in run.py's grammar (`config.parse_cli`): they decide
 `vlffn_start_layer_index`, `only_activate_used_experts`, `loss_names`, `merge_ratio`, `sum_lambda`, `central_weight`.
 
   --method interp    merge_weights      (--ratio overrides merge_ratio)
@@ -28,6 +28,10 @@ the consensus merge with TALL masks (merge.consensus_merge; none of the eight ha
                                          relevant to it, --consensus-k = how many experts must find an element relevant,
                                          --masks-out M.pt = also write the packed TALL masks, from which tall_restore.py
                                          rebuilds the experts; --lambda, --central as above)
+  --method emr       emr_merge          (elect a sign, take the largest agreeing magnitude; tuning-free: --lambda and --central as
+                                         above are all it reads.  --masks-out M.pt = also write {format: emr-masks-1, masks,
+                                         rescalers}: one agreement bit per element and expert and one scalar per tensor and
+                                         expert, from which tall_restore.py rebuilds the experts -- merge with --lambda 1 for that)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
                      dare: n, keep_below, kept per source, conflict, empty;
                      breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty;
@@ -36,7 +40,8 @@ the consensus merge with TALL masks (merge.consensus_merge; none of the eight ha
                      sce: n, K, the variance threshold, kept, sq and weight per source, tot, conflict, empty;
                      slerp: n, row_len, weights, lam and, per tensor, sq, dot per pair, coef64, coef32 and its bits, rho, resid,
                      status -- per row instead: rows, rows_linear, rows_zero, resid_max;
-                     consensus: n, op, k, tall_lambda, kept per source, selected, empty)
+                     consensus: n, op, k, tall_lambda, kept per source, selected, empty;
+                     emr: n, op, kept per source, zero, conflict, abs_sum, uni_sum and rescale per source)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -51,7 +56,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus", "emr")
 
 
 def build_parser():
@@ -89,7 +94,8 @@ def build_parser():
                    help="consensus: keep an element iff at least k experts find it relevant (a layer with S experts uses min(k, S)); "
                         "0 is plain task arithmetic")
     p.add_argument("--masks-out", dest="masks_out", default=None,
-                   help="consensus: write {format: tall-masks-1, tall_lambda, k, masks: {source key: int32 words}} here")
+                   help="consensus: write {format: tall-masks-1, tall_lambda, k, masks: {source key: int32 words}} here; "
+                        "emr: write {format: emr-masks-1, masks: {source key: int32 words}, rescalers: {source key: float}} here")
     p.add_argument("--report", default=None, help="write a JSON report here")
     p.add_argument("config", nargs="*", help="with <named configs> key=value ... (as for run.py)")
     return p
@@ -123,16 +129,16 @@ def parse_args(argv):
         merge = importlib.import_module("vl_merging_amd.merge")
         merge.tall_threshold(args.tall_lambda)  # the one statement of each rule; ValueError
         merge.consensus_k(args.consensus_k)
-    elif args.masks_out is not None:
-        raise ValueError("--masks-out belongs to --method consensus (got %s)" % args.method)
+    elif args.method != "emr" and args.masks_out is not None:
+        raise ValueError("--masks-out belongs to --method consensus or emr (got %s)" % args.method)
     return args, cfg
 
 
 def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None, della=None, sphere=None,
-                consensus=None):
+                consensus=None, emr=None):
     """The merged state_dict (device tensors for merged keys, the input's objects for the rest).  `dare`: the keyword arguments of
     merge.dare_merge (drop, seed, mode, rescale); `band`: those of merge.band_merge beside the density (gamma, mode); `della`: those of
-    merge.della_merge beside the density (epsilon, seed, mode, rescale); `sphere`: those of merge.sphere_merge (on, rows); `consensus`: those of merge.consensus_merge (tall_lambda, k, masks_out)."""
+    merge.della_merge beside the density (epsilon, seed, mode, rescale); `sphere`: those of merge.sphere_merge (on, rows); `consensus`: those of merge.consensus_merge (tall_lambda, k, masks_out); `emr`: those of merge.emr_merge (masks_out, rescalers_out)."""
     merge = importlib.import_module("vl_merging_amd.merge")
     if method == "interp":
         out = merge.merge_weights(sd, cfg)
@@ -168,6 +174,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
         out = merge.consensus_merge(sd, cfg, central_weight=central, report_out=rows, **(consensus or {}))
         if report is not None:
             report.extend(rows)
+    elif method == "emr":
+        rows = []
+        out = merge.emr_merge(sd, cfg, central_weight=central, report_out=rows, **(emr or {}))
+        if report is not None:
+            report.extend(rows)
     elif method == "breadcrumbs":
         rows = []
         out = merge.band_merge(sd, cfg, central_weight=central, density=density, report_out=rows, **(band or {}))
@@ -196,17 +207,22 @@ def main(argv):
     is_dare, is_band, is_della = args.method == "dare", args.method == "breadcrumbs", args.method == "della"
     is_sphere = args.method in ("slerp", "karcher")
     is_tall = args.method == "consensus"
-    masks = {} if is_tall and args.masks_out else None
+    is_emr = args.method == "emr"
+    masks = {} if (is_tall or is_emr) and args.masks_out else None
+    rescalers = {} if masks is not None and is_emr else None
     has_density = args.method in ("ties", "sce") or is_band or is_della
     out = merge_state(args.method, sd, cfg, central=central, density=args.density, report=report,
                       dare=dict(drop=args.drop, seed=args.seed, mode=args.dare_mode, rescale=args.rescale),
                       band=dict(gamma=args.gamma, mode=args.band_mode),
                       della=dict(epsilon=args.epsilon, seed=args.seed, mode=args.della_mode, rescale=args.rescale),
                       sphere=dict(on=args.sphere_on, rows=args.sphere_rows),
-                      consensus=dict(tall_lambda=args.tall_lambda, k=args.consensus_k, masks_out=masks))
+                      consensus=dict(tall_lambda=args.tall_lambda, k=args.consensus_k, masks_out=masks),
+                      emr=dict(masks_out=masks, rescalers_out=rescalers))
     torch.cuda.synchronize()
     torch.save({"state_dict": {k: v.detach().to("cpu") for k, v in out.items()}}, args.out)
-    if masks is not None:
+    if rescalers is not None:
+        torch.save({"format": "emr-masks-1", "masks": {k: v.to("cpu") for k, v in masks.items()}, "rescalers": rescalers}, args.masks_out)
+    elif masks is not None:
         torch.save({"format": "tall-masks-1", "tall_lambda": args.tall_lambda, "k": args.consensus_k,
                     "masks": {k: v.to("cpu") for k, v in masks.items()}}, args.masks_out)
     if args.report:

@@ -291,6 +291,12 @@ class ViLTransformerSS(nn.Module):
         return merge_ops.consensus_merge(state_dict, self.hparams.config, tall_lambda=tall_lambda, k=k, lam=lam, masks_out=masks_out,
                                          device=self._merge_device())
 
+    def emr_merge(self, state_dict, lam=None, masks_out=None, rescalers_out=None):
+        """EMR-Merging (elect, mask, rescale) of the experts' task vectors (no reference site; merge.emr_merge).  Same contract as
+        sum_task_vectors; not wired to a config key and not called from __init__."""
+        return merge_ops.emr_merge(state_dict, self.hparams.config, lam=lam, masks_out=masks_out, rescalers_out=rescalers_out,
+                                   device=self._merge_device())
+
     def band_merge(self, state_dict, density=0.9, gamma=0.01, mode="linear", lam=None):
         """Model Breadcrumbs merge of the experts' task vectors (no reference site; merge.band_merge).  Same contract as
         sum_task_vectors; not wired to a config key and not called from __init__."""

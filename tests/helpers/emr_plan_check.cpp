@@ -1,6 +1,6 @@
 // Host-side checks of what csrc/emr.hip takes from csrc/tall_mask.h and csrc/chunk_plan.h, compiled WITHOUT HIP as a stand-alone
 // program (tests/test_emr_cpu.py builds it with -fsanitize=address,undefined).
-//   emr_plan_check tail N...   walks the slots of every chunk of a job of N elements as emr_chunk does and prints, per N,
+//   emr_plan_check tail N...   walks the slots of every chunk of a job of N elements as mask_chunk does and prints, per N,
 //                              "tail N chunk thread slot": which chunk, thread and slot stand at the partial float4 n4 = N >> 2.
 //                              Exactly one place does when N & 3 != 0 (else the line says "tail N none"); it must be the job's last
 //                              chunk and thread n4 & 255 -- the rule's step 6 -- and every slot of that thread behind it lies past
@@ -26,7 +26,7 @@ static int tail(uint64_t n) {
       for (uint32_t t = 0; t < CHUNK_THREADS; ++t) {
         const uint64_t idx = start4 + t + (uint64_t)u * CHUNK_THREADS;
         const bool have = u < 4 && idx < n4;
-        if (!have && tl != 0 && idx == n4) {  // emr_slot's at_tail
+        if (!have && tl != 0 && idx == n4) {  // mask_slot's at_tail
           ++found;
           at_chunk = c;
           at_thread = t;

@@ -1,5 +1,5 @@
 """Inputs the GPU tests of the merge family (test_merge_gpu.py, test_ties_gpu.py, test_dare_gpu.py, test_pairstats_gpu.py,
-test_band_gpu.py, test_della_gpu.py) share."""
+test_band_gpu.py, test_della_gpu.py, test_tall_gpu.py, test_emr_gpu.py) share."""
 import functools
 
 import numpy as np
@@ -52,3 +52,22 @@ def one_buffer(arrays):
     buf = torch.from_numpy(host).cuda()
     assert buf.data_ptr() % 16 == 0
     return [buf[o:o + a.size] for a, o in zip(arrays, offs)]
+
+
+# ---------------------------------------------------------------- the plans with packed masks (test_tall_gpu.py, test_emr_gpu.py)
+def dev_words(words):
+    return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).cuda()
+
+
+def words_of(t):
+    return t.cpu().numpy().view("<u4")
+
+
+def poison(plan, outs):
+    """Outputs start as NaN and mask outputs as all ones: every float and every word that survives a run was written by it."""
+    for o in outs:
+        o.fill_(float("nan"))
+    for job, ms in zip(plan.jobs, plan.masks):
+        if ms is not None and job.op == 0:
+            for m in ms:
+                m.fill_(-1)

@@ -1,6 +1,6 @@
 // Host-only use of csrc/tall_mask.h (no HIP, no GPU), built and run as a child process by tests/test_tall_cpu.py under
 // AddressSanitizer + UBSan.
-//   tall_pack_check pack N...   for every length N: walks the job's chunks as tall.hip does -- 256 threads, four float4 slots per
+//   tall_pack_check pack N...   for every length N: walks the job's chunks as mask_chunk does -- 256 threads, four float4 slots per
 //                               chunk and the fifth where tall_has_tail_slot says so, eight neighbouring lanes folding their nibbles
 //                               into the word tall_word_of names at the shift tall_shift_of names, the ragged tail taken by the one
 //                               lane that stands at n4 -- with bit i of the mask = pattern(i), into a buffer of EXACTLY

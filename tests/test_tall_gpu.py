@@ -19,7 +19,7 @@ from test_ties_gpu import CASES, is_block, planted, to_dev
 from tall_restatement import consensus, pack, restore
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-from merge_inputs import base_size_state, one_buffer, tiny_jobs  # noqa: E402
+from merge_inputs import base_size_state, dev_words, one_buffer, poison, tiny_jobs, words_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -42,14 +42,6 @@ def rjob(u, c, words):
     return dict(op="restore", u=u, c=c, words=words)
 
 
-def dev_words(words):
-    return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).cuda()
-
-
-def words_of(t):
-    return t.cpu().numpy().view("<u4")
-
-
 def add_job(plan, j, name, base=None, srcs=None, out=None):
     """One job(...) into `plan`; `base` / `srcs`: device tensors to use instead of fresh copies."""
     base = torch.from_numpy(j["c"]).cuda() if base is None else base
@@ -58,16 +50,6 @@ def add_job(plan, j, name, base=None, srcs=None, out=None):
         return plan.add_restore(u, base, dev_words(j["words"]), out=out, name=name)
     srcs = [torch.from_numpy(s).cuda() for s in j["srcs"]] if srcs is None else srcs
     return plan.add(srcs, base, j["tall_lambda"], j["k"], lam=j["lam"], masks=j["masks"], out=out, name=name)
-
-
-def poison(plan, outs):
-    """Outputs start as NaN and mask outputs as all ones: every float and every word that survives a run was written by it."""
-    for o in outs:
-        o.fill_(float("nan"))
-    for job, ms in zip(plan.jobs, plan.masks):
-        if ms is not None and job.op == 0:
-            for m in ms:
-                m.fill_(-1)
 
 
 def run_plan(merge, jobs):

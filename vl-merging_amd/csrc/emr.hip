@@ -6,12 +6,11 @@
 //
 // The pass is the consensus merge's traffic with masks on, 4 (S + 1) B read, 4 B written and S / 8 B of mask per element
 // (RESTORE: 8 B + 1 / 8 B read, 4 B written), plus one 112-B record per 16-KiB chunk.
-//   vlm_emr_pass_kernel   one launch over the plan's chunk table through chunk_reduce_run (chunk_records.h).  The chunk body has
-//                         tall.hip's shape -- every thread of the workgroup enters every float4 slot, 16-B non-temporal loads and
-//                         stores, the eight nibbles of a mask word folded with three __shfl_xor steps and stored by the group
-//                         leader with a plain 4-B store, the ragged tail handled by the ONE lane that stands at the partial float4
-//                         -- and it also gathers, per thread, the f64 addends of step 6 and the counts; their wave sums go to
-//                         chunk_record, which leaves one record at the chunk's index.  Both ops, one kernel.
+//   vlm_emr_pass_kernel   one launch over the plan's chunk table through chunk_reduce_run (chunk_records.h).  The chunk body is
+//                         mask_chunk (mask_chunk.h, shared with tall.hip: the slot every thread enters, the one lane that owns the
+//                         ragged tail, the plain word store); this file's rule also gathers, per thread, the f64 addends of step 6
+//                         and the counts; their wave sums go to chunk_record, which leaves one record at the chunk's index.  Both
+//                         ops, one kernel.
 //   vlm_emr_fold_kernel   one workgroup per job at a time, one thread per slot: the job's records added in chunk order
 //                         (CHUNK_FOLD_RECORDS); then one thread does step 7 and writes the job's whole vlm_emr_result_t.
 // Two launches, ordered by the stream alone.  No atomics; every record and every result is overwritten by each run, so nothing is
@@ -23,10 +22,11 @@
 // S = 4 with masks on): see the figures behind EMR_BLOCKS_PER_CU below; no scratch.  LDS: the two record buffers of
 // chunk_reduce_run, 2 x 4 waves x 14 doubles = 896 B.
 // The run loop, the record writer and the fold are chunk_records.h's, the walker chunk_walk.h's, the record plan (layout, upload)
-// and the host checks chunk_plan.h's, the place of a bit and the checks on a job's masks tall_mask.h's.
+// and the host checks chunk_plan.h's, the chunk body mask_chunk.h's, the place of a bit and the checks on a job's masks tall_mask.h's.
 #include "vlm_common.h"
 #include "chunk_walk.h"
 #include "chunk_records.h"
+#include "mask_chunk.h"
 #include "tall_mask.h"
 
 #define EMR_THREADS CHUNK_THREADS
@@ -48,11 +48,6 @@ static_assert(EMR_SUMS == EMR_CONFLICT + 1 && EMR_SUMS == 14, "a record is a[4],
 static_assert(sizeof(vlm_emr_result_t) == 128 && offsetof(vlm_emr_result_t, uni_sum) == EMR_B * 8 &&
                   offsetof(vlm_emr_result_t, kept) == EMR_KEPT * 8 && offsetof(vlm_emr_result_t, rescale) == EMR_SUMS * 8,
               "a result begins as a record does, then the four rescalers");
-
-// what a chunk does, a compile-time constant of its body
-#define EMR_PLAIN 0     // MERGE without masks
-#define EMR_MASKS 1     // MERGE, one mask per source written
-#define EMR_RESTORE 2   // RESTORE: one mask read
 
 typedef records_view_t<vlm_emr_header_t, vlm_emr_job_t, double, vlm_emr_result_t> emr_view_t;
 __device__ __forceinline__ emr_view_t emr_view(unsigned char* ws) {
@@ -118,116 +113,30 @@ __device__ __forceinline__ float emr_pick(bool bit, float uni, float c, float re
   return __fadd_rn(c, __fmul_rn(rescale, bit ? t : 0.0f));
 }
 
-// One float4 slot of a chunk, entered by EVERY thread of the workgroup (tall.hip's tall_slot).  `have`: float4 idx lies inside the
-// tensor and v (one float4 per source) and b (the base) hold it.  The lane with idx == n4 of a tensor with a ragged tail handles
-// the tail's elements 4 n4 + t, t < tail, as the partial float4 it is -- their addends enter THIS lane's sums, behind its float4s
-// (every later slot of the lane lies past the end), in element order.  Every other lane past the end does nothing but take part
-// in the cross-lane steps, with zero bits.  `scale`: lam (MERGE) or rescale (RESTORE).
-template <int NSRC, int KIND>
-__device__ __forceinline__ void emr_slot(const vlm_emr_job_t& j, uint64_t idx, uint64_t n4, uint32_t tail, uint64_t n_words,
-                                         bool have, const f32x4* v, const f32x4& b, float scale, emr_acc_t<NSRC>& n) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t word = tall_word_of(idx);
-  const uint32_t shift = tall_shift_of(idx);   // == 4 (lane & 7): a chunk starts at a multiple of 8 float4s
-  const bool leader = (lane & 7) == 0 && word < n_words;
-  uint32_t nib[NSRC];                          // MERGE: bit c of nib[m] = agree_m of element c of this float4
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) nib[m] = 0;
-  if (KIND == EMR_RESTORE) {
-    // the leader reads the word once for the 32 elements of its eight lanes -- and only a word the mask has
-    uint32_t w = 0;
-    if (leader) w = __builtin_nontemporal_load(&reinterpret_cast<const uint32_t*>(j.mask[0])[word]);
-    w = __shfl(w, lane & ~7, 64);
-    nib[0] = (w >> shift) & 15u;
-  }
-  const bool at_tail = !have && tail != 0 && idx == n4;
-  if (have) {
-    f32x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (KIND == EMR_RESTORE) {
-        o[c] = emr_pick((nib[0] >> c) & 1u, v[0][c], b[c], scale, n.kept[0]);
-      } else {
-        float w[NSRC];
-#pragma unroll
-        for (int m = 0; m < NSRC; ++m) w[m] = v[m][c];
-        uint32_t agree;
-        o[c] = emr_elem<NSRC>(b[c], w, scale, n, agree);
-#pragma unroll
-        for (int m = 0; m < NSRC; ++m) nib[m] |= ((agree >> m) & 1u) << c;
-      }
-    }
-    __builtin_nontemporal_store(o, &reinterpret_cast<f32x4*>(j.dst)[idx]);
-  } else if (at_tail) {
-    for (uint32_t t = 0; t < tail; ++t) {
-      const uint64_t i = (n4 << 2) + t;  // < n_elem
-      float w[NSRC];
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m) w[m] = reinterpret_cast<const float*>(j.src[m])[i];
-      const float bt = reinterpret_cast<const float*>(j.base)[i];
-      float o;
-      if (KIND == EMR_RESTORE) {
-        o = emr_pick((nib[0] >> t) & 1u, w[0], bt, scale, n.kept[0]);
-      } else {
-        uint32_t agree;
-        o = emr_elem<NSRC>(bt, w, scale, n, agree);
-#pragma unroll
-        for (int m = 0; m < NSRC; ++m) nib[m] |= ((agree >> m) & 1u) << t;
-      }
-      reinterpret_cast<float*>(j.dst)[i] = o;
-    }
-  }
-  if (KIND == EMR_MASKS) {
-    // step 5, the whole wave active: eight nibbles -> one word in every lane of the eight; the leader stores it, with a plain
-    // store (docs/experiments.md, "Consensus merge": streamed past L2 the words cost 9 % of the pass instead of 2 %)
-#pragma unroll
-    for (int m = 0; m < NSRC; ++m) {
-      uint32_t w = nib[m] << shift;
-      w |= __shfl_xor(w, 1, 64);
-      w |= __shfl_xor(w, 2, 64);
-      w |= __shfl_xor(w, 4, 64);
-      if (leader) reinterpret_cast<uint32_t*>(j.mask[m])[word] = w;
-    }
-  }
-}
+// what mask_chunk asks of a method: `scale`, lam (MERGE) or rescale (RESTORE), and the thread's sums and counts, by reference
+template <int NSRC>
+struct emr_rule_t {
+  float scale;
+  emr_acc_t<NSRC>& n;
+  __device__ __forceinline__ float elem(float c, const float* w, uint32_t& bits) { return emr_elem<NSRC>(c, w, scale, n, bits); }
+  __device__ __forceinline__ float pick(bool bit, float u, float c) { return emr_pick(bit, u, c, scale, n.kept[0]); }
+};
 
-// The chunk at start4 of job j: chunk_stream's loads (4 float4 per thread, strided by the block, all issued before the first
-// use), the slots, then the wave sums of what the threads gathered into red[wave][slot] (lane 0 writes; only the slots the job has:
-// emr_slot_used).  No __restrict__: dst may be the base or a source exactly; every load of a float4 precedes its store.
+// The chunk at start4 of job j: mask_chunk (mask_chunk.h) with this file's rule, then the wave sums of what the threads gathered
+// into red[wave][slot] (lane 0 writes; only the slots the job has: emr_slot_used).
 template <int NSRC, int KIND>
 __device__ __forceinline__ void emr_chunk(const vlm_emr_job_t& j, uint64_t start4, double* red) {
-  const uint64_t n4 = j.n_elem >> 2, n_words = tall_mask_words(j.n_elem);
-  const uint32_t tail = (uint32_t)(j.n_elem & 3);
-  const float scale = KIND == EMR_RESTORE ? j.rescale : j.lam;
-  const f32x4* base = reinterpret_cast<const f32x4*>(j.base);
-  const f32x4* s[NSRC];
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) s[m] = reinterpret_cast<const f32x4*>(j.src[m]);
-  f32x4 v[4][NSRC];
-  f32x4 b[4];
-  uint64_t idx[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    idx[u] = start4 + threadIdx.x + u * CHUNK_THREADS;
-    if (idx[u] < n4) {
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m) v[u][m] = __builtin_nontemporal_load(&s[m][idx[u]]);
-      b[u] = __builtin_nontemporal_load(&base[idx[u]]);
-    }
-  }
   emr_acc_t<NSRC> n;
   n.clear();
-#pragma unroll
-  for (int u = 0; u < 4; ++u) emr_slot<NSRC, KIND>(j, idx[u], n4, tail, n_words, idx[u] < n4, v[u], b[u], scale, n);
-  if (tall_has_tail_slot(start4, j.n_elem))  // workgroup-uniform
-    emr_slot<NSRC, KIND>(j, start4 + CHUNK_FLOATS / 4 + threadIdx.x, n4, tail, n_words, false, v[0], b[0], scale, n);
+  emr_rule_t<NSRC> rule = {KIND == MASK_RESTORE ? j.rescale : j.lam, n};
+  mask_chunk<NSRC, KIND>(j, start4, rule);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double* r = red + wave * EMR_SUMS;
   auto put_n = [&](int slot, uint32_t c) {
     c = chunk_wave_sum(c);
     if (lane == 0) r[slot] = (double)c;
   };
-  if (KIND == EMR_RESTORE) {
+  if (KIND == MASK_RESTORE) {
     put_n(EMR_KEPT, n.kept[0]);
   } else {
 #pragma unroll
@@ -257,11 +166,11 @@ __global__ __launch_bounds__(EMR_THREADS) void vlm_emr_pass_kernel(unsigned char
       w.chunks, w.jobs, w.hdr->n_chunks, w.first, w.records, [](uint32_t) {},
       [](const vlm_emr_job_t& j, uint64_t start4, double* r) {
         if (j.op == VLM_EMR_RESTORE) {
-          emr_chunk<1, EMR_RESTORE>(j, start4, r);
+          emr_chunk<1, MASK_RESTORE>(j, start4, r);
         } else {
           with_nsrc(j.n_src, [&](auto S) {
-            if (j.mask[0]) emr_chunk<S(), EMR_MASKS>(j, start4, r);
-            else emr_chunk<S(), EMR_PLAIN>(j, start4, r);
+            if (j.mask[0]) emr_chunk<S(), MASK_WRITE>(j, start4, r);
+            else emr_chunk<S(), MASK_PLAIN>(j, start4, r);
           });
         }
       },

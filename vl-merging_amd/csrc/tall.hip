@@ -10,18 +10,15 @@
 //                           workgroup owns a CONTIGUOUS run of chunks, 16-B non-temporal loads and stores (mask words: plain
 //                           4-B stores, one per eight lanes), and the per-job
 //                           counters flushed (64-bit integer atomics) when the run leaves a job.  Both ops, one kernel.
-// The chunk body is this file's own, not chunk_stream: the mask words need the lanes of a wave to talk to each other, and
-// chunk_stream computes under `if (idx < n4)`.  Here a float4 SLOT is walked by the whole workgroup: a lane whose float4 lies
-// past the end computes nothing and contributes a zero nibble, and the eight lanes that hold one word's nibbles (tall_mask.h)
-// fold them with three __shfl_xor steps that every lane of the wave executes.  The ragged tail is not a separate path of
-// threads 0 .. 2: it is the partial float4 n4, handled by the ONE lane that stands at n4, so its bits enter the same fold as its
-// neighbours' and the tensor's last word -- float4 lanes, tail bits, zero padding -- is written once, by one lane.  Where n4 lies
-// just behind the tail chunk's last float4 the chunk walks a fifth slot for it (tall_has_tail_slot).
+// The chunk body is not chunk_stream but mask_chunk (mask_chunk.h, shared with emr.hip; the slot every thread enters, the one
+// lane that owns the ragged tail and the plain word store are explained there): this file gives it the rule per element, steps
+// 1-5 and the restore select, and the counters.
 // Integer counters only, so nothing depends on the order workgroups run in.  -ffp-contract=off and __f*_rn: one rounding per
 // operation, no FMA.  The run loop and the workspace's view are chunk_walk.h's, the counter plan (layout, upload, the two-launch
 // run) and the family's host checks chunk_plan.h's, as in dare.hip.
 #include "vlm_common.h"
 #include "chunk_walk.h"  // the run loop, the source-count dispatch and the counters: the whole family's
+#include "mask_chunk.h"  // the chunk body of the methods with packed masks
 #include "tall_mask.h"   // where an element's bit lives; the checks on a job's masks
 
 #define TALL_THREADS CHUNK_THREADS
@@ -29,11 +26,6 @@
 
 static_assert(VLM_TALL_COUNTERS == VLM_TIES_COUNTERS, "tall.hip counts into chunk_walk.h's ties_counts_t");
 #define TALL_SELECTED TIES_CONFLICT   // the slot behind kept[]: the elements with sel
-
-// what a chunk does, a compile-time constant of its body
-#define TALL_PLAIN 0     // CONSENSUS without masks
-#define TALL_MASKS 1     // CONSENSUS, one mask per source written
-#define TALL_RESTORE 2   // RESTORE: one mask read
 
 typedef counts_view_t<vlm_tall_header_t, vlm_tall_job_t> tall_view_t;
 
@@ -75,107 +67,14 @@ __device__ __forceinline__ float tall_pick(bool bit, float u, float c, ties_coun
   return bit ? u : c;
 }
 
-// One float4 slot of a chunk, entered by EVERY thread of the workgroup.  `have`: float4 idx lies inside the tensor and v (one
-// float4 per source) and b (the base) hold it.  The lane with idx == n4 of a tensor with a ragged tail handles the tail's
-// elements 4 n4 + t, t < tail, as the partial float4 it is.  Every other lane past the end does nothing but take part in the
-// cross-lane steps, with zero bits.
-template <int NSRC, int KIND>
-__device__ __forceinline__ void tall_slot(const vlm_tall_job_t& j, uint64_t idx, uint64_t n4, uint32_t tail, uint64_t n_words,
-                                          bool have, const f32x4* v, const f32x4& b, const tall_param_t& p, ties_counts_t& n) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t word = tall_word_of(idx);
-  const uint32_t shift = tall_shift_of(idx);   // == 4 (lane & 7): a chunk starts at a multiple of 8 float4s
-  const bool leader = (lane & 7) == 0 && word < n_words;
-  uint32_t nib[NSRC];                          // CONSENSUS: bit c of nib[m] = keep_m of element c of this float4
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) nib[m] = 0;
-  if (KIND == TALL_RESTORE) {
-    // the leader reads the word once for the 32 elements of its eight lanes -- and only a word the mask has
-    uint32_t w = 0;
-    if (leader) w = __builtin_nontemporal_load(&reinterpret_cast<const uint32_t*>(j.mask[0])[word]);
-    w = __shfl(w, lane & ~7, 64);
-    nib[0] = (w >> shift) & 15u;
-  }
-  const bool at_tail = !have && tail != 0 && idx == n4;
-  if (have) {
-    f32x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (KIND == TALL_RESTORE) {
-        o[c] = tall_pick((nib[0] >> c) & 1u, v[0][c], b[c], n);
-      } else {
-        float w[NSRC];
-#pragma unroll
-        for (int m = 0; m < NSRC; ++m) w[m] = v[m][c];
-        uint32_t keep;
-        o[c] = tall_elem<NSRC>(b[c], w, p, n, keep);
-#pragma unroll
-        for (int m = 0; m < NSRC; ++m) nib[m] |= ((keep >> m) & 1u) << c;
-      }
-    }
-    __builtin_nontemporal_store(o, &reinterpret_cast<f32x4*>(j.dst)[idx]);
-  } else if (at_tail) {
-    for (uint32_t t = 0; t < tail; ++t) {
-      const uint64_t i = (n4 << 2) + t;  // < n_elem
-      float w[NSRC];
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m) w[m] = reinterpret_cast<const float*>(j.src[m])[i];
-      const float bt = reinterpret_cast<const float*>(j.base)[i];
-      float o;
-      if (KIND == TALL_RESTORE) {
-        o = tall_pick((nib[0] >> t) & 1u, w[0], bt, n);
-      } else {
-        uint32_t keep;
-        o = tall_elem<NSRC>(bt, w, p, n, keep);
-#pragma unroll
-        for (int m = 0; m < NSRC; ++m) nib[m] |= ((keep >> m) & 1u) << t;
-      }
-      reinterpret_cast<float*>(j.dst)[i] = o;
-    }
-  }
-  if (KIND == TALL_MASKS) {
-    // step 6, the whole wave active: eight nibbles -> one word in every lane of the eight; the leader stores it.  A plain store,
-    // not a non-temporal one: a wave's eight words are 32 B and the four waves of a workgroup fill one 128-B line between them,
-    // which L2 puts together when the words may stay there; streamed past it they cost 9 % of the pass instead of 2 %
-    // (docs/experiments.md, "Consensus merge").
-#pragma unroll
-    for (int m = 0; m < NSRC; ++m) {
-      uint32_t w = nib[m] << shift;
-      w |= __shfl_xor(w, 1, 64);
-      w |= __shfl_xor(w, 2, 64);
-      w |= __shfl_xor(w, 4, 64);
-      if (leader) reinterpret_cast<uint32_t*>(j.mask[m])[word] = w;
-    }
-  }
-}
-
-// The chunk at start4 of job j: chunk_stream's loads (4 float4 per thread, strided by the block, all issued before the first
-// use), then the slots.  No __restrict__: dst may be the base or a source exactly; every load of a float4 precedes its store.
-template <int NSRC, int KIND>
-__device__ __forceinline__ void tall_chunk(const vlm_tall_job_t& j, uint64_t start4, const tall_param_t& p, ties_counts_t& n) {
-  const uint64_t n4 = j.n_elem >> 2, n_words = tall_mask_words(j.n_elem);
-  const uint32_t tail = (uint32_t)(j.n_elem & 3);
-  const f32x4* base = reinterpret_cast<const f32x4*>(j.base);
-  const f32x4* s[NSRC];
-#pragma unroll
-  for (int m = 0; m < NSRC; ++m) s[m] = reinterpret_cast<const f32x4*>(j.src[m]);
-  f32x4 v[4][NSRC];
-  f32x4 b[4];
-  uint64_t idx[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    idx[u] = start4 + threadIdx.x + u * CHUNK_THREADS;
-    if (idx[u] < n4) {
-#pragma unroll
-      for (int m = 0; m < NSRC; ++m) v[u][m] = __builtin_nontemporal_load(&s[m][idx[u]]);
-      b[u] = __builtin_nontemporal_load(&base[idx[u]]);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) tall_slot<NSRC, KIND>(j, idx[u], n4, tail, n_words, idx[u] < n4, v[u], b[u], p, n);
-  if (tall_has_tail_slot(start4, j.n_elem))  // workgroup-uniform
-    tall_slot<NSRC, KIND>(j, start4 + CHUNK_FLOATS / 4 + threadIdx.x, n4, tail, n_words, false, v[0], b[0], p, n);
-}
+// what mask_chunk asks of a method: a job's scalars and the thread's counters, by reference
+template <int NSRC>
+struct tall_rule_t {
+  const tall_param_t& p;
+  ties_counts_t& n;
+  __device__ __forceinline__ float elem(float c, const float* w, uint32_t& bits) { return tall_elem<NSRC>(c, w, p, n, bits); }
+  __device__ __forceinline__ float pick(bool bit, float u, float c) { return tall_pick(bit, u, c, n); }
+};
 
 __global__ __launch_bounds__(TALL_THREADS) void vlm_tall_clear_kernel(unsigned char* __restrict__ ws) {
   const tall_view_t w = counts_view<vlm_tall_header_t, vlm_tall_job_t>(ws);
@@ -201,11 +100,13 @@ __global__ __launch_bounds__(TALL_THREADS) void vlm_tall_apply_kernel(unsigned c
       },
       [&](const vlm_tall_job_t& j, uint64_t start4) {
         if (j.op == VLM_TALL_RESTORE) {
-          tall_chunk<1, TALL_RESTORE>(j, start4, p, n);
+          tall_rule_t<1> rule = {p, n};
+          mask_chunk<1, MASK_RESTORE>(j, start4, rule);
         } else {
           with_nsrc(j.n_src, [&](auto S) {
-            if (j.mask[0]) tall_chunk<S(), TALL_MASKS>(j, start4, p, n);
-            else tall_chunk<S(), TALL_PLAIN>(j, start4, p, n);
+            tall_rule_t<S()> rule = {p, n};
+            if (j.mask[0]) mask_chunk<S(), MASK_WRITE>(j, start4, rule);
+            else mask_chunk<S(), MASK_PLAIN>(j, start4, rule);
           });
         }
       },

@@ -5,7 +5,8 @@
 // word idx4 >> 3.  A 16-KiB chunk starts at a multiple of 1024 float4s and thread t takes float4 start4 + t + 256 u, so the eight
 // lanes t & ~7 .. t | 7 of a wave hold the eight nibbles of ONE word, in order.  The ragged tail (n & 3 elements) is the partial
 // float4 n4 = n >> 2: nibble n4 & 7 of word n4 >> 3, which is the tensor's last word.
-// Compiles without HIP (tests/helpers/tall_pack_check.cpp does so).
+// Compiles without HIP (tests/helpers/tall_pack_check.cpp does so); the device body that walks a chunk by these rules is
+// mask_chunk.h's.
 #pragma once
 #include "chunk_plan.h"
 

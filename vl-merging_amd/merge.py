@@ -1,4 +1,5 @@
-"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock, SCE, SLERP / Karcher mean, Consensus merging with TALL masks (and the restore of the experts from them) -- and the expert-pair statistics
+"""Checkpoint merging on the GPU: interpolation, task-vector arithmetic, RegMean, TIES, DARE, Breadcrumbs, DELLA, Model Stock, SCE,
+SLERP / Karcher mean, Consensus merging with TALL masks (and the restore of the experts from them) -- and the expert-pair statistics
 (expert_stats) that say how far apart the experts are before any of them is tried.
 
 Drop-in for ViLTransformerSS.merge_weights / sum_task_vectors / regmean
@@ -778,21 +779,66 @@ def tall_mask_words(n):
     return (int(n) + 31) // 32
 
 
-TALL_OPS = {L.TALL_CONSENSUS: "consensus", L.TALL_RESTORE: "restore"}
+def _packed_mask(mask, n, device):
+    """`mask` as a restore job reads it: an int32 tensor of ceil(n / 32) words, flat, contiguous and 16-byte aligned on `device` (a
+    CPU tensor is copied there); VlmError if it is not a mask of n elements."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.numel() != tall_mask_words(n):
+        raise L.VlmError("a mask for %d elements is an int32 tensor of %d words, got %s" % (
+            n, tall_mask_words(n), "%s x %d" % (mask.dtype, mask.numel()) if isinstance(mask, torch.Tensor) else type(mask).__name__))
+    mask = mask.detach().reshape(-1)
+    if mask.device != device or not mask.is_contiguous() or (mask.data_ptr() & 15):
+        mask = mask.to(device, copy=True).contiguous()
+    return mask
 
 
-class TallPlan(_Plan):
-    """The job table of csrc/tall.hip; run() enqueues the counter reset and the one streaming launch that serves both ops -- the
-    consensus merge (add) and the restore of one expert from the unified tensor, the central tensor and a packed mask
-    (add_restore) -- without a host synchronisation.  self.masks[job] holds a consensus job's mask tensors (int32, ceil(n / 32)
-    words per source; None without masks) or the one mask a restore job reads."""
-
-    KIND, GPU_ONLY, JOB = "consensus", "the consensus kernel runs on the GPU only", L.TallJob
-    BYTES, UPLOAD, RUN, HEADER = "vlm_tall_plan_bytes", "vlm_tall_plan_upload", "vlm_tall_run", L.TallHeader
+class _MaskedPlan(_Plan):
+    """A plan whose jobs have packed masks (csrc/mask_chunk.h): a merge job writes none or one per source, a restore job reads
+    one.  self.masks[job] holds a merge job's mask tensors (int32, ceil(n / 32) words per source; None without masks) or the one
+    mask a restore job reads.  A subclass's add() and add_restore() validate their own arguments and hand the two helpers a
+    `fill(job)` for the fields of their own."""
 
     def __init__(self, device):
         super().__init__(device)
         self.masks: List[Optional[List[torch.Tensor]]] = []
+
+    def _add_masked(self, fill, srcs, base, masks, out, name):
+        """A merge job: _add, and with `masks` one int32 tensor of ceil(n / 32) words per source, allocated here, in job.mask."""
+        n = srcs[0].numel()
+        made = [torch.empty(tall_mask_words(n), dtype=torch.int32, device=self.device) for _ in srcs] if masks else None
+
+        def fill_masks(job):
+            fill(job)
+            for m in range(job.n_src if made else 0):
+                job.mask[m] = made[m].data_ptr()
+        out = self._add(fill_masks, srcs, base, out, name)
+        self.masks.append(made)
+        self.bytes_written += 4 * tall_mask_words(n) * len(srcs) if made else 0
+        return out
+
+    def _add_restore(self, fill, unified, base, mask, out, name):
+        """A restore job: _add with the one source `unified`, and `mask` (_packed_mask) in job.mask[0]."""
+        n = unified.numel()
+        mask = _packed_mask(mask, n, self.device)
+
+        def fill_mask(job):
+            fill(job)
+            job.mask[0] = mask.data_ptr()
+        out = self._add(fill_mask, [unified], base, out, name)
+        self.masks.append([mask])
+        self.bytes_read += 4 * tall_mask_words(n)
+        return out
+
+
+TALL_OPS = {L.TALL_CONSENSUS: "consensus", L.TALL_RESTORE: "restore"}
+
+
+class TallPlan(_MaskedPlan):
+    """The job table of csrc/tall.hip; run() enqueues the counter reset and the one streaming launch that serves both ops -- the
+    consensus merge (add) and the restore of one expert from the unified tensor, the central tensor and a packed mask
+    (add_restore) -- without a host synchronisation.  self.masks: _MaskedPlan's."""
+
+    KIND, GPU_ONLY, JOB = "consensus", "the consensus kernel runs on the GPU only", L.TallJob
+    BYTES, UPLOAD, RUN, HEADER = "vlm_tall_plan_bytes", "vlm_tall_plan_upload", "vlm_tall_run", L.TallHeader
 
     def add(self, srcs, base, tall_lambda, k, lam=1.0, masks=False, out=None, name=None):
         """One output tensor.  `out` may be `base` or one of `srcs` (the pass is elementwise) or any tensor that meets none of them.
@@ -800,35 +846,21 @@ class TallPlan(_Plan):
         word of them."""
         tall_lambda = tall_threshold(tall_lambda)
         k = consensus_k(k, len(srcs))
-        n = srcs[0].numel()
-        made = [torch.empty(tall_mask_words(n), dtype=torch.int32, device=self.device) for _ in srcs] if masks else None
 
         def fill(job):
             job.op = L.TALL_CONSENSUS
             job.k = k
             job.tall_lambda = tall_lambda
             job.lam = float(lam)
-            for m in range(job.n_src if made else 0):
-                job.mask[m] = made[m].data_ptr()
-        out = self._add(fill, srcs, base, out, name)
-        self.masks.append(made)
-        self.bytes_written += 4 * tall_mask_words(n) * len(srcs) if made else 0
-        return out
+        return self._add_masked(fill, srcs, base, masks, out, name)
 
     def add_restore(self, unified, base, mask, out=None, name=None):
         """One expert's tensor: out[i] = bit i of `mask` ? unified[i] : base[i].  `mask`: an int32 tensor of ceil(n / 32) words (a CPU
         tensor is copied to the device)."""
-        n = unified.numel()
-        mask = _packed_mask(mask, n, self.device)
-
         def fill(job):
             job.op = L.TALL_RESTORE
             job.k, job.tall_lambda, job.lam = 0, 0.0, 1.0
-            job.mask[0] = mask.data_ptr()
-        out = self._add(fill, [unified], base, out, name)
-        self.masks.append([mask])
-        self.bytes_read += 4 * tall_mask_words(n)
-        return out
+        return self._add_restore(fill, unified, base, mask, out, name)
 
     def report(self):
         """Per job, read back after a run (this synchronises): `op` ("consensus" | "restore"), `k`, `tall_lambda`, `kept` per source
@@ -844,6 +876,32 @@ class TallPlan(_Plan):
 
 # dst -> source template of every merged tensor name
 _SRC_OF = {dst: src for i in range(NUM_MERGE_LAYERS) for src, dst in _tensor_names(i)}
+
+
+def _restore(plan_type, add, unified_state_dict, masks, config, central_weight, device, plan_out):
+    """The walk tall_restore and emr_restore share, ufo + masks -> all_moe: for every source key in `masks`,
+    `add(plan, unified tensor, central tensor, key)` of the destination key's tensors; a layer with ONE source hands the unified
+    tensor through under the source key; KeyError for a key of `masks` that names no source of a multi-source layer."""
+    out = _passthrough(unified_state_dict)
+    central = _central(central_weight, config)
+    plan = plan_type(device)
+    seen = set()
+    for i in range(NUM_MERGE_LAYERS):
+        mods = modalities_for_layer(config, i)
+        for src, dst in _tensor_names(i):
+            if len(mods) == 1:
+                out[src(mods[0])] = unified_state_dict[dst]
+                continue
+            for m in mods:
+                key = src(m)
+                if key in masks:
+                    out[key] = add(plan, unified_state_dict[dst], central[dst], key)
+                    seen.add(key)
+    missing = [key for key in masks if key not in seen]
+    if missing:
+        raise KeyError("masks name no source of a multi-source layer: %s" % ", ".join(sorted(missing)[:4]))
+    _finish(plan, plan_out)
+    return out
 
 
 def consensus_merge(state_dict, config, central_weight=None, tall_lambda=0.4, k=2, lam=None, masks_out: Optional[dict] = None,
@@ -883,26 +941,8 @@ def tall_restore(unified_state_dict, masks, config, central_weight=None, device=
     `masks` that names no source of a multi-source layer under `config` is a KeyError; a mask whose word count does not fit its
     tensor is a VlmError.  One job per expert and tensor: each re-reads the unified and the central tensor.  `plan_out` receives
     the TallPlan if it has jobs."""
-    out = _passthrough(unified_state_dict)
-    central = _central(central_weight, config)
-    plan = TallPlan(device)
-    seen = set()
-    for i in range(NUM_MERGE_LAYERS):
-        mods = modalities_for_layer(config, i)
-        for src, dst in _tensor_names(i):
-            if len(mods) == 1:
-                out[src(mods[0])] = unified_state_dict[dst]
-                continue
-            for m in mods:
-                key = src(m)
-                if key in masks:
-                    out[key] = plan.add_restore(unified_state_dict[dst], central[dst], masks[key], name=key)
-                    seen.add(key)
-    missing = [key for key in masks if key not in seen]
-    if missing:
-        raise KeyError("masks name no source of a multi-source layer: %s" % ", ".join(sorted(missing)[:4]))
-    _finish(plan, plan_out)
-    return out
+    return _restore(TallPlan, lambda plan, uni, c, key: plan.add_restore(uni, c, masks[key], name=key),
+                    unified_state_dict, masks, config, central_weight, device, plan_out)
 
 
 EMR_OPS = {L.EMR_MERGE: "emr", L.EMR_RESTORE: "restore"}
@@ -915,63 +955,32 @@ def emr_rescale(rescale):
     return float(rescale)
 
 
-def _packed_mask(mask, n, device):
-    """`mask` as a restore job reads it: an int32 tensor of ceil(n / 32) words, flat, contiguous and 16-byte aligned on `device` (a
-    CPU tensor is copied there); VlmError if it is not a mask of n elements."""
-    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.numel() != tall_mask_words(n):
-        raise L.VlmError("a mask for %d elements is an int32 tensor of %d words, got %s" % (
-            n, tall_mask_words(n), "%s x %d" % (mask.dtype, mask.numel()) if isinstance(mask, torch.Tensor) else type(mask).__name__))
-    mask = mask.detach().reshape(-1)
-    if mask.device != device or not mask.is_contiguous() or (mask.data_ptr() & 15):
-        mask = mask.to(device, copy=True).contiguous()
-    return mask
-
-
-class EmrPlan(_Plan):
+class EmrPlan(_MaskedPlan):
     """The job table of csrc/emr.hip; run() enqueues the one streaming launch that serves both ops -- the EMR merge (add) and the
     restore of one expert from the unified tensor, the central tensor, a packed mask and a rescaler (add_restore) -- and the fold
-    that ends in the rescalers, without a host synchronisation.  self.masks[job] holds a merge job's mask tensors (int32,
-    ceil(n / 32) words per source; None without masks) or the one mask a restore job reads."""
+    that ends in the rescalers, without a host synchronisation.  self.masks: _MaskedPlan's."""
 
     KIND, GPU_ONLY, JOB = "EMR", "the EMR kernels run on the GPU only", L.EmrJob
     BYTES, UPLOAD, RUN, HEADER = "vlm_emr_plan_bytes", "vlm_emr_plan_upload", "vlm_emr_run", L.EmrHeader
-
-    def __init__(self, device):
-        super().__init__(device)
-        self.masks: List[Optional[List[torch.Tensor]]] = []
 
     def add(self, srcs, base, lam=1.0, masks=False, out=None, name=None):
         """One output tensor.  `out` may be `base` or one of `srcs` (the pass is elementwise) or any tensor that meets none of them.
         `masks=True` allocates one int32 tensor of ceil(n / 32) words per source, kept in self.masks[job]; every run writes every
         word of them."""
-        n = srcs[0].numel()
-        made = [torch.empty(tall_mask_words(n), dtype=torch.int32, device=self.device) for _ in srcs] if masks else None
-
         def fill(job):
             job.op = L.EMR_MERGE
             job.lam, job.rescale = float(lam), 0.0
-            for m in range(job.n_src if made else 0):
-                job.mask[m] = made[m].data_ptr()
-        out = self._add(fill, srcs, base, out, name)
-        self.masks.append(made)
-        self.bytes_written += 4 * tall_mask_words(n) * len(srcs) if made else 0
-        return out
+        return self._add_masked(fill, srcs, base, masks, out, name)
 
     def add_restore(self, unified, base, mask, rescale, out=None, name=None):
         """One expert's tensor: out[i] = base[i] + rescale * (bit i of `mask` ? unified[i] - base[i] : 0).  `mask`: an int32 tensor
         of ceil(n / 32) words (a CPU tensor is copied to the device); `rescale`: a finite number >= 0."""
         rescale = emr_rescale(rescale)
-        n = unified.numel()
-        mask = _packed_mask(mask, n, self.device)
 
         def fill(job):
             job.op = L.EMR_RESTORE
             job.lam, job.rescale = 1.0, rescale
-            job.mask[0] = mask.data_ptr()
-        out = self._add(fill, [unified], base, out, name)
-        self.masks.append([mask])
-        self.bytes_read += 4 * tall_mask_words(n)
-        return out
+        return self._add_restore(fill, unified, base, mask, out, name)
 
     def results(self):
         """The raw vlm_emr_result_t of every job as the device left it (this synchronises)."""
@@ -1035,26 +1044,8 @@ def emr_restore(unified_state_dict, masks, rescalers, config, central_weight=Non
     returned.  A key of `masks` that names no source of a multi-source layer under `config` is a KeyError, and so is a key that has
     a mask but no rescaler; a mask whose word count does not fit its tensor is a VlmError.  One job per expert and tensor: each
     re-reads the unified and the central tensor.  `plan_out` receives the EmrPlan if it has jobs."""
-    out = _passthrough(unified_state_dict)
-    central = _central(central_weight, config)
-    plan = EmrPlan(device)
-    seen = set()
-    for i in range(NUM_MERGE_LAYERS):
-        mods = modalities_for_layer(config, i)
-        for src, dst in _tensor_names(i):
-            if len(mods) == 1:
-                out[src(mods[0])] = unified_state_dict[dst]
-                continue
-            for m in mods:
-                key = src(m)
-                if key in masks:
-                    out[key] = plan.add_restore(unified_state_dict[dst], central[dst], masks[key], rescalers[key], name=key)
-                    seen.add(key)
-    missing = [key for key in masks if key not in seen]
-    if missing:
-        raise KeyError("masks name no source of a multi-source layer: %s" % ", ".join(sorted(missing)[:4]))
-    _finish(plan, plan_out)
-    return out
+    return _restore(EmrPlan, lambda plan, uni, c, key: plan.add_restore(uni, c, masks[key], rescalers[key], name=key),
+                    unified_state_dict, masks, config, central_weight, device, plan_out)
 
 
 SPHERE_STATUS ={L.SPHERE_OK: "ok", L.SPHERE_LINEAR: "linear", L.SPHERE_ZERO: "zero"}

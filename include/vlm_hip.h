@@ -1245,6 +1245,48 @@ int vlm_cholesky_f64_batched(double* const* A_list, int count, int n, int* statu
 int vlm_solve_spd_right_f64_batched(double* const* chol_list, int n, double* const* rhs_list, int ld, int rows, int count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Iso-C: isotropic merging (Marczak et al. 2025, "No Task Left Behind: Isotropic Model Merging with Common and Task-Specific
+ * Subspaces") of a weight MATRIX, csrc/isoc.hip + csrc/f64ops.hip.  No reference site.  The rule, per destination matrix [m, n]
+ * with central tensor c, sources W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), lam and r = min(m, n); fp32 values are widened
+ * exactly, every operation is one correctly rounded fp64 operation, no FMA outside the matrix products:
+ *   1. D = ((0 + (W_0 - c)) + (W_1 - c)) + ...          (the SUM of the task vectors, not their mean)
+ *   2. with D = U diag(sigma) V^T the thin SVD:  Q = U V^T over the non-zero sigma (the polar factor of D);  nuclear = sum sigma
+ *   3. dst = fl32(c + s * Q) with s = (lam * nuclear) / r, product, quotient, product and sum in this order, ONE rounding to fp32
+ *   4. ||D||_F = 0:  dst = c bit for bit
+ * Q comes from a Cholesky-based QDWH iteration instead of an SVD.  The matrix is worked on as [rows >= cols] (D^T when m < n):
+ *   alpha = ||D||_F;  X_0 = D / alpha;  per step with host-made coefficients (a, b, c):
+ *     Z = I + c X^T X  (vlm_iso_gram);  L = chol(Z)  (vlm_cholesky_f64_batched);  Y = X (L L^T)^-1  (vlm_solve_spd_right_f64_batched);
+ *     X <- (b / c) X + (a - b / c) Y  (vlm_iso_step, which also records ||X_new - X||_F^2)
+ *   then Q = X and nuclear = <X, D>  (vlm_iso_finish).
+ * X_0 is never formed: the first vlm_iso_gram reads D and folds 1 / alpha^2 in from the device, the first vlm_iso_step divides by
+ * alpha.  Nothing here synchronises; the caller reads the heads whenever it chooses.
+ *
+ * The working set of one matrix is ONE device allocation of VLM_ISO_HEAD + 3 * m * n doubles: the head, then D, X and Y, each
+ * [rows][cols] row-major.  head[0] = ||D||_F^2, head[1] = <X, D>, head[2 + k] = ||X_{k+1} - X_k||_F^2 of step k < VLM_ISO_MAX_STEPS.
+ * Every call takes `count` (<= 64) matrices of ONE shape in lock step; the lists are HOST arrays of device pointers.  `partials`:
+ * device scratch of count * vlm_iso_parts(m, n) doubles; the sums are made in a fixed order (the same bits every run).  c, the
+ * sources and dst are contiguous and 16-byte aligned; dst may be c or a source.
+ *   vlm_iso_delta   D (and Y = D) and head[0] from c_list[count] and src_list[S][count]
+ *   vlm_iso_gram    Z_list[b] [cols][cols] = I + f X^T X, upper-triangular tiles computed, mirrored on the way out; first: the
+ *                   operand is D and f = c / head[0] (0 where head[0] is not positive), else the operand is X and f = c
+ *   vlm_iso_step    X <- p X + q Y, Y <- X, head[2 + k]; first: X is D / alpha and Y is divided by alpha as well
+ *   vlm_iso_finish  two phases, either or both (`phases`, a bit mask): VLM_ISO_PHASE_NUCLEAR head[1] = <X, D>; VLM_ISO_PHASE_APPLY
+ *                   dst_list[b] by step 3 and 4 from head[1] as it stands.  The apply phase READS c: where dst is c, a second apply
+ *                   would add the step twice -- a caller that may iterate further applies once, after its verdict (isoc.py does) */
+#define VLM_ISO_HEAD 64
+#define VLM_ISO_MAX_STEPS 40
+#define VLM_ISO_PHASE_NUCLEAR 1
+#define VLM_ISO_PHASE_APPLY 2
+int vlm_iso_parts(int m, int n);
+int vlm_iso_delta(const float* const* c_list, const float* const* src_list, int S, int m, int n, double* const* work_list,
+                  double* partials, int count, void* stream);
+int vlm_iso_gram(double* const* work_list, int rows, int cols, int first, double c, double* const* Z_list, int count, void* stream);
+int vlm_iso_step(double* const* work_list, int rows, int cols, int first, double p, double q, int k, double* partials, int count,
+                 void* stream);
+int vlm_iso_finish(double* const* work_list, const float* const* c_list, float* const* dst_list, int m, int n, double lam,
+                   double* partials, int count, int phases, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused attention (K4 + K7 + K7b): softmax(scale*Q K^T + bias[h] + key mask) V, head_dim = 64.
  * Replaces Attention.forward's core, modules/vision_transformer.py:346-358, the bias materialisation
  * get_rel_pos_bias modules/vilt_module.py:1061-1064 (never formed here), and the text/image block-diagonal

@@ -141,6 +141,9 @@ class TallHeader(ctypes.Structure):
 DELLA_LINEAR, DELLA_TIES = 0, 1
 DELLA_COUNTERS = MERGE_MAX_SRC + 2  # VLM_DELLA_COUNTERS: kept per source, conflict, empty
 DELLA_MAX_ROW = 4096                # VLM_DELLA_MAX_ROW: the longest row whose ranks one workgroup makes in LDS
+ISO_HEAD = 64                       # VLM_ISO_HEAD: doubles in front of an Iso-C working set (norms, step norms)
+ISO_MAX_STEPS = 40                  # VLM_ISO_MAX_STEPS
+ISO_PHASE_NUCLEAR, ISO_PHASE_APPLY = 1, 2  # VLM_ISO_PHASE_*: the phases of vlm_iso_finish, a bit mask
 
 
 class DellaJob(ctypes.Structure):
@@ -482,6 +485,14 @@ SIGNATURES = {
                                      ctypes.POINTER(c_void_p), c_int, ctypes.c_double, ctypes.POINTER(c_void_p), c_int, c_int, c_void_p]),
     "vlm_cholesky_f64_batched": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
     "vlm_solve_spd_right_f64_batched": (c_int, [ctypes.POINTER(c_void_p), c_int, ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_void_p]),
+    "vlm_iso_parts": (c_int, [c_int, c_int]),
+    "vlm_iso_delta": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.POINTER(c_void_p),
+                              c_void_p, c_int, c_void_p]),
+    "vlm_iso_gram": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.c_double, ctypes.POINTER(c_void_p), c_int, c_void_p]),
+    "vlm_iso_step": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_int,
+                             c_void_p]),
+    "vlm_iso_finish": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int,
+                               ctypes.c_double, c_void_p, c_int, c_int, c_void_p]),
     "vlm_cross_entropy_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     "vlm_cross_entropy_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p]),

@@ -8,6 +8,7 @@
 // MFMA f64 16x16x4 operand layout: A[16][4]: lane l holds A[l & 15][l >> 4]; B[4][16]: lane l holds B[l >> 4][l & 15];
 // C/D[16][16]: register r of lane l holds row 4*r + (l >> 4) of column l & 15.
 #include "vlm_common.h"
+#include "f64_tab.h"
 
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
@@ -104,9 +105,29 @@ struct f64_acc_t {
 // ---------------------------------------------------------------------------------------------------- Gram (SYRK)
 // G[D][D] += X^T X for X [M][D] (bf16 or fp32 activations, converted exactly), upper-triangular tiles only, mirrored on
 // the way out; the M rows are cut into gridDim.z slices that meet in G through fp64 atomics.
-template <typename T>
-__global__ __launch_bounds__(256) void gram_f64_kernel(const T* __restrict__ x, int ldx, int M, int D, double* __restrict__ g) {
+// The same body is Iso-C's polar step Z = I + f X^T X for a TABLE of fp64 operands (P = gram_iso_t, blockIdx.y the matrix): one
+// slice, so every element is one accumulator chain in a fixed order, stored plainly -- no atomics, the same bits every run.
+// f = c, or c / ||D||_F^2 from the matrix's own head on the first step, where the operand is D and X_0 = D / ||D||_F is never
+// formed (an all-zero D gives Z = I).
+struct gram_sum_t {
+  static constexpr bool ISO = false;
+};
+struct gram_iso_t {
+  static constexpr bool ISO = true;
+  f64_tab_t W, Z;  // the matrices' working sets (f64_tab.h) and their [D][D] results
+  size_t off;      // of the operand inside a working set
+  double c;
+  int first;
+};
+template <typename T, typename P>
+__global__ __launch_bounds__(256) void gram_f64_kernel(const T* __restrict__ x_, int ldx, int M, int D, double* __restrict__ g_, const P p) {
   __shared__ double sa[F64_LDS_DOUBLES], sb[F64_LDS_DOUBLES];
+  const T* __restrict__ x = x_;
+  double* __restrict__ g = g_;
+  if constexpr (P::ISO) {
+    x = reinterpret_cast<const T*>(p.W.p[blockIdx.y] + p.off);
+    g = p.Z.p[blockIdx.y];
+  }
   // blockIdx.x enumerates tile pairs (ti <= tj)
   const int nt = (D + F64_TILE - 1) / F64_TILE;
   int ti = 0, rem = blockIdx.x;
@@ -120,10 +141,43 @@ __global__ __launch_bounds__(256) void gram_f64_kernel(const T* __restrict__ x, 
     f64_tile_mac(acc.v, k0, k1,
                  [&](int k, int c) { return i0 + c < D ? f64_load(x + (size_t)k * ldx + i0 + c) : 0.0; },
                  [&](int k, int c) { return j0 + c < D ? f64_load(x + (size_t)k * ldx + j0 + c) : 0.0; }, sa, sb);
-  acc.for_each(i0, j0, D, D, [&](int i, int j, double v) {
-    atomicAdd(g + (size_t)i * D + j, v);
-    if (ti != tj) atomicAdd(g + (size_t)j * D + i, v);  // (a diagonal tile is computed in full)
-  });
+  if constexpr (P::ISO) {
+    double f = p.c;
+    if (p.first) {
+      const double fro2 = p.W.p[blockIdx.y][ISO_FRO2];
+      f = fro2 > 0.0 ? p.c / fro2 : 0.0;
+    }
+    acc.for_each(i0, j0, D, D, [&](int i, int j, double v) {
+      const double z = __dadd_rn(i == j ? 1.0 : 0.0, __dmul_rn(f, v));
+      g[(size_t)i * D + j] = z;
+      if (ti != tj) g[(size_t)j * D + i] = z;
+    });
+  } else {
+    acc.for_each(i0, j0, D, D, [&](int i, int j, double v) {
+      atomicAdd(g + (size_t)i * D + j, v);
+      if (ti != tj) atomicAdd(g + (size_t)j * D + i, v);  // (a diagonal tile is computed in full)
+    });
+  }
+}
+
+// Z_b = I + f X_b^T X_b for `count` working sets of ONE shape [rows][cols] (include/vlm_hip.h: Iso-C).  A general
+// vlm_gemm_f64_batched(ta = 1) would compute both triangles: twice the flops of the step's largest product.
+extern "C" int vlm_iso_gram(double* const* work_list, int rows, int cols, int first, double c, double* const* Z_list, int count,
+                            void* stream) {
+  if (rows == 0 || cols == 0 || count == 0) return VLM_OK;
+  if (rows < cols || cols < 0) return VLM_ERR_ARG;
+  gram_iso_t p;
+  int rc = f64_tab(work_list, count, p.W);
+  if (!rc) rc = f64_tab(Z_list, count, p.Z);
+  if (rc) return rc;
+  p.off = VLM_ISO_HEAD + (first ? 0 : (size_t)rows * cols);
+  p.c = c;
+  p.first = first;
+  const int nt = (cols + F64_TILE - 1) / F64_TILE;
+  hipLaunchKernelGGL((gram_f64_kernel<double, gram_iso_t>), dim3(nt * (nt + 1) / 2, count, 1), dim3(256), 0, (hipStream_t)stream,
+                     (const double*)nullptr, cols, rows, cols, (double*)nullptr, p);
+  VLM_CHECK_LAUNCH();
+  return VLM_OK;
 }
 
 extern "C" int vlm_gram_f64(const void* x, int ldx, int M, int D, int x_is_f32, double* gram, void* stream) {
@@ -149,9 +203,11 @@ extern "C" int vlm_gram_f64(const void* x, int ldx, int M, int D, int x_is_f32, 
   }
   dim3 grid(pairs, 1, slices);
   if (x_is_f32)
-    hipLaunchKernelGGL((gram_f64_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float*>(x), ldx, M, D, gram);
+    hipLaunchKernelGGL((gram_f64_kernel<float, gram_sum_t>), grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float*>(x), ldx, M, D, gram,
+                       gram_sum_t());
   else
-    hipLaunchKernelGGL((gram_f64_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const bf16_t*>(x), ldx, M, D, gram);
+    hipLaunchKernelGGL((gram_f64_kernel<bf16_t, gram_sum_t>), grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const bf16_t*>(x), ldx, M, D, gram,
+                       gram_sum_t());
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }
@@ -162,18 +218,7 @@ extern "C" int vlm_gram_f64(const void* x, int ldx, int M, int D, int x_is_f32, 
 // Every kernel below the Gram takes its matrices from kernel-argument tables: `count` (<= VLM_F64_MAX_BATCH) problems of ONE shape
 // per launch, blockIdx.z / .y / .x = the problem (the 36 + 12 independent solves of a RegMean merge have two shapes: a chain of
 // ~5 000 dependent 64-wide block launches becomes ~420 launches that fill the chip).  A single matrix is a one-entry table.
-#define VLM_F64_MAX_BATCH 64
-struct f64_tab_t {
-  double* p[VLM_F64_MAX_BATCH];
-};
-static int f64_tab(double* const* list, int count, f64_tab_t& t) {
-  if (!list || count <= 0 || count > VLM_F64_MAX_BATCH) return VLM_ERR_ARG;
-  for (int i = 0; i < count; ++i) {
-    if (!list[i]) return VLM_ERR_ARG;
-    t.p[i] = list[i];
-  }
-  return VLM_OK;
-}
+// (f64_tab.h: f64_tab_t, f64_tab)
 
 // lower: C is a symmetric update (M == N) of which only the tiles on and below the diagonal are computed -- the Cholesky trailing
 // update A22 -= L21 L21^T, whose upper triangle nothing reads (round 5: half the flops and half the C traffic of a K = 64 GEMM

@@ -56,6 +56,17 @@ tests/emr_restatement.py.  Its rule (include/vlm_hip.h), per tensor with central
   6. a[m] = sum f64(|x_m|), b[m] = sum (agree_m ? f64(e) : 0) in the family's pinned order;  rescale[m] = f32(a[m] / b[m])
 emr_restore is the way back: dst = central + rescale * (bit ? unified - central : 0) per expert.  Rescalers are per tensor, not per
 model, and an element with s == 0 contributes nothing: the two departures from the paper's code.
+
+isoc.isoc_merge (Iso-C, isotropic merging; Marczak et al. 2025) lives in isoc.py beside regmean.py, whose float64 leg it runs on: no
+reference site, csrc/isoc.hip and the SYRK of csrc/f64ops.hip held to tests/isoc_restatement.py.  It is the one method here that
+looks at a weight as a matrix.  Its rule (include/vlm_hip.h), per 2-D tensor [m, n] with central tensor c, sources W_0 .. W_{S-1}, lam
+and r = min(m, n), in float64:
+  1. D = ((0 + (W_0 - c)) + (W_1 - c)) + ...      (the sum, not the mean)
+  2. D = U diag(sigma) V^T;  Q = U V^T over the non-zero sigma
+  3. dst = fl32(c + ((lam * sum sigma) / r) * Q);  D = 0: dst = c
+Q is the polar factor of D and sum sigma = <Q, D>: a Cholesky-based QDWH iteration makes them from products, SPD factorisations and
+right-solves, with coefficients that depend on a lower bound chosen up front and not on the data.  Every other tensor takes the
+mean task vector through the task-vector job of this module (ratios lam / S), a layer with one source the ratio-1 job.
 """
 import ctypes
 import math

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus,emr} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus,emr,isoc} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
@@ -32,6 +32,9 @@ the consensus merge with TALL masks (merge.consensus_merge) and EMR-Merging (mer
                                          above are all it reads.  --masks-out M.pt = also write {format: emr-masks-1, masks,
                                          rescalers}: one agreement bit per element and expert and one scalar per tensor and
                                          expert, from which tall_restore.py rebuilds the experts -- merge with --lambda 1 for that)
+  --method isoc      isoc.isoc_merge    (Iso-C: every weight matrix takes the SUM of its task vectors with the singular values
+                                         flattened to their mean, every other tensor the mean task vector; tuning-free: --lambda
+                                         and --central as above are all it reads)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
                      dare: n, keep_below, kept per source, conflict, empty;
                      breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty;
@@ -41,7 +44,8 @@ the consensus merge with TALL masks (merge.consensus_merge) and EMR-Merging (mer
                      slerp: n, row_len, weights, lam and, per tensor, sq, dot per pair, coef64, coef32 and its bits, rho, resid,
                      status -- per row instead: rows, rows_linear, rows_zero, resid_max;
                      consensus: n, op, k, tall_lambda, kept per source, selected, empty;
-                     emr: n, op, kept per source, zero, conflict, abs_sum, uni_sum and rescale per source)
+                     emr: n, op, kept per source, zero, conflict, abs_sum, uni_sum and rescale per source;
+                     isoc, per matrix: n, shape, transposed, S, fro, nuclear, sigma_mean, steps, last_step, converged)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -56,7 +60,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus", "emr")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus", "emr", "isoc")
 
 
 def build_parser():
@@ -177,6 +181,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
     elif method == "emr":
         rows = []
         out = merge.emr_merge(sd, cfg, central_weight=central, report_out=rows, **(emr or {}))
+        if report is not None:
+            report.extend(rows)
+    elif method == "isoc":
+        rows = []
+        out = importlib.import_module("vl_merging_amd.isoc").isoc_merge(sd, cfg, central_weight=central, report_out=rows)
         if report is not None:
             report.extend(rows)
     elif method == "breadcrumbs":

@@ -846,6 +846,88 @@ def solve_spd_right_(rhs, chol):
     return rhs
 
 
+def _iso_work(work, m, n, who):
+    """The working sets of an Iso-C call (include/vlm_hip.h): contiguous float64 [ISO_HEAD + 3 m n] each, at most F64_MAX_BATCH."""
+    if not 1 <= len(work) <= F64_MAX_BATCH or m < 1 or n < 1:
+        raise L.VlmError("%s: 1 .. %d matrices of a positive shape" % (who, F64_MAX_BATCH))
+    for w in work:
+        if w.dtype != F64 or w.dim() != 1 or w.numel() != L.ISO_HEAD + 3 * m * n or not w.is_contiguous():
+            raise L.VlmError("%s: a working set is a contiguous float64 [%d + 3 * %d * %d] tensor" % (who, L.ISO_HEAD, m, n))
+
+
+def _iso_f32(ts, m, n, who):
+    for t in ts:
+        if t.dtype != F32 or tuple(t.shape) != (m, n) or not t.is_contiguous() or (t.data_ptr() & 15):
+            raise L.VlmError("%s: contiguous, 16-byte aligned float32 [%d, %d] tensors" % (who, m, n))
+
+
+def iso_partials(m, n, count, device):
+    """The scratch the Iso-C sums of `count` [m, n] matrices go through."""
+    return torch.empty(count * L.get_lib().vlm_iso_parts(m, n), dtype=F64, device=device)
+
+
+def _iso_scratch(partials, m, n, count, who):
+    if partials.dtype != F64 or not partials.is_contiguous() or partials.numel() < count * L.get_lib().vlm_iso_parts(m, n):
+        raise L.VlmError(who + ": partials too small (iso_partials)")
+
+
+def iso_delta(base, srcs, work, partials):
+    """Iso-C step 1 for matrices of ONE shape [m, n] (vlm_iso_delta): work[b] receives D = sum_k (srcs[k][b] - base[b]) in float64,
+    transposed when m < n, a copy of it as Y, and ||D||_F^2 in its head.  srcs: S lists of len(base) tensors."""
+    m, n = base[0].shape
+    L.require_cuda(partials, *base, *work, *[t for s in srcs for t in s])
+    _iso_work(work, m, n, "iso_delta")
+    if not 1 <= len(srcs) <= L.MERGE_MAX_SRC or any(len(s) != len(base) for s in srcs) or len(work) != len(base):
+        raise L.VlmError("iso_delta: 1 .. %d source lists as long as the list of central tensors" % L.MERGE_MAX_SRC)
+    _iso_f32(list(base) + [t for s in srcs for t in s], m, n, "iso_delta")
+    _iso_scratch(partials, m, n, len(base), "iso_delta")
+    L.check(L.get_lib().vlm_iso_delta(_ptr_list(base), _ptr_list([t for s in srcs for t in s]), len(srcs), m, n, _ptr_list(work),
+                                      L.ptr(partials), len(base), L.stream_ptr()), "vlm_iso_delta")
+    return work
+
+
+def iso_gram(work, rows, cols, zs, c, first):
+    """zs[b] [cols, cols] = I + f X_b^T X_b on v_mfma_f64, upper-triangular tiles only (vlm_iso_gram): the operand is the working
+    set's X and f = c, or (first) its D and f = c / ||D||_F^2 from its head."""
+    L.require_cuda(*work, *zs)
+    _iso_work(work, rows, cols, "iso_gram")
+    if rows < cols or len(zs) != len(work) or _f64_squares(zs, "iso_gram") != cols:
+        raise L.VlmError("iso_gram: rows >= cols and one [cols, cols] result per working set")
+    L.check(L.get_lib().vlm_iso_gram(_ptr_list(work), rows, cols, int(bool(first)), float(c), _ptr_list(zs), len(work), L.stream_ptr()),
+            "vlm_iso_gram")
+    return zs
+
+
+def iso_step(work, rows, cols, p, q, k, first, partials):
+    """X <- p X + q Y, Y <- X and ||X_new - X||_F^2 into head[2 + k] for every working set (vlm_iso_step)."""
+    L.require_cuda(partials, *work)
+    _iso_work(work, rows, cols, "iso_step")
+    if not 0 <= k < L.ISO_MAX_STEPS:
+        raise L.VlmError("iso_step: step %d of at most %d" % (k, L.ISO_MAX_STEPS))
+    _iso_scratch(partials, rows, cols, len(work), "iso_step")
+    L.check(L.get_lib().vlm_iso_step(_ptr_list(work), rows, cols, int(bool(first)), float(p), float(q), k, L.ptr(partials), len(work),
+                                     L.stream_ptr()), "vlm_iso_step")
+    return work
+
+
+def iso_finish(work, base, dst, lam, partials, phases=L.ISO_PHASE_NUCLEAR | L.ISO_PHASE_APPLY):
+    """The phases of vlm_iso_finish for matrices of ONE shape [m, n]: ISO_PHASE_NUCLEAR puts <X, D> into head[1]; ISO_PHASE_APPLY
+    writes dst[b] = fl32(base[b] + ((lam * head[1]) / min(m, n)) * X).  dst[b] may be base[b] or a source -- then apply ONCE: the
+    phase reads base[b]."""
+    if phases not in (L.ISO_PHASE_NUCLEAR, L.ISO_PHASE_APPLY, L.ISO_PHASE_NUCLEAR | L.ISO_PHASE_APPLY):
+        raise L.VlmError("iso_finish: phases is ISO_PHASE_NUCLEAR, ISO_PHASE_APPLY or both, got %r" % (phases,))
+    m, n = base[0].shape
+    L.require_cuda(partials, *work, *base, *dst)
+    _iso_work(work, m, n, "iso_finish")
+    if len(base) != len(work) or len(dst) != len(work):
+        raise L.VlmError("iso_finish: one central tensor and one output per working set")
+    _iso_f32(list(base) + list(dst), m, n, "iso_finish")
+    _iso_scratch(partials, m, n, len(work), "iso_finish")
+    L.check(L.get_lib().vlm_iso_finish(_ptr_list(work), _ptr_list(base), _ptr_list(dst), m, n, float(lam), L.ptr(partials), len(work),
+                                       phases, L.stream_ptr()), "vlm_iso_finish")
+    return dst
+
+
 def patch_im2col(image, patches, patch, lead_rows):
     L.require_cuda(image, patches)
     B, C, H, W = image.shape

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from ... import _lib as L
 from ... import engine
+from ... import isoc as isoc_ops
 from ... import merge as merge_ops
 from ... import ops
 from ... import regmean as regmean_ops
@@ -295,6 +296,12 @@ class ViLTransformerSS(nn.Module):
         """EMR-Merging (elect, mask, rescale) of the experts' task vectors (no reference site; merge.emr_merge).  Same contract as
         sum_task_vectors; not wired to a config key and not called from __init__."""
         return merge_ops.emr_merge(state_dict, self.hparams.config, lam=lam, masks_out=masks_out, rescalers_out=rescalers_out,
+                                   device=self._merge_device())
+
+    def isoc_merge(self, state_dict, lam=None, report_out=None, factors_out=None):
+        """Iso-C (isotropic) merge of the experts' task vectors (no reference site; isoc.isoc_merge).  Same contract as
+        sum_task_vectors; not wired to a config key and not called from __init__."""
+        return isoc_ops.isoc_merge(state_dict, self.hparams.config, lam=lam, report_out=report_out, factors_out=factors_out,
                                    device=self._merge_device())
 
     def band_merge(self, state_dict, density=0.9, gamma=0.01, mode="linear", lam=None):

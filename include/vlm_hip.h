@@ -1287,6 +1287,51 @@ int vlm_iso_finish(double* const* work_list, const float* const* c_list, float* 
                    double* partials, int count, int phases, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * WUDI-Merging (Cheng et al., ICML 2025, "Whoever Started the Interference Should End It: Guiding Data-Free Model Merging via
+ * Task Vectors") of a weight MATRIX, csrc/wudi.hip + the products of csrc/f64ops.hip.  No reference site.  Per linear layer the
+ * method minimises  L(X) = sum_i (1 / ||tau_i||_F^2) ||(X - tau_i) tau_i^T||_F^2  over the merged task vector X by Adam, starting
+ * from the sum of the task vectors.  The rule, per destination matrix [m, n] (m = out, n = in, as stored) with central tensor c,
+ * sources W_0 .. W_{S-1} (1 <= S <= VLM_MERGE_MAX_SRC), lam, iters = T >= 1, lr, beta1, beta2, eps; fp32 values are widened
+ * exactly, everything elementwise is one correctly rounded fp64 operation each, no FMA outside the matrix products, whose sums
+ * may run in any order:
+ *   1. tau_i = W_i - c;  n_i = sum tau_i^2 in a fixed order;  w_i = 1 / n_i, 0 where n_i = 0
+ *   2. G = sum_i w_i tau_i^T tau_i [n, n];  B = sum_i tau_i (w_i tau_i^T tau_i) [m, n];  K = sum_i n_i ||w_i tau_i^T tau_i||_F^2
+ *      (= sum_i w_i <tau_i (tau_i^T tau_i), tau_i>), the sums over i in source order from 0
+ *   3. X_0 = ((0 + tau_0) + tau_1) + ...;  M = V = 0
+ *   4. for t = 1 .. T, in the operation order of torch.optim.Adam:
+ *        g = 2 (X_{t-1} G - B);  loss_{t-1} = <X_{t-1}, X_{t-1} G - 2 B> + K  (= L(X_{t-1}))
+ *        M = beta1 M + (1 - beta1) g;  V = beta2 V + ((1 - beta2) g) g
+ *        X_t = X_{t-1} - step_t * (M / (sqrt(V) / bc2s_t + eps))   with step_t = lr / (1 - beta1^t), bc2s_t = sqrt(1 - beta2^t)
+ *   5. dst = fl32(c + lam * X_T): product, sum, ONE rounding to fp32
+ * The gradient of L is 2 (X G - B): the RegMean normal equation with w_i tau_i^T tau_i in place of a data Gram.  step_t and bc2s_t
+ * are functions of t alone: the caller makes them as host doubles, nothing between the first launch and the last synchronises.
+ *
+ * The working set of one matrix is ONE device allocation of vlm_wudi_work_doubles(m, n) = VLM_WUDI_HEAD + 2 n n + 5 m n doubles:
+ * the head, G, a setup scratch [n][n], then B, X (buffer 0), X (buffer 1), M and V, each [m][n] row-major.  A step READS X_{t-1}
+ * from buffer (t - 1) & 1 and WRITES X_t to buffer t & 1 (every workgroup of a tile row reads the row's whole panel of X_{t-1}
+ * while its neighbours store: in place would be a race); X_T starts at vlm_wudi_state_offset(m, n, T).  head[0 .. 3] = n_i,
+ * head[4 .. 7] = ||w_i tau_i^T tau_i||_F^2, head[8] = K, head[9] = loss_0 = L(X_0), head[10] = loss_{T-1} = L(X_{T-1}).
+ * Every call takes `count` (<= 64) matrices of ONE shape [m, n] in lock step; the lists are HOST arrays of device pointers.
+ * `partials`: device scratch of count * vlm_wudi_parts(m, n) doubles that lives from prepare to finish (it carries the per-tile
+ * loss shares of step 1 and of the latest later step), matrix b of a call owning doubles [b, b + 1) * vlm_wudi_parts(m, n) of it:
+ * a step may run matrices that several prepare calls set up (different S) in ONE launch when their slices lie side by side, and
+ * finish may again be called per slice (different lam).  Every sum is made in a fixed order without atomics (the same bits every
+ * run).  c, the sources and dst are contiguous and 16-byte aligned; dst may be c or a source.
+ *   vlm_wudi_prepare  steps 1 - 3 from c_list[count] and src_list[S][count] (tau_i passes through V, M and V end zero)
+ *   vlm_wudi_step     step 4 for ONE t >= 1: one launch, the product X G on 64 x 64 MFMA-f64 tiles with the update in its epilogue
+ *   vlm_wudi_finish   head[8 .. 10] and step 5 after `iters` steps */
+#define VLM_WUDI_HEAD 16
+int vlm_wudi_parts(int m, int n);
+size_t vlm_wudi_work_doubles(int m, int n);
+size_t vlm_wudi_state_offset(int m, int n, int iters);
+int vlm_wudi_prepare(const float* const* c_list, const float* const* src_list, int S, int m, int n, double* const* work_list,
+                     double* partials, int count, void* stream);
+int vlm_wudi_step(double* const* work_list, int m, int n, int t, double step, double bc2s, double beta1, double beta2, double eps,
+                  double* partials, int count, void* stream);
+int vlm_wudi_finish(double* const* work_list, const float* const* c_list, float* const* dst_list, int S, int m, int n, int iters,
+                    double lam, double* partials, int count, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused attention (K4 + K7 + K7b): softmax(scale*Q K^T + bias[h] + key mask) V, head_dim = 64.
  * Replaces Attention.forward's core, modules/vision_transformer.py:346-358, the bias materialisation
  * get_rel_pos_bias modules/vilt_module.py:1061-1064 (never formed here), and the text/image block-diagonal

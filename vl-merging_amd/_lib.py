@@ -144,6 +144,7 @@ DELLA_MAX_ROW = 4096                # VLM_DELLA_MAX_ROW: the longest row whose r
 ISO_HEAD = 64                       # VLM_ISO_HEAD: doubles in front of an Iso-C working set (norms, step norms)
 ISO_MAX_STEPS = 40                  # VLM_ISO_MAX_STEPS
 ISO_PHASE_NUCLEAR, ISO_PHASE_APPLY = 1, 2  # VLM_ISO_PHASE_*: the phases of vlm_iso_finish, a bit mask
+WUDI_HEAD = 16                      # VLM_WUDI_HEAD: doubles in front of a WUDI working set (n_i, ||G_i||^2, K, the two losses)
 
 
 class DellaJob(ctypes.Structure):
@@ -493,6 +494,15 @@ SIGNATURES = {
                              c_void_p]),
     "vlm_iso_finish": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int,
                                ctypes.c_double, c_void_p, c_int, c_int, c_void_p]),
+    "vlm_wudi_parts": (c_int, [c_int, c_int]),
+    "vlm_wudi_work_doubles": (ctypes.c_size_t, [c_int, c_int]),
+    "vlm_wudi_state_offset": (ctypes.c_size_t, [c_int, c_int, c_int]),
+    "vlm_wudi_prepare": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.POINTER(c_void_p),
+                                 c_void_p, c_int, c_void_p]),
+    "vlm_wudi_step": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                              ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p]),
+    "vlm_wudi_finish": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int,
+                                ctypes.c_double, c_void_p, c_int, c_void_p]),
     "vlm_cross_entropy_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     "vlm_cross_entropy_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p]),

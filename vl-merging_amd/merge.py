@@ -67,6 +67,14 @@ and r = min(m, n), in float64:
 Q is the polar factor of D and sum sigma = <Q, D>: a Cholesky-based QDWH iteration makes them from products, SPD factorisations and
 right-solves, with coefficients that depend on a lower bound chosen up front and not on the data.  Every other tensor takes the
 mean task vector through the task-vector job of this module (ratios lam / S), a layer with one source the ratio-1 job.
+
+wudi.wudi_merge (WUDI-Merging; Cheng et al. 2025) lives in wudi.py: the second matrix-aware method and the one ITERATED one, no
+reference site, csrc/wudi.hip and the products of csrc/f64ops.hip held to tests/wudi_restatement.py.  Its rule (include/vlm_hip.h),
+per 2-D tensor [m, n] with central tensor c, sources W_0 .. W_{S-1} and lam, in float64 with tau_i = W_i - c:
+  1. n_i = ||tau_i||_F^2;  G = sum_i tau_i^T tau_i / n_i;  B = sum_i tau_i (tau_i^T tau_i) / n_i
+  2. X_0 = sum_i tau_i;  `iters` steps of Adam (lr, 0.9, 0.999, 1e-8) with the gradient 2 (X G - B)
+  3. dst = fl32(c + lam * X_iters)
+Every other tensor and a layer with one source are treated as for Iso-C.
 """
 import ctypes
 import math

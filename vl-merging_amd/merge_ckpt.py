@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus,emr,isoc} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus,emr,isoc,wudi} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
@@ -35,6 +35,10 @@ the consensus merge with TALL masks (merge.consensus_merge) and EMR-Merging (mer
   --method isoc      isoc.isoc_merge    (Iso-C: every weight matrix takes the SUM of its task vectors with the singular values
                                          flattened to their mean, every other tensor the mean task vector; tuning-free: --lambda
                                          and --central as above are all it reads)
+  --method wudi      wudi.wudi_merge    (WUDI-Merging: every weight matrix takes --wudi-iters Adam steps at --wudi-lr, in float64,
+                                         on sum_i ||(X - tau_i) tau_i^T||_F^2 / ||tau_i||_F^2 from the sum of its task vectors
+                                         tau_i -- data-free: the task vectors' own Gram matrices stand in for RegMean's --, every
+                                         other tensor the mean task vector; --lambda and --central as above)
   --report R.json    one entry per merged tensor (ties: n, K, threshold, kept per source, conflict, empty;
                      dare: n, keep_below, kept per source, conflict, empty;
                      breadcrumbs: n, k_hi, k_lo, both thresholds, kept and outlier per source, conflict, empty;
@@ -45,7 +49,8 @@ the consensus merge with TALL masks (merge.consensus_merge) and EMR-Merging (mer
                      status -- per row instead: rows, rows_linear, rows_zero, resid_max;
                      consensus: n, op, k, tall_lambda, kept per source, selected, empty;
                      emr: n, op, kept per source, zero, conflict, abs_sum, uni_sum and rescale per source;
-                     isoc, per matrix: n, shape, transposed, S, fro, nuclear, sigma_mean, steps, last_step, converged)
+                     isoc, per matrix: n, shape, transposed, S, fro, nuclear, sigma_mean, steps, last_step, converged;
+                     wudi, per matrix: n, shape, S, iters, lr, sq per source, loss_first, loss_last)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
 """
@@ -60,7 +65,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus", "emr", "isoc")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus", "emr", "isoc", "wudi")
 
 
 def build_parser():
@@ -97,6 +102,8 @@ def build_parser():
     p.add_argument("--consensus-k", dest="consensus_k", type=int, default=2,
                    help="consensus: keep an element iff at least k experts find it relevant (a layer with S experts uses min(k, S)); "
                         "0 is plain task arithmetic")
+    p.add_argument("--wudi-iters", dest="wudi_iters", type=int, default=300, help="wudi: Adam steps per weight matrix, >= 1")
+    p.add_argument("--wudi-lr", dest="wudi_lr", type=float, default=1e-5, help="wudi: Adam's learning rate, > 0")
     p.add_argument("--masks-out", dest="masks_out", default=None,
                    help="consensus: write {format: tall-masks-1, tall_lambda, k, masks: {source key: int32 words}} here; "
                         "emr: write {format: emr-masks-1, masks: {source key: int32 words}, rescalers: {source key: float}} here")
@@ -129,6 +136,11 @@ def parse_args(argv):
         importlib.import_module("vl_merging_amd.merge").della_window(args.density, args.epsilon)  # the one statement; ValueError
         if not 0 <= args.seed < 2 ** 64:
             raise ValueError("DELLA seed must fit 64 bits, got %r" % (args.seed,))
+    if args.method == "wudi":
+        if args.wudi_iters < 1:
+            raise ValueError("WUDI takes --wudi-iters >= 1, got %r" % (args.wudi_iters,))
+        if not (args.wudi_lr > 0.0 and args.wudi_lr < float("inf")):
+            raise ValueError("WUDI takes a finite --wudi-lr > 0, got %r" % (args.wudi_lr,))
     if args.method == "consensus":
         merge = importlib.import_module("vl_merging_amd.merge")
         merge.tall_threshold(args.tall_lambda)  # the one statement of each rule; ValueError
@@ -139,10 +151,10 @@ def parse_args(argv):
 
 
 def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=None, band=None, della=None, sphere=None,
-                consensus=None, emr=None):
+                consensus=None, emr=None, wudi=None):
     """The merged state_dict (device tensors for merged keys, the input's objects for the rest).  `dare`: the keyword arguments of
     merge.dare_merge (drop, seed, mode, rescale); `band`: those of merge.band_merge beside the density (gamma, mode); `della`: those of
-    merge.della_merge beside the density (epsilon, seed, mode, rescale); `sphere`: those of merge.sphere_merge (on, rows); `consensus`: those of merge.consensus_merge (tall_lambda, k, masks_out); `emr`: those of merge.emr_merge (masks_out, rescalers_out)."""
+    merge.della_merge beside the density (epsilon, seed, mode, rescale); `sphere`: those of merge.sphere_merge (on, rows); `consensus`: those of merge.consensus_merge (tall_lambda, k, masks_out); `emr`: those of merge.emr_merge (masks_out, rescalers_out); `wudi`: those of wudi.wudi_merge (iters, lr)."""
     merge = importlib.import_module("vl_merging_amd.merge")
     if method == "interp":
         out = merge.merge_weights(sd, cfg)
@@ -188,6 +200,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
         out = importlib.import_module("vl_merging_amd.isoc").isoc_merge(sd, cfg, central_weight=central, report_out=rows)
         if report is not None:
             report.extend(rows)
+    elif method == "wudi":
+        rows = []
+        out = importlib.import_module("vl_merging_amd.wudi").wudi_merge(sd, cfg, central_weight=central, report_out=rows, **(wudi or {}))
+        if report is not None:
+            report.extend(rows)
     elif method == "breadcrumbs":
         rows = []
         out = merge.band_merge(sd, cfg, central_weight=central, density=density, report_out=rows, **(band or {}))
@@ -226,7 +243,8 @@ def main(argv):
                       della=dict(epsilon=args.epsilon, seed=args.seed, mode=args.della_mode, rescale=args.rescale),
                       sphere=dict(on=args.sphere_on, rows=args.sphere_rows),
                       consensus=dict(tall_lambda=args.tall_lambda, k=args.consensus_k, masks_out=masks),
-                      emr=dict(masks_out=masks, rescalers_out=rescalers))
+                      emr=dict(masks_out=masks, rescalers_out=rescalers),
+                      wudi=dict(iters=args.wudi_iters, lr=args.wudi_lr))
     torch.cuda.synchronize()
     torch.save({"state_dict": {k: v.detach().to("cpu") for k, v in out.items()}}, args.out)
     if rescalers is not None:

@@ -928,6 +928,73 @@ def iso_finish(work, base, dst, lam, partials, phases=L.ISO_PHASE_NUCLEAR | L.IS
     return dst
 
 
+def wudi_work_doubles(m, n):
+    """Doubles in the working set of one [m, n] matrix of a WUDI merge (include/vlm_hip.h: WUDI_HEAD + 2 n n + 5 m n)."""
+    return L.get_lib().vlm_wudi_work_doubles(m, n)
+
+
+def wudi_partials(m, n, count, device):
+    """The scratch of `count` [m, n] matrices of a WUDI merge; it lives from wudi_prepare to wudi_finish (the loss shares)."""
+    return torch.empty(count * L.get_lib().vlm_wudi_parts(m, n), dtype=F64, device=device)
+
+
+def wudi_state(work, m, n, iters):
+    """X after `iters` steps, a [m, n] view of the working set (the buffer the last step wrote)."""
+    o = L.get_lib().vlm_wudi_state_offset(m, n, iters)
+    return work[o: o + m * n].view(m, n)
+
+
+def _wudi_work(work, m, n, partials, who):
+    if not 1 <= len(work) <= F64_MAX_BATCH or m < 1 or n < 1:
+        raise L.VlmError("%s: 1 .. %d matrices of a positive shape" % (who, F64_MAX_BATCH))
+    size = wudi_work_doubles(m, n)
+    for w in work:
+        if w.dtype != F64 or w.dim() != 1 or w.numel() != size or not w.is_contiguous():
+            raise L.VlmError("%s: a working set is a contiguous float64 [%d] tensor for a [%d, %d] matrix" % (who, size, m, n))
+    if partials.dtype != F64 or not partials.is_contiguous() or partials.numel() < len(work) * L.get_lib().vlm_wudi_parts(m, n):
+        raise L.VlmError(who + ": partials too small (wudi_partials)")
+
+
+def wudi_prepare(base, srcs, work, partials):
+    """WUDI steps 1 - 3 for matrices of ONE shape [m, n] (vlm_wudi_prepare): every working set receives n_i, G, B and X_0 of its
+    matrix, its M and V zero.  srcs: S lists of len(base) tensors."""
+    m, n = base[0].shape
+    L.require_cuda(partials, *base, *work, *[t for s in srcs for t in s])
+    _wudi_work(work, m, n, partials, "wudi_prepare")
+    if not 1 <= len(srcs) <= L.MERGE_MAX_SRC or any(len(s) != len(base) for s in srcs) or len(work) != len(base):
+        raise L.VlmError("wudi_prepare: 1 .. %d source lists as long as the list of central tensors" % L.MERGE_MAX_SRC)
+    _iso_f32(list(base) + [t for s in srcs for t in s], m, n, "wudi_prepare")
+    L.check(L.get_lib().vlm_wudi_prepare(_ptr_list(base), _ptr_list([t for s in srcs for t in s]), len(srcs), m, n, _ptr_list(work),
+                                         L.ptr(partials), len(base), L.stream_ptr()), "vlm_wudi_prepare")
+    return work
+
+
+def wudi_step(work, m, n, t, step, bc2s, partials, beta1=0.9, beta2=0.999, eps=1e-8):
+    """Adam step t >= 1 of every working set (vlm_wudi_step): ONE launch, X_{t-1} G on the MFMA-f64 tiles with the update in the
+    epilogue, X_t into the other buffer.  step = lr / (1 - beta1^t) and bc2s = sqrt(1 - beta2^t) are the caller's doubles."""
+    L.require_cuda(partials, *work)
+    _wudi_work(work, m, n, partials, "wudi_step")
+    if t < 1 or not step > 0.0 or not bc2s > 0.0 or not eps > 0.0 or not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+        raise L.VlmError("wudi_step: t >= 1, step, bc2s, eps > 0 and betas in [0, 1), got %r" % ((t, step, bc2s, eps, beta1, beta2),))
+    L.check(L.get_lib().vlm_wudi_step(_ptr_list(work), m, n, t, float(step), float(bc2s), float(beta1), float(beta2), float(eps),
+                                      L.ptr(partials), len(work), L.stream_ptr()), "vlm_wudi_step")
+    return work
+
+
+def wudi_finish(work, base, dst, S, iters, lam, partials):
+    """K and the two losses into the heads, dst[b] = fl32(base[b] + lam * X_iters) (vlm_wudi_finish).  dst[b] may be base[b] or a
+    source."""
+    m, n = base[0].shape
+    L.require_cuda(partials, *work, *base, *dst)
+    _wudi_work(work, m, n, partials, "wudi_finish")
+    if len(base) != len(work) or len(dst) != len(work) or not 1 <= S <= L.MERGE_MAX_SRC or iters < 1:
+        raise L.VlmError("wudi_finish: one central tensor and one output per working set, 1 .. %d sources, iters >= 1" % L.MERGE_MAX_SRC)
+    _iso_f32(list(base) + list(dst), m, n, "wudi_finish")
+    L.check(L.get_lib().vlm_wudi_finish(_ptr_list(work), _ptr_list(base), _ptr_list(dst), S, m, n, iters, float(lam), L.ptr(partials),
+                                        len(work), L.stream_ptr()), "vlm_wudi_finish")
+    return dst
+
+
 def patch_im2col(image, patches, patch, lead_rows):
     L.require_cuda(image, patches)
     B, C, H, W = image.shape

@@ -20,6 +20,7 @@ from ... import isoc as isoc_ops
 from ... import merge as merge_ops
 from ... import ops
 from ... import regmean as regmean_ops
+from ... import wudi as wudi_ops
 from . import heads, objectives, vilt_utils
 from . import vision_transformer as vit
 
@@ -303,6 +304,12 @@ class ViLTransformerSS(nn.Module):
         sum_task_vectors; not wired to a config key and not called from __init__."""
         return isoc_ops.isoc_merge(state_dict, self.hparams.config, lam=lam, report_out=report_out, factors_out=factors_out,
                                    device=self._merge_device())
+
+    def wudi_merge(self, state_dict, lam=None, report_out=None, states_out=None, iters=300, lr=1e-5):
+        """WUDI merge of the experts' task vectors (no reference site; wudi.wudi_merge).  Same contract as sum_task_vectors; not
+        wired to a config key and not called from __init__."""
+        return wudi_ops.wudi_merge(state_dict, self.hparams.config, lam=lam, report_out=report_out, states_out=states_out,
+                                   iters=iters, lr=lr, device=self._merge_device())
 
     def band_merge(self, state_dict, density=0.9, gamma=0.01, mode="linear", lam=None):
         """Model Breadcrumbs merge of the experts' task vectors (no reference site; merge.band_merge).  Same contract as

@@ -1332,6 +1332,65 @@ int vlm_wudi_finish(double* const* work_list, const float* const* c_list, float*
                     double lam, double* partials, int count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Batched float64 SVD by one-sided (Hestenes) Jacobi, csrc/jacobi.hip.  No reference site.  A matrix is worked on as [p <= q]: p rows
+ * of length q, row-major (a tall matrix as its transpose: the caller stages it).  The working set of one matrix is ONE device
+ * allocation of vlm_svd_work_doubles(p, q) = VLM_SVD_HEAD + p q + p p + 2 p doubles: the head, A [p][q], R [p][p], s [p], then
+ * rank [p] and order [p] as int32.  A starts as the matrix and R as I (vlm_svd_reset, which also zeroes the head); both take the same
+ * row rotations, so A ends as diag(s) V^T and R as U^T with  matrix = R^T A.
+ *   A SWEEP is the round-robin tournament over the p rows (csrc/jacobi_schedule.h; a bye when p is odd): vlm_svd_steps(p) = p - 1
+ *   (p even) or p (p odd) steps of floor(p / 2) disjoint pairs.  Every step is ONE launch over `count` (<= 64) matrices of one
+ *   working shape, one workgroup per pair and matrix.  Per pair (i, j), every operation one correctly rounded fp64 operation:
+ *     alpha = |a_i|^2, beta = |a_j|^2, gamma = a_i . a_j, summed in a fixed lane-then-wave order (the same bits every run);
+ *     rotate iff |gamma| > sqrt(q) 2^-53 sqrt(alpha beta):
+ *       zeta = (beta - alpha) / (2 gamma);  t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2))  (sign(0) = 1);  c = 1 / sqrt(1 + t^2);  s = c t;
+ *       a_i <- c a_i - s a_j,  a_j <- s a_i + c a_j,  and the same for rows i, j of R.
+ *   head[2 + k] = the rotations of sweep k, head[32 + k] = the largest |gamma| / sqrt(alpha beta) sweep k met (k < VLM_SVD_MAX_SWEEPS):
+ *   a count and a maximum, one vector atomic each per workgroup, independent of the order.  A matrix whose sweep k - 1 rotated
+ *   nothing is finished: sweep k leaves it untouched (its workgroups return at once), so sweeps must be issued in order from 0
+ *   on a reset head, and a caller may enqueue more sweeps than a matrix needs and read the heads once.  Nothing here synchronises.
+ *   q > 8192 (a row no longer fits a workgroup's registers) is VLM_ERR_UNSUPPORTED.
+ *   vlm_svd_reset   R = I, head = 0
+ *   vlm_svd_sweep   all steps of sweep `sweep`
+ *   vlm_svd_finish  s_j = |a_j| (fixed order);  rank[j] = the rows in front of row j by (s descending, index ascending) and
+ *                   order[rank[j]] = j;  head[0] = s_max;  A's rows become the unit rows v_j = a_j / s_j -- a ZERO row where s_j = 0 or
+ *                   s_j <= floor_rel * s_max (0 <= floor_rel < 1);  head[1] = the number of rows zeroed.
+ *
+ * TSV-M (Gargiulo et al., CVPR 2025, "Task Singular Vectors: Reducing Task Interference in Model Merging") of a weight MATRIX,
+ * csrc/tsvm.hip + the SVD above + vlm_gemm_f64_batched.  No reference site.  The rule, per destination matrix [m, n] with central
+ * tensor c, sources W_0 .. W_{S-1} (2 <= S <= VLM_MERGE_MAX_SRC), lam, r = min(m, n) and k = floor(r / S); fp32 values are widened
+ * exactly, everything runs in float64:
+ *   1. tau_i = W_i - c = U_i diag(s_i) V_i^T, the thin SVD, singular values in descending order
+ *   2. expert i's first k triplets go to columns [i k, (i + 1) k) of Ucat [m, kS], scat [kS] and Vcat [n, kS]; a triplet with s = 0
+ *      exactly contributes a ZERO column to Ucat and Vcat (an expert equal to c adds nothing; no arbitrary basis is injected)
+ *   3. Uo = polar(Ucat), Vo = polar(Vcat) with polar(B) = sum over sigma_j > 2^-40 sigma_max of p_j q_j^T from B = P diag(sigma) Q^T
+ *      (the paper's u v^T of svd(Ucat); directions the experts share exactly are dropped, and counted, not completed arbitrarily)
+ *   4. dst = fl32(c + lam * (Uo diag(scat) Vo^T)): product, sum, ONE rounding to fp32
+ *   5. k = 0 (r < S): the merged task vector is zero and dst = c bit for bit
+ * The rule is symmetric under transposition, so everything runs in the working orientation [p <= q] of tau_i (tau_i^T when m > n).
+ * polar(B^T) = polar(B)^T, and from the row-Jacobi of B^T [kS, len] it is R^T times the unit rows with floor_rel = 2^-40.
+ *   vlm_tsv_delta   A of work_list[b] = src_list[b] - c_list[b] in working orientation (follow with vlm_svd_reset)
+ *   vlm_tsv_gather  after vlm_svd_finish of S x count first SVDs (src_work_list[S][count], working shape [p, q]): row i k + r of the
+ *                   destination's A [kS][len] = expert i's row order[r] of R (side 0, len = p) or of the unit rows (side 1, len = q),
+ *                   a zero row where that s is exactly 0; side 1 also writes scat_list[b][i k + r] = that s (follow with vlm_svd_reset)
+ *   vlm_tsv_apply   step 4 (and 5 at kS = 0): T = PU^T diag(scat) PV on 64 x 64 MFMA-f64 tiles from the TRANSPOSED polar factors
+ *                   pu_list[b] [kS][p] and pv_list[b] [kS][q], stored to t_list[b] [p][q]; dst in the tensor's own orientation in the
+ *                   epilogue.  c, the sources and dst are contiguous and 16-byte aligned; dst may be c or a source. */
+#define VLM_SVD_HEAD 64
+#define VLM_SVD_MAX_SWEEPS 30
+size_t vlm_svd_work_doubles(int p, int q);
+int vlm_svd_steps(int p);
+int vlm_svd_reset(double* const* work_list, int p, int q, int count, void* stream);
+int vlm_svd_sweep(double* const* work_list, int p, int q, int sweep, int count, void* stream);
+int vlm_svd_finish(double* const* work_list, int p, int q, double floor_rel, int count, void* stream);
+int vlm_tsv_delta(const float* const* c_list, const float* const* src_list, int m, int n, double* const* work_list, int count,
+                  void* stream);
+int vlm_tsv_gather(const double* const* src_work_list, int S, int p, int q, int k, int side, double* const* dst_work_list,
+                   double* const* scat_list, int count, void* stream);
+int vlm_tsv_apply(const double* const* pu_list, const double* const* pv_list, const double* const* scat_list,
+                  const float* const* c_list, float* const* dst_list, double* const* t_list, int m, int n, int kS, double lam, int count,
+                  void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused attention (K4 + K7 + K7b): softmax(scale*Q K^T + bias[h] + key mask) V, head_dim = 64.
  * Replaces Attention.forward's core, modules/vision_transformer.py:346-358, the bias materialisation
  * get_rel_pos_bias modules/vilt_module.py:1061-1064 (never formed here), and the text/image block-diagonal

@@ -145,6 +145,9 @@ ISO_HEAD = 64                       # VLM_ISO_HEAD: doubles in front of an Iso-C
 ISO_MAX_STEPS = 40                  # VLM_ISO_MAX_STEPS
 ISO_PHASE_NUCLEAR, ISO_PHASE_APPLY = 1, 2  # VLM_ISO_PHASE_*: the phases of vlm_iso_finish, a bit mask
 WUDI_HEAD = 16                      # VLM_WUDI_HEAD: doubles in front of a WUDI working set (n_i, ||G_i||^2, K, the two losses)
+SVD_HEAD = 64                       # VLM_SVD_HEAD: doubles in front of a Jacobi SVD working set
+SVD_MAX_SWEEPS = 30                 # VLM_SVD_MAX_SWEEPS: head[2 + k] rotations, head[32 + k] largest off-diagonal ratio of sweep k
+SVD_MAX_Q = 8192                    # the longest row a Jacobi workgroup holds in registers
 
 
 class DellaJob(ctypes.Structure):
@@ -503,6 +506,16 @@ SIGNATURES = {
                               ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p]),
     "vlm_wudi_finish": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int,
                                 ctypes.c_double, c_void_p, c_int, c_void_p]),
+    "vlm_svd_work_doubles": (ctypes.c_size_t, [c_int, c_int]),
+    "vlm_svd_steps": (c_int, [c_int]),
+    "vlm_svd_reset": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_void_p]),
+    "vlm_svd_sweep": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p]),
+    "vlm_svd_finish": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, ctypes.c_double, c_int, c_void_p]),
+    "vlm_tsv_delta": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, ctypes.POINTER(c_void_p), c_int, c_void_p]),
+    "vlm_tsv_gather": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p),
+                               ctypes.POINTER(c_void_p), c_int, c_void_p]),
+    "vlm_tsv_apply": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                              ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p]),
     "vlm_cross_entropy_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     "vlm_cross_entropy_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p]),

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus,emr,isoc,wudi} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
+"""`python merge_ckpt.py --method {interp,taskvec,ties,dare,breadcrumbs,della,stock,sce,slerp,karcher,consensus,emr,isoc,tsvm,wudi} --ckpt IN --out OUT [...] with <named configs> key=value ...`:
 merge the modality experts of an all_moe checkpoint on the GPU and write the merged (ufo) checkpoint to disk.
 
 The reference merges only while a model loads (src/vilt/modules/vilt_module.py:284-305 calls merge_weights /
@@ -35,6 +35,10 @@ the consensus merge with TALL masks (merge.consensus_merge) and EMR-Merging (mer
   --method isoc      isoc.isoc_merge    (Iso-C: every weight matrix takes the SUM of its task vectors with the singular values
                                          flattened to their mean, every other tensor the mean task vector; tuning-free: --lambda
                                          and --central as above are all it reads)
+  --method tsvm      tsvm.tsvm_merge    (TSV-M: every weight matrix keeps each expert's leading min(m, n) // S singular triplets and
+                                         orthogonalises the kept subspaces across the experts before recombining them, through a
+                                         float64 Jacobi SVD; every other tensor the mean task vector; tuning-free: --lambda and
+                                         --central as above are all it reads)
   --method wudi      wudi.wudi_merge    (WUDI-Merging: every weight matrix takes --wudi-iters Adam steps at --wudi-lr, in float64,
                                          on sum_i ||(X - tau_i) tau_i^T||_F^2 / ||tau_i||_F^2 from the sum of its task vectors
                                          tau_i -- data-free: the task vectors' own Gram matrices stand in for RegMean's --, every
@@ -50,6 +54,8 @@ the consensus merge with TALL masks (merge.consensus_merge) and EMR-Merging (mer
                      consensus: n, op, k, tall_lambda, kept per source, selected, empty;
                      emr: n, op, kept per source, zero, conflict, abs_sum, uni_sum and rescale per source;
                      isoc, per matrix: n, shape, transposed, S, fro, nuclear, sigma_mean, steps, last_step, converged;
+                     tsvm, per matrix: n, shape, transposed, S, k, sweeps and converged of every SVD taken ({tau: per source, U, V}),
+                     s_max, s_kept_min, s_dropped_max and energy_kept per source, dropped ({U, V}: polar directions dropped);
                      wudi, per matrix: n, shape, S, iters, lr, sq per source, loss_first, loss_last)
 
 The output is a `{"state_dict": ...}` file of CPU tensors: checkpoint.load_ckpt and the reference's torch.load read it.
@@ -65,7 +71,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus", "emr", "isoc", "wudi")
+METHODS = ("interp", "taskvec", "ties", "dare", "breadcrumbs", "della", "stock", "sce", "slerp", "karcher", "consensus", "emr", "isoc", "tsvm", "wudi")
 
 
 def build_parser():
@@ -198,6 +204,11 @@ def merge_state(method, sd, cfg, central=None, density=0.2, report=None, dare=No
     elif method == "isoc":
         rows = []
         out = importlib.import_module("vl_merging_amd.isoc").isoc_merge(sd, cfg, central_weight=central, report_out=rows)
+        if report is not None:
+            report.extend(rows)
+    elif method == "tsvm":
+        rows = []
+        out = importlib.import_module("vl_merging_amd.tsvm").tsvm_merge(sd, cfg, central_weight=central, report_out=rows)
         if report is not None:
             report.extend(rows)
     elif method == "wudi":

@@ -773,19 +773,19 @@ def _f64_rhs(rhs, n, who):
     return rows, ld
 
 
-def gemm_f64_batched(a_list, b_list, c_list, alpha=1.0, beta=0.0):
-    """c[i] = alpha * a[i] @ b[i] + beta * c[i] for products of ONE shape, one launch per 64 of them (vlm_gemm_f64_batched);
-    a: contiguous float64 or float32 [M,K] (one dtype), b / c: contiguous float64."""
+def gemm_f64_batched(a_list, b_list, c_list, alpha=1.0, beta=0.0, ta=False):
+    """c[i] = alpha * op(a[i]) @ b[i] + beta * c[i] for products of ONE shape, one launch per 64 of them (vlm_gemm_f64_batched);
+    a: contiguous float64 or float32 [M,K] (one dtype) -- [K,M] with ta, op(a) = a^T: the T.N form --, b / c: contiguous float64."""
     if not (len(a_list) == len(b_list) == len(c_list)):
         raise L.VlmError("gemm_f64_batched: three lists of one length")
     if not a_list:
         return c_list
     L.require_cuda(*a_list, *b_list, *c_list)
     a0, b0, c0 = a_list[0], b_list[0], c_list[0]
-    M, K = a0.shape
+    M, K = (a0.shape[1], a0.shape[0]) if ta else a0.shape
     N = b0.shape[1]
     for a, b, c in zip(a_list, b_list, c_list):
-        if a.dtype != a0.dtype or a.dtype not in (F64, F32) or b.dtype != F64 or c.dtype != F64 or tuple(a.shape) != (M, K) \
+        if a.dtype != a0.dtype or a.dtype not in (F64, F32) or b.dtype != F64 or c.dtype != F64 or tuple(a.shape) != tuple(a0.shape) \
                 or tuple(b.shape) != (K, N) or tuple(c.shape) != (M, N) or not (a.is_contiguous() and b.is_contiguous() and c.is_contiguous()):
             raise L.VlmError("gemm_f64_batched: contiguous a [M,K] (one of float64/float32), float64 b [K,N], c [M,N] of one shape")
     if K == 0:
@@ -794,7 +794,7 @@ def gemm_f64_batched(a_list, b_list, c_list, alpha=1.0, beta=0.0):
                 c.zero_()
         return c_list
     for a, b, c in _f64_chunks(a_list, b_list, c_list):
-        L.check(L.get_lib().vlm_gemm_f64_batched(0, 0, M, N, K, float(alpha), _ptr_list(a), K, int(a0.dtype == F32), _ptr_list(b), N,
+        L.check(L.get_lib().vlm_gemm_f64_batched(int(bool(ta)), 0, M, N, K, float(alpha), _ptr_list(a), M if ta else K, int(a0.dtype == F32), _ptr_list(b), N,
                                                  float(beta), _ptr_list(c), N, len(a), L.stream_ptr()), "vlm_gemm_f64_batched")
     return c_list
 
@@ -992,6 +992,112 @@ def wudi_finish(work, base, dst, S, iters, lam, partials):
     _iso_f32(list(base) + list(dst), m, n, "wudi_finish")
     L.check(L.get_lib().vlm_wudi_finish(_ptr_list(work), _ptr_list(base), _ptr_list(dst), S, m, n, iters, float(lam), L.ptr(partials),
                                         len(work), L.stream_ptr()), "vlm_wudi_finish")
+    return dst
+
+
+def svd_work_doubles(p, q):
+    """Doubles in the working set of one [p <= q] matrix of the Jacobi SVD (include/vlm_hip.h: SVD_HEAD + p q + p p + 2 p)."""
+    return L.get_lib().vlm_svd_work_doubles(p, q)
+
+
+def svd_views(work, p, q):
+    """(head, A [p, q], R [p, p], s [p], rank [p] int32, order [p] int32): views of one working set."""
+    o = L.SVD_HEAD
+    ints = work[o + p * q + p * p + p: o + p * q + p * p + 2 * p].view(torch.int32)
+    return (work[:o], work[o: o + p * q].view(p, q), work[o + p * q: o + p * q + p * p].view(p, p),
+            work[o + p * q + p * p: o + p * q + p * p + p], ints[:p], ints[p:])
+
+
+def _svd_work(work, p, q, who):
+    if not 1 <= len(work) <= F64_MAX_BATCH or p < 1 or q < p:
+        raise L.VlmError("%s: 1 .. %d matrices of a working shape [p <= q]" % (who, F64_MAX_BATCH))
+    if q > L.SVD_MAX_Q:
+        raise L.VlmError("%s: a row of %d doubles does not fit a workgroup's registers (at most %d)" % (who, q, L.SVD_MAX_Q))
+    size = svd_work_doubles(p, q)
+    for w in work:
+        if w.dtype != F64 or w.dim() != 1 or w.numel() != size or not w.is_contiguous():
+            raise L.VlmError("%s: a working set is a contiguous float64 [%d] tensor for a [%d, %d] matrix" % (who, size, p, q))
+
+
+def svd_reset(work, p, q):
+    """R = I and a zero head for every working set (vlm_svd_reset): A is the caller's to fill, before or after."""
+    L.require_cuda(*work)
+    _svd_work(work, p, q, "svd_reset")
+    L.check(L.get_lib().vlm_svd_reset(_ptr_list(work), p, q, len(work), L.stream_ptr()), "vlm_svd_reset")
+    return work
+
+
+def svd_sweep(work, p, q, sweep):
+    """Sweep number `sweep` (from 0, in order) of the one-sided Jacobi iteration on every working set: one launch per tournament
+    step (vlm_svd_sweep).  A matrix whose previous sweep rotated nothing is left untouched."""
+    L.require_cuda(*work)
+    _svd_work(work, p, q, "svd_sweep")
+    if not 0 <= sweep < L.SVD_MAX_SWEEPS:
+        raise L.VlmError("svd_sweep: sweep %d of at most %d" % (sweep, L.SVD_MAX_SWEEPS))
+    L.check(L.get_lib().vlm_svd_sweep(_ptr_list(work), p, q, sweep, len(work), L.stream_ptr()), "vlm_svd_sweep")
+    return work
+
+
+def svd_finish(work, p, q, floor_rel=0.0):
+    """s, rank and order of every working set, its A turned into unit rows -- zero rows where s_j = 0 or s_j <= floor_rel * s_max --
+    head[0] = s_max, head[1] = the rows zeroed (vlm_svd_finish)."""
+    L.require_cuda(*work)
+    _svd_work(work, p, q, "svd_finish")
+    if not 0.0 <= floor_rel < 1.0:
+        raise L.VlmError("svd_finish: 0 <= floor_rel < 1, got %r" % (floor_rel,))
+    L.check(L.get_lib().vlm_svd_finish(_ptr_list(work), p, q, float(floor_rel), len(work), L.stream_ptr()), "vlm_svd_finish")
+    return work
+
+
+def tsv_delta(base, srcs, work):
+    """A of work[b] = srcs[b] - base[b] in float64 for matrices of ONE shape [m, n], stored [min, max] (transposed when m > n)
+    (vlm_tsv_delta).  svd_reset makes the set ready for its sweeps."""
+    m, n = base[0].shape
+    L.require_cuda(*base, *srcs, *work)
+    _svd_work(work, min(m, n), max(m, n), "tsv_delta")
+    if len(srcs) != len(base) or len(work) != len(base):
+        raise L.VlmError("tsv_delta: one source and one working set per central tensor")
+    _iso_f32(list(base) + list(srcs), m, n, "tsv_delta")
+    L.check(L.get_lib().vlm_tsv_delta(_ptr_list(base), _ptr_list(srcs), m, n, _ptr_list(work), len(base), L.stream_ptr()), "vlm_tsv_delta")
+    return work
+
+
+def tsv_gather(src_work, p, q, k, side, dst_work, scat=None):
+    """Rows [i k, (i + 1) k) of dst_work[b]'s A = expert i's k leading left (side 0, rows of R, length p) or right (side 1, unit
+    rows, length q) singular vectors, zero rows for zero singular values; side 1 writes the singular values to scat[b] [k S]
+    (vlm_tsv_gather).  src_work: S lists of len(dst_work) finished working sets of shape [p, q]."""
+    S = len(src_work)
+    flat = [w for ws in src_work for w in ws]
+    L.require_cuda(*flat, *dst_work, *(scat or []))
+    if not 1 <= S <= L.MERGE_MAX_SRC or any(len(ws) != len(dst_work) for ws in src_work) or side not in (0, 1) or not 1 <= k * S <= p:
+        raise L.VlmError("tsv_gather: 1 .. %d lists of working sets as long as the destinations, side 0 or 1, 1 <= k S <= p" % L.MERGE_MAX_SRC)
+    for ws in src_work:
+        _svd_work(ws, p, q, "tsv_gather")
+    _svd_work(dst_work, k * S, q if side else p, "tsv_gather")
+    if side:
+        if scat is None or len(scat) != len(dst_work) or any(s.dtype != F64 or s.numel() != k * S or not s.is_contiguous() for s in scat):
+            raise L.VlmError("tsv_gather: side 1 takes one contiguous float64 [k S] tensor per destination")
+    L.check(L.get_lib().vlm_tsv_gather(_ptr_list(flat), S, p, q, k, side, _ptr_list(dst_work), _ptr_list(scat) if side else None,
+                                       len(dst_work), L.stream_ptr()), "vlm_tsv_gather")
+    return dst_work
+
+
+def tsv_apply(pu, pv, scat, base, dst, t, kS, lam):
+    """t[b] [p, q] = pu[b]^T diag(scat[b]) pv[b] on the MFMA-f64 tiles and dst[b] = fl32(base[b] + lam * t[b]) in the tensors' own
+    orientation (vlm_tsv_apply); pu [kS, p], pv [kS, q] the transposed polar factors.  kS = 0: t = 0, dst = base bit for bit (pu, pv
+    and scat are not read).  dst[b] may be base[b] or a source."""
+    m, n = base[0].shape
+    p, q = min(m, n), max(m, n)
+    L.require_cuda(*pu, *pv, *scat, *base, *dst, *t)
+    if not 1 <= len(base) <= F64_MAX_BATCH or not (len(pu) == len(pv) == len(scat) == len(dst) == len(t) == len(base)) or not 0 <= kS <= p:
+        raise L.VlmError("tsv_apply: 1 .. %d matrices, one entry per list and matrix, 0 <= kS <= min(m, n)" % F64_MAX_BATCH)
+    _iso_f32(list(base) + list(dst), m, n, "tsv_apply")
+    for a, b, s, x in zip(pu, pv, scat, t):
+        if any(y.dtype != F64 or not y.is_contiguous() for y in (a, b, s, x)) or tuple(x.shape) != (p, q) \
+                or (kS and (tuple(a.shape) != (kS, p) or tuple(b.shape) != (kS, q) or s.numel() != kS)):
+            raise L.VlmError("tsv_apply: contiguous float64 pu [kS, %d], pv [kS, %d], scat [kS] and t [%d, %d]" % (p, q, p, q))
+    L.check(L.get_lib().vlm_tsv_apply(_ptr_list(pu), _ptr_list(pv), _ptr_list(scat), _ptr_list(base), _ptr_list(dst), _ptr_list(t), m, n,
+                                      kS, float(lam), len(base), L.stream_ptr()), "vlm_tsv_apply")
     return dst
 
 

@@ -97,6 +97,10 @@ def ulp_diff(a, b):
 
 # ---------------------------------------------------------------------------------------------------------------- inputs
 SHAPES = [(16, 16, 2), (48, 16, 3), (16, 32, 2), (40, 24, 4), (130, 70, 2), (200, 72, 3), (257, 129, 2)]
+# Past the limits of csrc/isoc.hip, kept apart from SHAPES so that no other parametrised test grows: 363 x 362 gives 65 partials
+# (the one-wave fold's second trip), 727 x 723 = 525 621 elements, odd and above 256 workgroups x 2048 (the stride loops' second
+# trip); each tall and wide, because the device works on the transpose when m < n.
+BOUNDARY_SHAPES = [(363, 362, 3), (362, 363, 2), (727, 723, 2), (723, 727, 2)]
 
 
 def planted_delta(m, n, sig, rng):

@@ -60,7 +60,16 @@ def test_gemm_f64_one_element_short_reduction(ops):
 
 
 def test_scale_gram(ops):
-    g = torch.randn(130, 130, device="cuda", dtype=torch.float64)
+    scale_gram_case(ops, 130)
+
+
+def test_scale_gram_past_the_grid_cap(ops):
+    assert 1025 * 1025 > 4096 * 256   # more elements than the capped grid has threads: the stride loop's second trip
+    scale_gram_case(ops, 1025)
+
+
+def scale_gram_case(ops, n):
+    g = torch.randn(n, n, device="cuda", dtype=torch.float64)
     g = g @ g.t()
     out = torch.empty_like(g)
     ops.scale_gram(g, out, 0.9)
@@ -149,6 +158,24 @@ def test_batched_gemm_is_the_single_call_bit_for_bit(ops, a32):
         for i in range(count):
             assert torch.equal(got[i], single[i]), (beta, i)
         want = A[7].double() @ B[7] + beta * C0[7]
+        assert float((got[7] - want).abs().max()) <= 1e-12 * float(want.abs().max())
+
+
+@pytest.mark.parametrize("a32", [False, True])
+def test_batched_gemm_with_a_transposed_is_the_single_call_bit_for_bit(ops, a32):
+    """The T.N form TSV-M's products take: a stored [K, M], op(a) = a^T; per product the bits of vlm_gemm_f64 with ta, with and
+    without the accumulate; 70 products cross the 64-per-launch table."""
+    gen = torch.Generator(device="cuda"); gen.manual_seed(9)
+    M, K, N, count = 100, 136, 72, 70
+    A = [torch.randn(K, M, device="cuda", dtype=torch.float32 if a32 else torch.float64, generator=gen) for _ in range(count)]
+    B = [torch.randn(K, N, device="cuda", dtype=torch.float64, generator=gen) for _ in range(count)]
+    C0 = [torch.randn(M, N, device="cuda", dtype=torch.float64, generator=gen) for _ in range(count)]
+    for beta in (0.0, 1.0):
+        single = [ops.gemm_f64(a, b, c.clone(), ta=True, beta=beta) for a, b, c in zip(A, B, C0)]
+        got = ops.gemm_f64_batched(A, B, [c.clone() for c in C0], beta=beta, ta=True)
+        for i in range(count):
+            assert torch.equal(got[i], single[i]), (beta, i)
+        want = A[7].double().t() @ B[7] + beta * C0[7]
         assert float((got[7] - want).abs().max()) <= 1e-12 * float(want.abs().max())
 
 

@@ -65,6 +65,22 @@ def test_iteration_meets_the_svd_definition(m, n, S):
         assert got[:, 5:9].tobytes() == c[:, 5:9].tobytes()
 
 
+@pytest.mark.parametrize("m,n,S", R.BOUNDARY_SHAPES)
+def test_the_boundary_inputs_are_well_posed(m, n, S):
+    """The condition of the GPU suite's rules at the shapes past the kernels' limits (test_isoc_gpu.py), at its lam: the numpy
+    iteration alone meets them with room to spare -- its error against the SVD leaves tol = min(1e-8, max(8 err, r eps)) far below
+    1e-8, X^T X = I to 1e-14, the last step a hundredth of its bound, and no fp32 output differs from the SVD definition's."""
+    c, srcs = R.inputs(m, n, S)
+    r = min(m, n)
+    want, q, nuc = R.iso_svd(c, srcs, 0.75)
+    got, X, nuc2, norms = R.iso_qdwh(c, srcs, 0.75)
+    assert np.abs(X - q).max() <= 1e-12 and abs(nuc - nuc2) <= 1e-13 * nuc
+    Xw = R.working(X)
+    assert np.abs(Xw.T @ Xw - np.eye(r)).max() <= 1e-14
+    assert norms[-1] <= 1e-12 * np.sqrt(r)
+    assert got.tobytes() == want.tobytes()
+
+
 def test_restatement_edges():
     c, srcs = R.inputs(16, 32, 2)
     out, X, nuc, norms = R.iso_qdwh(c, [c.copy(), c.copy()], 0.75)          # D = 0: c itself
@@ -94,6 +110,8 @@ def test_abi_exports_the_iso_entries(pkg):
     # host-side functions of the shape alone (no device is touched)
     assert lib.vlm_iso_parts(16, 16) == 1 and lib.vlm_iso_parts(0, 5) == 0
     assert lib.vlm_iso_parts(64, 33) == 2 and lib.vlm_iso_parts(3072, 768) == 256
+    # the boundary shapes cross the limits they are there for: a 65th partial; the cap with more than 2048 elements a workgroup
+    assert [lib.vlm_iso_parts(m, n) for m, n, _ in R.BOUNDARY_SHAPES] == [65, 65, 256, 256] and 727 * 723 > 256 * 2048
     isoc = importlib.import_module("vl_merging_amd.isoc")
     assert 8 + isoc.EXTRA_MAX <= L.ISO_MAX_STEPS and 2 + L.ISO_MAX_STEPS <= L.ISO_HEAD
     with pytest.raises(L.VlmError):

@@ -84,6 +84,32 @@ def check_output(got, c, X_own, nuclear, lam, want):
 # ---------------------------------------------------------------------------------------------------------------- kernels
 @pytest.mark.parametrize("m,n,S", R.SHAPES)
 def test_delta_bit_for_bit_and_its_norm(m, n, S, ops):
+    delta_bit_for_bit_and_its_norm(m, n, S, ops)
+
+
+def crosses_the_limit(m, n):
+    """A boundary shape is past the limit it is there for, by the library's own count of partials: more than the 64 a one-wave fold
+    reads in one trip, or the cap of 256 workgroups with more than 2048 elements each."""
+    parts = importlib.import_module("vl_merging_amd._lib").get_lib().vlm_iso_parts(m, n)
+    if m * n > 256 * 2048:
+        assert parts == 256 and (m * n) % 2 == 1
+    else:
+        assert parts == 65
+
+
+@pytest.mark.parametrize("m,n,S", R.BOUNDARY_SHAPES)
+def test_delta_bit_for_bit_and_its_norm_past_the_fold_and_the_cap(m, n, S, ops):
+    crosses_the_limit(m, n)
+    delta_bit_for_bit_and_its_norm(m, n, S, ops)
+
+
+@pytest.mark.parametrize("m,n,S", R.BOUNDARY_SHAPES)
+def test_polar_factor_nuclear_norm_and_output_past_the_fold_and_the_cap(m, n, S, isoc):
+    crosses_the_limit(m, n)
+    polar_factor_nuclear_norm_and_output(m, n, S, isoc)
+
+
+def delta_bit_for_bit_and_its_norm(m, n, S, ops):
     L = importlib.import_module("vl_merging_amd._lib")
     ref = reference(m, n, S)
     c, srcs = ref["c"], ref["srcs"]
@@ -106,6 +132,10 @@ def test_delta_bit_for_bit_and_its_norm(m, n, S, ops):
 
 @pytest.mark.parametrize("m,n,S", R.SHAPES)
 def test_polar_factor_nuclear_norm_and_output(m, n, S, isoc):
+    polar_factor_nuclear_norm_and_output(m, n, S, isoc)
+
+
+def polar_factor_nuclear_norm_and_output(m, n, S, isoc):
     ref = reference(m, n, S)
     c, srcs = ref["c"], ref["srcs"]
     r = min(m, n)

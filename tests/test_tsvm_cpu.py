@@ -118,6 +118,46 @@ def test_restated_sweeps_reach_the_svd(p, q):
     assert np.abs(Rm.T @ A - A0).max() <= 8 * p * 2.0 ** -52 * ref[0]
 
 
+@pytest.mark.parametrize("q", R.PAIR_Q)
+def test_restated_sweeps_on_duplicate_one_hot_pairs(q):
+    """The exact case of the GPU suite (test_tsvm_gpu.py) through the restated sweep: the values it asserts on the device are
+    what the device's formulas give in numpy doubles."""
+    A0, C, v = R.duplicate_pairs(q)
+    assert C[0] == 0 and C[-1] == q - 1 and len(C) == len(set(C)) and A0.shape == (2 * len(C), q)
+    assert all(u * 256 in C and min(u * 256 + 255, q - 1) in C for u in range((q + 255) // 256))
+    A, Rm, counts = R.jacobi(A0)
+    s = np.sqrt((A * A).sum(1))
+    Vt = np.divide(A, s[:, None], out=np.zeros_like(A), where=s[:, None] > 0)
+    R.check_duplicate_pairs(C, v, s, Vt, Rm, counts)
+
+
+@pytest.mark.parametrize("p,q", R.BOUNDARY_SKINNY)
+def test_restated_sweeps_reach_the_svd_at_the_long_rows(p, q):
+    """The skinny shapes of the GPU suite past q = 512, under the GPU suite's own constants (p 2^-52 units, test_tsvm_gpu.py):
+    the algorithm alone is well inside them, so a device value above is the kernel's."""
+    A0 = R.gaussian(p, q)
+    A, Rm, counts = R.jacobi(A0)
+    s = np.sqrt((A * A).sum(1))
+    Vt = A / s[:, None]
+    sl = np.linalg.svd(A0, compute_uv=False)
+    unit = p * 2.0 ** -52
+    assert counts[-1] == 0
+    assert np.abs(Rm @ Rm.T - np.eye(p)).max() <= 16.0 * unit and np.abs(Vt @ Vt.T - np.eye(p)).max() <= 12.0 * unit
+    assert np.sqrt(((A0 - Rm.T @ A) ** 2).sum()) <= 8.2 * unit * np.sqrt((A0 * A0).sum())
+    assert np.abs(np.sort(s)[::-1] - sl).max() <= 4.4 * unit * sl[0]
+
+
+@pytest.mark.parametrize("m,n,S", R.BOUNDARY_MERGE)
+def test_the_boundary_merge_inputs_are_well_posed(m, n, S):
+    """test_the_gpu_inputs_are_well_posed for the two merges past the kernels' grid caps, at the lam = 1 the GPU suite runs."""
+    c, srcs = R.planted(m, n, S)
+    a, b = R.tsvm(c, srcs, 1.0), R.tsvm(c, srcs, 1.0, flip=True)
+    u = R.ulp_diff(a["out"], b["out"])
+    assert u.max() <= 1 and int((u > 0).sum()) <= max(2, 1e-4 * c.size), (int(u.max()), int((u > 0).sum()))
+    k = a["k"]
+    assert k * S in (512, 513) and all(s[k - 1] > 5 * s[k] for s in a["s"]) and a["dropped"] == b["dropped"] == (0, 0)
+
+
 def test_restated_schedule_matches_the_header():
     """pairs() is csrc/jacobi_schedule.h in numpy: every pair once per sweep, disjoint within a step."""
     for p in list(range(1, 10)) + [64]:

@@ -30,7 +30,9 @@ F = np.float32
 U52 = 2.0 ** -52
 # residual <= C * p * 2^-52 (singular values and the reconstruction: relative to s_max and ||A||_F).  C = 8 x LAPACK's own worst
 # residual over these inputs in the same unit: 2.000 (U^T U - I), 1.500 (V V^T - I), 1.025 (reconstruction), 0.551 (its singular
-# values of A against those of A^T).  The device's worst on the first run: 1.788, 0.250, 0.853, 0.607.
+# values of A against those of A^T).  The device's worst on the first run: 1.788, 0.250, 0.853, 0.607.  The constants were not
+# retaken for the shapes past q = 512 and p = 256 (R.BOUNDARY_SKINNY, R.BOUNDARY_TALL), where the device's worst is 1.269, 0.667,
+# 1.062, 1.306 and the restated sweep's 1.50, 1.50, 1.05, 1.15 (LAPACK's own: 1.333, 2.500, 2.212, 1.170).
 C_ORTH_R, C_ORTH_V, C_RECON, C_SIGMA = 16.0, 12.0, 8.2, 4.4
 ROW_KEYS = ["dst", "n", "shape", "transposed", "S", "k", "sweeps", "converged", "s_max", "s_kept_min", "s_dropped_max", "energy_kept",
             "dropped"]
@@ -103,6 +105,71 @@ def test_svd_of_gaussian_matrices(p, q, tsvm):
         assert p == q or a[key].tobytes() == b[key].tobytes(), key
     (again,), _ = svd_run(tsvm, [A0])                # two runs, identical bits
     assert all(a[key].tobytes() == again[key].tobytes() for key in ("R", "Vt", "s", "rank", "order", "head")) and a["row"] == again["row"]
+
+
+@pytest.mark.parametrize("q", R.PAIR_Q)
+def test_svd_of_duplicate_one_hot_pairs_in_every_instantiation(q, tsvm):
+    """One q per instantiation of jacobi_step_kernel above PER = 1, entries at the first and last element of every register slot
+    (tsvm_restatement.duplicate_pairs): exact, no tolerance.  A slot left out of the three sums leaves gamma = 0 and the pair
+    unrotated (no zero row); a slot left out of the store leaves the row its old norm."""
+    A0, C, v = R.duplicate_pairs(q)
+    (got,), _ = svd_run(tsvm, [A0])
+    row = got["row"]
+    assert row["converged"] and row["sweeps"] == 2 and (row["p"], row["q"], row["transposed"]) == (2 * len(C), q, False)
+    R.check_duplicate_pairs(C, v, got["s"], got["Vt"], got["R"], row["rotations"])
+    assert got["head"][1] == len(C) and got["head"][0] == got["s"].max()
+
+
+@pytest.mark.parametrize("p,q", R.BOUNDARY_SKINNY)
+def test_svd_of_gaussian_matrices_at_the_long_rows(p, q, tsvm):
+    """Every instantiation from PER = 4 up at its first and last q, against LAPACK under the constants above."""
+    A0 = R.gaussian(p, q)
+    (a, b), _ = svd_run(tsvm, [A0, A0.T.copy()])
+    check_svd(A0, a, "long rows")
+    check_svd(A0.T, b, "long rows, tall")
+    for key in ("R", "Vt", "s", "rank", "order"):
+        assert a[key].tobytes() == b[key].tobytes(), key
+
+
+@pytest.mark.parametrize("p,q", R.BOUNDARY_TALL)
+def test_svd_of_gaussian_matrices_past_256_rows(p, q, tsvm):
+    """p > 256: the rotation of R in a second register slot and the second trip of svd_rank_kernel's loops; 513 x 513 elements of
+    R: svd_reset_kernel's grid at its cap."""
+    ops = importlib.import_module("vl_merging_amd.ops")
+    A0 = R.gaussian(p, q)
+    # an adopted working set that holds NaN wherever the kernels do not write: a rank or an order entry that a loop skips is no
+    # index then, whatever the allocator handed out
+    work = torch.full((ops.svd_work_doubles(p, q),), float("nan"), dtype=torch.float64, device="cuda")
+    ops.svd_views(work, p, q)[1].copy_(dev(A0))
+    plan = tsvm.SvdPlan("cuda")
+    j = plan.adopt(work, p, q)
+    plan.run()
+    torch.cuda.synchronize()
+    a = dict(R=plan.rt(j).cpu().numpy(), Vt=plan.vt(j).cpu().numpy(), s=plan.s(j).cpu().numpy(), rank=plan.rank(j).cpu().numpy(),
+             order=plan.order(j).cpu().numpy(), head=plan.head(j).cpu().numpy(), row=plan.rows[j])
+    check_svd(A0, a, "tall rows")
+
+
+@pytest.mark.parametrize("m,n", [(513, 513), (520, 513)])
+def test_tsv_delta_bit_for_bit_past_the_grid_cap(m, n, tsvm):
+    """m n > 256 workgroups x 1024 elements: the stride loop's second trip.  513 x 513 is odd (a tail of one element), 520 x 513
+    is tall (stored transposed).  Two matrices a call; nothing but A is written."""
+    L = importlib.import_module("vl_merging_amd._lib")
+    ops = importlib.import_module("vl_merging_amd.ops")
+    assert m * n > 256 * 1024 and (m * n) % 4 == (1 if m == n else 0)
+    p, q = min(m, n), max(m, n)
+    rng = np.random.default_rng(m + n)
+    cs = [rng.standard_normal((m, n)).astype(F) for _ in range(2)]
+    ss = [rng.standard_normal((m, n)).astype(F) for _ in range(2)]
+    work = torch.full((2, ops.svd_work_doubles(p, q)), float("nan"), dtype=torch.float64, device="cuda")
+    ops.tsv_delta([dev(c) for c in cs], [dev(s) for s in ss], [work[0], work[1]])
+    torch.cuda.synchronize()
+    got = work.cpu().numpy()
+    for b in range(2):
+        d = ss[b].astype(np.float64) - cs[b].astype(np.float64)
+        d = np.ascontiguousarray(d.T) if m > n else d
+        assert got[b, L.SVD_HEAD: L.SVD_HEAD + p * q].tobytes() == d.tobytes(), b
+        assert np.isnan(got[b, :L.SVD_HEAD]).all() and np.isnan(got[b, L.SVD_HEAD + p * q:]).all(), b
 
 
 def test_svd_rank_deficient_and_zero(tsvm):
@@ -216,6 +283,19 @@ def reference(m, n, S):
 @pytest.mark.parametrize("lam", [0.75, 1.0])
 @pytest.mark.parametrize("m,n,S", R.MERGE_CASES)
 def test_against_the_restatement(m, n, S, lam, tsvm):
+    against_the_restatement(m, n, S, lam, tsvm)
+
+
+@pytest.mark.parametrize("m,n,S", R.BOUNDARY_MERGE)
+def test_against_the_restatement_past_the_grid_caps(m, n, S, tsvm):
+    """The same check at one size past the limits: tsv_delta's grid cap, several tiles of tsv_apply each way with a reduction
+    kS = 512 and 513 (ragged by one against its 16-row stage), and the Jacobi kernels at p > 256, q > 512."""
+    k = min(m, n) // S
+    assert m * n > 256 * 1024 and k * S == (513 if S == 3 else 512) and min(m, n) > 256 and max(m, n) > 512
+    against_the_restatement(m, n, S, 1.0, tsvm)
+
+
+def against_the_restatement(m, n, S, lam, tsvm):
     ref = reference(m, n, S)
     c, srcs = ref["c"], ref["srcs"]
     p, q = min(m, n), max(m, n)

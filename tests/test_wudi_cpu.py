@@ -57,6 +57,21 @@ def test_loss_constant(m, n, S):
     assert ref["loss_first"] == ref["loss_last"]   # one step: the iterate the last step started from is X_0
 
 
+@pytest.mark.parametrize("case,iters", R.BOUNDARY_CASES)
+def test_the_boundary_inputs_are_well_posed(case, iters):
+    """The condition of the GPU suite's rules at the shapes past the kernels' limits (test_wudi_gpu.py): the restatement's two
+    summation orders differ by far less than the tolerance made from them, and in no fp32 output."""
+    m, n, S = case
+    c, srcs = R.inputs(m, n, S)
+    a, b = R.wudi(c, srcs, 0.75, iters), R.wudi(c, srcs, 0.75, iters, permute=True)
+    x0 = np.abs(a["X0"]).max()
+    spread = np.abs(a["X"] - b["X"]).max()
+    tol = min(2.0 ** -30 * x0, max(16 * spread, (n + iters) * 2.0 ** -52 * x0))
+    assert 16 * spread <= tol and tol == (n + iters) * 2.0 ** -52 * x0   # the rounding term decides, not the spread
+    assert a["out"].tobytes() == b["out"].tobytes()
+    assert a["loss_last"] < a["loss_first"]
+
+
 def test_restatement_edges():
     c, srcs = R.inputs(16, 24, 2)
     ref = R.wudi(c, [c.copy(), c.copy()], 0.75, 5)                            # zero task vectors: c itself, nothing NaN
@@ -85,6 +100,8 @@ def test_abi_exports_the_wudi_entries(pkg):
     assert lib.vlm_wudi_state_offset(3, 2, 0) == L.WUDI_HEAD + 8 + 6 and lib.vlm_wudi_state_offset(3, 2, 2) == L.WUDI_HEAD + 8 + 6
     assert lib.vlm_wudi_state_offset(3, 2, 301) == L.WUDI_HEAD + 8 + 12
     assert lib.vlm_wudi_parts(64, 64) == 2 + 2 and lib.vlm_wudi_parts(130, 70) == 5 + 2 * 6 and lib.vlm_wudi_parts(0, 1) == 0
+    # the boundary shapes cross the limits they are there for: the capped 256 partials and 144 tiles; a 65th partial
+    assert [lib.vlm_wudi_parts(*case[:2]) for case, _ in R.BOUNDARY_CASES] == [256 + 2 * 144, 256 + 2 * 144, 65 + 2 * 36]
     wudi = importlib.import_module("vl_merging_amd.wudi")
     with pytest.raises(L.VlmError):
         wudi.WudiPlan("cpu")

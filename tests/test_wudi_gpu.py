@@ -98,6 +98,28 @@ def check_matrix(got, X, row, c, srcs, lam, iters, ref, what):
 @pytest.mark.parametrize("iters", R.STEPS)
 @pytest.mark.parametrize("m,n,S", R.SHAPES)
 def test_against_the_restatement(m, n, S, iters, wudi):
+    against_the_restatement(m, n, S, iters, wudi)
+
+
+def boundary_counts(m, n):
+    """(partials of an elementwise sum, tiles) of a shape from the library's own count, vlm_wudi_parts = partials + 2 tiles with
+    64 x 64 tiles; the partials are those of the larger of [m][n] and [n][n]."""
+    tiles = -(-m // 64) * -(-n // 64)
+    return importlib.import_module("vl_merging_amd._lib").get_lib().vlm_wudi_parts(m, n) - 2 * tiles, tiles, n * max(m, n)
+
+
+@pytest.mark.parametrize("case,iters", R.BOUNDARY_CASES)
+def test_against_the_restatement_past_the_fold_and_the_cap(case, iters, wudi):
+    m, n, S = case
+    sums, tiles, N = boundary_counts(m, n)
+    if m * n > 256 * 2048:   # the cap of 256 workgroups with more than 2048 elements each, and a loss fold over more than 64 tiles
+        assert sums == 256 and N > 256 * 2048 and (m * n) % 2 == 1 and tiles == 144
+    else:                    # a 65th partial for the one-wave fold
+        assert sums == 65 and tiles == 36
+    against_the_restatement(m, n, S, iters, wudi)
+
+
+def against_the_restatement(m, n, S, iters, wudi):
     c, srcs = R.case(m, n, S)
     ref = reference(c, srcs, LAM, iters, (m, n, S, iters))
     (got,), (X,), (row,), _ = run(wudi, [(c, srcs, LAM)], iters)

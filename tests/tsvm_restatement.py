@@ -134,6 +134,58 @@ SHAPES = [(1, 1), (2, 3), (5, 7), (8, 8), (33, 70), (64, 192), (96, 288)]
 MERGE_CASES = sorted({(m, n, S) for (p, q) in SHAPES for (m, n) in ((p, q), (q, p)) for S in (2, 3)})
 
 
+# Past the limits of csrc/jacobi.hip and csrc/tsvm.hip, kept apart from SHAPES and MERGE_CASES so that no other parametrised test
+# grows: the step kernel is instantiated for PER = 1, 2, 4, 8, 12, 16, 32 doubles per lane and row and dispatched by ceil(q / 256).
+PAIR_Q = [300, 768, 1100, 3072, 3073, 8192]             # one q per instantiation above PER = 1: 2, 4, 8, 12, 16, 32
+# skinny: the first and the last q of every instantiation from 4 up, each run as given and tall
+BOUNDARY_SKINNY = [(2, 513), (3, 1024), (2, 1025), (3, 2048), (2, 2049), (3, 3072), (2, 3073), (3, 4096), (2, 4097), (3, 8192), (4, 768)]
+# p > 256: the second register slot of a row of R and the second trip of the rank loop; p p > 1024 x 256: the reset grid's cap
+BOUNDARY_TALL = [(257, 300), (513, 520)]
+# m n > 256 x 1024 (the delta grid's cap); the second has kS = 513 = p, ragged by one against the 16-row stage of the apply
+BOUNDARY_MERGE = [(513, 520, 2), (520, 513, 3)]
+
+
+def pair_columns(q):
+    """The first and the last element of every 256-wide register slot a row of q doubles fills, with 0 and q - 1."""
+    cols = {0, q - 1}
+    for u in range((q + 255) // 256):
+        cols |= {u * 256, min(u * 256 + 255, q - 1)}
+    return sorted(cols)
+
+
+def duplicate_pairs(q):
+    """(A [2 L, q], C, v): rows 2a and 2a + 1 both hold the single entry v[a] = (-1)^a 2^-(a % 20) at column C[a] = pair_columns(q)[a].
+    Distinct pairs have disjoint supports (gamma = 0: no rotation); a duplicate pair has alpha = beta = gamma: zeta = 0, t = 1,
+    c = s, and its one rotation leaves row 2a exactly zero and row 2a + 1 = (c v + c v) e_C[a]."""
+    C = pair_columns(q)
+    v = np.array([(-1.0) ** a * 2.0 ** -(a % 20) for a in range(len(C))])
+    A = np.zeros((2 * len(C), q))
+    for a, col in enumerate(C):
+        A[2 * a, col] = A[2 * a + 1, col] = v[a]
+    return A, C, v
+
+
+def check_duplicate_pairs(C, v, s, Vt, Rm, rotations):
+    """What a Jacobi SVD of duplicate_pairs(q) gives, with no tolerance beyond the rounding of c = 1 / sqrt(2) itself: s [2 L] the
+    row norms, Vt [2 L, q] the unit rows (zero rows where s = 0), Rm [2 L, 2 L] the accumulated rotations, rotations per sweep."""
+    L = len(C)
+    assert list(rotations) == [L, 0]                                       # every duplicate pair once; the second sweep rotates nothing
+    assert int((s == 0.0).sum()) == L and not s[0::2].any()                # one exact zero per pair: a slot never loaded or stored breaks it
+    want = np.sqrt(2.0) * np.abs(v)
+    assert (np.abs(s[1::2] - want) <= 2 * np.spacing(want)).all()
+    hot = np.zeros_like(Vt)
+    hot[2 * np.arange(L) + 1, C] = np.sign(v)                              # (c v + c v) / |c v + c v|: exactly +-1 at the planted column
+    assert np.array_equal(Vt, hot)
+    c = 1.0 / np.sqrt(2.0)
+    a = 2 * np.arange(L)
+    blocks = np.stack([Rm[a, a], -Rm[a, a + 1], Rm[a + 1, a], Rm[a + 1, a + 1]])   # (c, -s; s, c) with s = c
+    assert (np.abs(blocks - c) <= np.spacing(c)).all()
+    rest = Rm.copy()
+    for d in ((0, 0), (0, 1), (1, 0), (1, 1)):
+        rest[a + d[0], a + d[1]] = 0.0
+    assert not rest.any()
+
+
 def gaussian(p, q, seed=0):
     return np.random.default_rng(5000 * p + q + seed).standard_normal((p, q))
 

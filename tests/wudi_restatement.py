@@ -80,6 +80,10 @@ def ulp_diff(a, b):
 SHAPES = [(80, 48, 2), (48, 80, 3), (130, 70, 2), (64, 64, 2), (1, 130, 2), (67, 1, 3)]
 STEPS = [1, 7, 40]
 LONG = ((80, 48, 2), 300)   # one run at the default step count
+# Past the limits of csrc/wudi.hip, kept apart from SHAPES so that no other parametrised test grows, ((m, n, S), steps): 727 x 723 is
+# odd, above 256 workgroups x 2048 elements (the stride loops' second trip) and 12 x 12 = 144 tiles (the loss fold's third trip),
+# tall and wide because the sum grid takes the larger of [m][n] and [n][n]; 363 x 362 gives 65 partials (the fold's second trip)
+BOUNDARY_CASES = [((727, 723, 2), 7), ((723, 727, 3), 7), ((363, 362, 2), 40)]
 
 
 def inputs(m, n, S, s=1e-3, seed=0):

@@ -2,56 +2,19 @@
 // and the order of its operations: include/vlm_hip.h.  Per step the products, the factorisation and the solve are csrc/f64ops.hip's
 // (vlm_iso_gram: the SYRK body of the Gram cache; vlm_cholesky_f64_batched; vlm_solve_spd_right_f64_batched); what is here forms D
 // and its norm, combines X and Y after a step, and writes the merged tensor.  Every kernel runs `count` matrices of one shape in
-// lock step, blockIdx.y the matrix, pointers from kernel-argument tables (f64_tab.h).
+// lock step, blockIdx.y the matrix, pointers from kernel-argument tables (f64_tab.h, f32_io.h).
 //
-// Sums (||D||_F^2, the step norms, <X, D>) are made in a FIXED order: a thread adds its elements in index order, a workgroup's 256
-// sums meet in a shuffle tree, the workgroups' partials (iso_parts of them, a function of the shape alone) are added by one wave in
-// the same way.  No atomics: three runs give the same bits.
+// Sums (||D||_F^2, the step norms, <X, D>) are made in the FIXED order of f64_sum.h, f64_elem_parts(rows * cols) partials per matrix:
+// three runs give the same bits.  The fp32 tensors are read and written through f32_io.h.
 #include "vlm_common.h"
 #include "f64_tab.h"
-
-#define ISO_MAX_PARTS 256
-#define ISO_PER_BLOCK 2048  // elements per partial: a matrix of N elements runs min(ISO_MAX_PARTS, ceil(N / 2048)) workgroups, each
-                            // striding over the matrix and leaving one partial sum
+#include "f64_sum.h"
+#include "f32_io.h"
 
 struct iso_in_tab_t {
   const float* c[VLM_F64_MAX_BATCH];
   const float* s[VLM_MERGE_MAX_SRC][VLM_F64_MAX_BATCH];
 };
-struct f32_tab_t {
-  float* p[VLM_F64_MAX_BATCH];
-};
-
-static int iso_parts(size_t N) {
-  const size_t p = (N + ISO_PER_BLOCK - 1) / ISO_PER_BLOCK;
-  return p > ISO_MAX_PARTS ? ISO_MAX_PARTS : (int)(p ? p : 1);
-}
-
-// The workgroup's sum of `v` in a fixed order, valid in thread 0.
-__device__ __forceinline__ double iso_block_sum(double v) {
-  __shared__ double wsum[4];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = __dadd_rn(v, __shfl_down(v, d));
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return __dadd_rn(__dadd_rn(wsum[0], wsum[1]), __dadd_rn(wsum[2], wsum[3]));
-}
-
-// W[b][slot] = the sum of matrix b's `parts` partials: one wave per matrix.
-__global__ __launch_bounds__(64) void iso_fold_kernel(const double* __restrict__ partials, int parts, const f64_tab_t W, int slot) {
-  const double* __restrict__ p = partials + (size_t)blockIdx.x * parts;
-  double v = 0.0;
-  for (int i = threadIdx.x; i < parts; i += 64) v = __dadd_rn(v, p[i]);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = __dadd_rn(v, __shfl_down(v, d));
-  if (threadIdx.x == 0) W.p[blockIdx.x][slot] = v;
-}
-
-static int iso_fold(const double* partials, int parts, const f64_tab_t& W, int slot, int count, hipStream_t s) {
-  hipLaunchKernelGGL(iso_fold_kernel, dim3(count), dim3(64), 0, s, partials, parts, W, slot);
-  VLM_CHECK_LAUNCH();
-  return VLM_OK;
-}
 
 // D = ((0 + (W_0 - c)) + (W_1 - c)) + ... in fp64 from the fp32 tensors [m][n] (float4 loads; a ragged tail element by element),
 // stored in working orientation -- transposed when m < n -- as D and as Y, the first solve's right-hand side.  The transposed store
@@ -67,24 +30,10 @@ __global__ __launch_bounds__(256) void iso_delta_kernel(const iso_in_tab_t in, c
   for (size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; e < N; e += (size_t)gridDim.x * 1024) {
     const int cnt = N - e < 4 ? (int)(N - e) : 4;
     float cv[4], sv[VLM_MERGE_MAX_SRC][4];
-    if (cnt == 4) {
-      const float4 t = *reinterpret_cast<const float4*>(c + e);
-      cv[0] = t.x, cv[1] = t.y, cv[2] = t.z, cv[3] = t.w;
+    f32_load4(c, e, cnt, cv);
 #pragma unroll
-      for (int k = 0; k < VLM_MERGE_MAX_SRC; ++k)
-        if (k < S) {
-          const float4 u = *reinterpret_cast<const float4*>(in.s[k][b] + e);
-          sv[k][0] = u.x, sv[k][1] = u.y, sv[k][2] = u.z, sv[k][3] = u.w;
-        }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        cv[j] = j < cnt ? c[e + j] : 0.0f;
-#pragma unroll
-        for (int k = 0; k < VLM_MERGE_MAX_SRC; ++k)
-          if (k < S) sv[k][j] = j < cnt ? in.s[k][b][e + j] : 0.0f;
-      }
-    }
+    for (int k = 0; k < VLM_MERGE_MAX_SRC; ++k)
+      if (k < S) f32_load4(in.s[k][b], e, cnt, sv[k]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (j >= cnt) break;
@@ -93,13 +42,13 @@ __global__ __launch_bounds__(256) void iso_delta_kernel(const iso_in_tab_t in, c
       for (int k = 0; k < VLM_MERGE_MAX_SRC; ++k)
         if (k < S) d = __dadd_rn(d, __dsub_rn((double)sv[k][j], (double)cv[j]));
       const size_t f = e + j;
-      const size_t w = transposed ? (f % n) * m + f / n : f;
+      const size_t w = transposed ? f64_transposed(f, m, n) : f;
       D[w] = d;
       Y[w] = d;
       acc = __dadd_rn(acc, __dmul_rn(d, d));
     }
   }
-  acc = iso_block_sum(acc);
+  acc = f64_block_sum(acc);
   if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = acc;
 }
 
@@ -127,7 +76,7 @@ __global__ __launch_bounds__(256) void iso_step_kernel(const f64_tab_t W, size_t
     X[e] = xn;
     Y[e] = xn;
   }
-  acc = iso_block_sum(acc);
+  acc = f64_block_sum(acc);
   if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = acc;
 }
 
@@ -138,14 +87,14 @@ __global__ __launch_bounds__(256) void iso_dot_kernel(const f64_tab_t W, size_t 
   const double* __restrict__ X = D + N;
   double acc = 0.0;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < N; e += (size_t)gridDim.x * 256) acc = __dadd_rn(acc, __dmul_rn(X[e], D[e]));
-  acc = iso_block_sum(acc);
+  acc = f64_block_sum(acc);
   if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = acc;
 }
 
 // finish, phase 2: dst = fl32(c + s X) with s = (lam * <X, D>) / r, X read back through the transpose when m < n (strided, once per
 // merge); c itself where ||D||_F^2 = 0.  A thread reads its elements of c before it writes them: dst may be c, or a source (no
 // source is read here).
-__global__ __launch_bounds__(256) void iso_apply_kernel(const iso_in_tab_t in, const f32_tab_t dst, const f64_tab_t W, int m, int n,
+__global__ __launch_bounds__(256) void iso_apply_kernel(const iso_in_tab_t in, const f32_out_tab_t dst, const f64_tab_t W, int m, int n,
                                                         int transposed, double lam, double r) {
   const int b = blockIdx.y;
   const size_t N = (size_t)m * n;
@@ -158,63 +107,36 @@ __global__ __launch_bounds__(256) void iso_apply_kernel(const iso_in_tab_t in, c
   for (size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; e < N; e += (size_t)gridDim.x * 1024) {
     const int cnt = N - e < 4 ? (int)(N - e) : 4;
     float cv[4];
-    if (cnt == 4) {
-      const float4 t = *reinterpret_cast<const float4*>(c + e);
-      cv[0] = t.x, cv[1] = t.y, cv[2] = t.z, cv[3] = t.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) cv[j] = j < cnt ? c[e + j] : 0.0f;
-    }
+    f32_load4(c, e, cnt, cv);
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const size_t f = e + j;
-      const double x = j < cnt ? X[transposed ? (f % n) * m + f / n : f] : 0.0;
+      const double x = j < cnt ? X[transposed ? f64_transposed(f, m, n) : f] : 0.0;
       o[j] = zero ? cv[j] : __double2float_rn(__dadd_rn((double)cv[j], __dmul_rn(s, x)));
     }
-    if (cnt == 4) {
-      *reinterpret_cast<float4*>(out + e) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (j < cnt) out[e + j] = o[j];
-    }
+    f32_store4(out, e, cnt, o);
   }
 }
 
-static int iso_shape(int m, int n, int count) {
-  return m > 0 && n > 0 && count > 0 && count <= VLM_F64_MAX_BATCH ? VLM_OK : VLM_ERR_ARG;
-}
+static int iso_shape(int m, int n, int count) { return m > 0 && n > 0 ? f64_count(count) : VLM_ERR_ARG; }
 
-static int iso_in_tab(const float* const* c_list, const float* const* src_list, int S, int count, iso_in_tab_t& t) {
-  if (!c_list) return VLM_ERR_ARG;
-  for (int i = 0; i < count; ++i) {
-    if (!c_list[i] || ((uintptr_t)c_list[i] & 15)) return VLM_ERR_ARG;
-    t.c[i] = c_list[i];
-    for (int k = 0; k < S; ++k) {
-      const float* s = src_list[(size_t)k * count + i];
-      if (!s || ((uintptr_t)s & 15)) return VLM_ERR_ARG;
-      t.s[k][i] = s;
-    }
-  }
-  return VLM_OK;
-}
-
-extern "C" int vlm_iso_parts(int m, int n) { return m > 0 && n > 0 ? iso_parts((size_t)m * n) : 0; }
+extern "C" int vlm_iso_parts(int m, int n) { return m > 0 && n > 0 ? f64_elem_parts((size_t)m * n) : 0; }
 
 extern "C" int vlm_iso_delta(const float* const* c_list, const float* const* src_list, int S, int m, int n, double* const* work_list,
                              double* partials, int count, void* stream) {
   if (iso_shape(m, n, count) || S < 1 || S > VLM_MERGE_MAX_SRC || !src_list || !partials) return VLM_ERR_ARG;
   iso_in_tab_t in;
   f64_tab_t W;
-  int rc = iso_in_tab(c_list, src_list, S, count, in);
+  int rc = f32_ptrs(c_list, count, in.c);
+  for (int k = 0; k < S && !rc; ++k) rc = f32_ptrs(src_list + (size_t)k * count, count, in.s[k]);
   if (!rc) rc = f64_tab(work_list, count, W);
   if (rc) return rc;
-  const int parts = iso_parts((size_t)m * n);
+  const int parts = f64_elem_parts((size_t)m * n);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(iso_delta_kernel, dim3(parts, count), dim3(256), 0, s, in, W, S, m, n, m < n ? 1 : 0, partials);
   VLM_CHECK_LAUNCH();
-  return iso_fold(partials, parts, W, ISO_FRO2, count, s);
+  return f64_fold(partials, parts, parts, W, ISO_FRO2, count, s);
 }
 
 extern "C" int vlm_iso_step(double* const* work_list, int rows, int cols, int first, double p, double q, int k, double* partials,
@@ -224,11 +146,11 @@ extern "C" int vlm_iso_step(double* const* work_list, int rows, int cols, int fi
   int rc = f64_tab(work_list, count, W);
   if (rc) return rc;
   const size_t N = (size_t)rows * cols;
-  const int parts = iso_parts(N);
+  const int parts = f64_elem_parts(N);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(iso_step_kernel, dim3(parts, count), dim3(256), 0, s, W, N, first, p, q, partials);
   VLM_CHECK_LAUNCH();
-  return iso_fold(partials, parts, W, ISO_STEP0 + k, count, s);
+  return f64_fold(partials, parts, parts, W, ISO_STEP0 + k, count, s);
 }
 
 extern "C" int vlm_iso_finish(double* const* work_list, const float* const* c_list, float* const* dst_list, int m, int n, double lam,
@@ -236,22 +158,19 @@ extern "C" int vlm_iso_finish(double* const* work_list, const float* const* c_li
   if (iso_shape(m, n, count) || !dst_list || !partials || phases < 1 || phases > (VLM_ISO_PHASE_NUCLEAR | VLM_ISO_PHASE_APPLY))
     return VLM_ERR_ARG;
   iso_in_tab_t in;
-  f32_tab_t dst;
+  f32_out_tab_t dst;
   f64_tab_t W;
-  int rc = iso_in_tab(c_list, nullptr, 0, count, in);
+  int rc = f32_ptrs(c_list, count, in.c);
+  if (!rc) rc = f32_ptrs(dst_list, count, dst.p);
   if (!rc) rc = f64_tab(work_list, count, W);
   if (rc) return rc;
-  for (int i = 0; i < count; ++i) {
-    if (!dst_list[i] || ((uintptr_t)dst_list[i] & 15)) return VLM_ERR_ARG;
-    dst.p[i] = dst_list[i];
-  }
   const size_t N = (size_t)m * n;
-  const int parts = iso_parts(N);
+  const int parts = f64_elem_parts(N);
   hipStream_t s = (hipStream_t)stream;
   if (phases & VLM_ISO_PHASE_NUCLEAR) {
     hipLaunchKernelGGL(iso_dot_kernel, dim3(parts, count), dim3(256), 0, s, W, N, partials);
     VLM_CHECK_LAUNCH();
-    rc = iso_fold(partials, parts, W, ISO_NUCLEAR, count, s);
+    rc = f64_fold(partials, parts, parts, W, ISO_NUCLEAR, count, s);
     if (rc) return rc;
   }
   if (phases & VLM_ISO_PHASE_APPLY) {

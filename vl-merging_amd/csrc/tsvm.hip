@@ -2,25 +2,18 @@
 // SVD working sets, the gather of every expert's leading triplets into Ucat^T and Vcat^T, and the recombination
 // Uo diag(scat) Vo^T on the MFMA-f64 tiles of f64_tile.h with the output in its epilogue.  The rule: include/vlm_hip.h.  Every
 // kernel runs `count` matrices of one shape in lock step, blockIdx.y (the product: .z) the matrix, pointers from kernel-argument
-// tables.  No atomics and no sums outside the product: the same bits every run.
+// tables (f64_tab.h, f32_io.h).  No atomics and no sums outside the product: the same bits every run.
 #include "vlm_common.h"
 #include "f64_tab.h"
+#include "f32_io.h"
 #include "f64_tile.h"
 
-struct tsv_in_tab_t {
-  const float* c[VLM_F64_MAX_BATCH];
-  const float* s[VLM_F64_MAX_BATCH];
-};
 struct tsv_src_tab_t {
   const double* w[VLM_MERGE_MAX_SRC][VLM_F64_MAX_BATCH];
 };
-struct tsv_out_tab_t {
-  const float* c[VLM_F64_MAX_BATCH];
-  float* dst[VLM_F64_MAX_BATCH];
-};
 
 // A = W - c in fp64 from the fp32 tensors [m][n], stored as [p <= q] rows: transposed when m > n (a strided store, once per merge).
-__global__ __launch_bounds__(256) void tsv_delta_kernel(const tsv_in_tab_t in, const f64_tab_t W, int m, int n, int transposed) {
+__global__ __launch_bounds__(256) void tsv_delta_kernel(const f32_in_tab_t in, const f64_tab_t W, int m, int n, int transposed) {
   const int b = blockIdx.y;
   const size_t N = (size_t)m * n;
   const float* __restrict__ c = in.c[b];
@@ -29,22 +22,13 @@ __global__ __launch_bounds__(256) void tsv_delta_kernel(const tsv_in_tab_t in, c
   for (size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; e < N; e += (size_t)gridDim.x * 1024) {
     const int cnt = N - e < 4 ? (int)(N - e) : 4;
     float cv[4], sv[4];
-    if (cnt == 4) {
-      const float4 t = *reinterpret_cast<const float4*>(c + e), u = *reinterpret_cast<const float4*>(s + e);
-      cv[0] = t.x, cv[1] = t.y, cv[2] = t.z, cv[3] = t.w;
-      sv[0] = u.x, sv[1] = u.y, sv[2] = u.z, sv[3] = u.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        cv[j] = j < cnt ? c[e + j] : 0.0f;
-        sv[j] = j < cnt ? s[e + j] : 0.0f;
-      }
-    }
+    f32_load4(c, e, cnt, cv);
+    f32_load4(s, e, cnt, sv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (j >= cnt) break;
       const size_t f = e + j;
-      A[transposed ? (f % n) * m + f / n : f] = (double)sv[j] - (double)cv[j];
+      A[transposed ? f64_transposed(f, m, n) : f] = (double)sv[j] - (double)cv[j];
     }
   }
 }
@@ -71,7 +55,7 @@ __global__ __launch_bounds__(256) void tsv_gather_kernel(const tsv_src_tab_t src
 // T [p][q] = PU^T diag(scat) PV with PU [kS][p] and PV [kS][q] (the transposed polar factors), one 64 x 64 tile per workgroup, and
 // dst = fl32(c + lam * T) in the tensor's own orientation (element (i, j) of T is element (j, i) of a tall tensor).  A lane reads
 // its elements of c before it writes them: dst may be c.  kS = 0: T = 0 and dst = c bit for bit.
-__global__ __launch_bounds__(256) void tsv_apply_kernel(const f64_tab_t PU, const f64_tab_t PV, const f64_tab_t scat, const tsv_out_tab_t io,
+__global__ __launch_bounds__(256) void tsv_apply_kernel(const f64_tab_t PU, const f64_tab_t PV, const f64_tab_t scat, const f32_io_tab_t io,
                                                         const f64_tab_t Tt, int p, int q, int kS, int n_orig, int transposed, double lam) {
   __shared__ double sa[F64_LDS_DOUBLES], sb[F64_LDS_DOUBLES];
   const int b = blockIdx.z;
@@ -94,26 +78,16 @@ __global__ __launch_bounds__(256) void tsv_apply_kernel(const f64_tab_t PU, cons
   });
 }
 
-static int tsv_f32(const float* const* list, int count) {
-  if (!list) return VLM_ERR_ARG;
-  for (int i = 0; i < count; ++i)
-    if (!list[i] || ((uintptr_t)list[i] & 15)) return VLM_ERR_ARG;
-  return VLM_OK;
-}
-
-static int tsv_count(int count) { return count >= 1 && count <= VLM_F64_MAX_BATCH ? VLM_OK : VLM_ERR_ARG; }
-
 extern "C" int vlm_tsv_delta(const float* const* c_list, const float* const* src_list, int m, int n, double* const* work_list, int count,
                              void* stream) {
-  if (m < 1 || n < 1 || tsv_count(count)) return VLM_ERR_ARG;
+  if (m < 1 || n < 1 || f64_count(count)) return VLM_ERR_ARG;
   if ((m > n ? m : n) > 8192) return VLM_ERR_UNSUPPORTED;
-  tsv_in_tab_t in;
+  f32_in_tab_t in;
   f64_tab_t W;
-  int rc = tsv_f32(c_list, count);
-  if (!rc) rc = tsv_f32(src_list, count);
+  int rc = f32_ptrs(c_list, count, in.c);
+  if (!rc) rc = f32_ptrs(src_list, count, in.s);
   if (!rc) rc = f64_tab(work_list, count, W);
   if (rc) return rc;
-  for (int i = 0; i < count; ++i) in.c[i] = c_list[i], in.s[i] = src_list[i];
   const size_t blocks = ((size_t)m * n + 1023) / 1024;
   hipLaunchKernelGGL(tsv_delta_kernel, dim3((unsigned)(blocks > 256 ? 256 : blocks), count), dim3(256), 0, (hipStream_t)stream, in, W, m, n,
                      m > n ? 1 : 0);
@@ -123,7 +97,7 @@ extern "C" int vlm_tsv_delta(const float* const* c_list, const float* const* src
 
 extern "C" int vlm_tsv_gather(const double* const* src_work_list, int S, int p, int q, int k, int side, double* const* dst_work_list,
                               double* const* scat_list, int count, void* stream) {
-  if (S < 1 || S > VLM_MERGE_MAX_SRC || p < 1 || q < p || k < 1 || (long)k * S > p || (side != 0 && side != 1) || tsv_count(count) ||
+  if (S < 1 || S > VLM_MERGE_MAX_SRC || p < 1 || q < p || k < 1 || (long)k * S > p || (side != 0 && side != 1) || f64_count(count) ||
       !src_work_list)
     return VLM_ERR_ARG;
   tsv_src_tab_t src;
@@ -145,17 +119,16 @@ extern "C" int vlm_tsv_apply(const double* const* pu_list, const double* const* 
                              const float* const* c_list, float* const* dst_list, double* const* t_list, int m, int n, int kS, double lam,
                              int count, void* stream) {
   const int p = m < n ? m : n, q = m < n ? n : m;
-  if (m < 1 || n < 1 || kS < 0 || kS > p || tsv_count(count)) return VLM_ERR_ARG;
+  if (m < 1 || n < 1 || kS < 0 || kS > p || f64_count(count)) return VLM_ERR_ARG;
   f64_tab_t PU, PV, scat, T;
-  tsv_out_tab_t io;
+  f32_io_tab_t io;
   int rc = f64_tab(const_cast<double* const*>(pu_list), count, PU);
   if (!rc) rc = f64_tab(const_cast<double* const*>(pv_list), count, PV);
   if (!rc) rc = f64_tab(const_cast<double* const*>(scat_list), count, scat);
   if (!rc) rc = f64_tab(t_list, count, T);
-  if (!rc) rc = tsv_f32(c_list, count);
-  if (!rc) rc = tsv_f32(const_cast<const float* const*>(dst_list), count);
+  if (!rc) rc = f32_ptrs(c_list, count, io.c);
+  if (!rc) rc = f32_ptrs(dst_list, count, io.dst);
   if (rc) return rc;
-  for (int i = 0; i < count; ++i) io.c[i] = c_list[i], io.dst[i] = dst_list[i];
   dim3 grid((q + F64_TILE - 1) / F64_TILE, (p + F64_TILE - 1) / F64_TILE, count);
   hipLaunchKernelGGL(tsv_apply_kernel, grid, dim3(256), 0, (hipStream_t)stream, PU, PV, scat, io, T, p, q, kS, n, m > n ? 1 : 0, lam);
   VLM_CHECK_LAUNCH();

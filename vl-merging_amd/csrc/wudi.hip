@@ -9,14 +9,13 @@
 // reads that row's whole panel of X_{t-1} as its A operand while its neighbours are already in their epilogues: updated in place,
 // late readers would multiply a mixture of two iterates.
 //
-// Sums (n_i, ||G_i||_F^2, the loss) are made in a FIXED order and without atomics: a thread adds its elements in index order, a
-// workgroup's 256 sums meet in a shuffle tree, the partials are added by one wave in the same way: the same bits every run.
+// Sums (n_i, ||G_i||_F^2, the loss) are made in the FIXED order of f64_sum.h, without atomics: the same bits every run.  The fp32
+// tensors are read and written through f32_io.h.
 #include "vlm_common.h"
 #include "f64_tab.h"
+#include "f64_sum.h"
+#include "f32_io.h"
 #include "f64_tile.h"
-
-#define WUDI_MAX_PARTS 256
-#define WUDI_PER_BLOCK 2048  // elements per partial of an elementwise sum
 
 // The working set of one matrix: ONE allocation of VLM_WUDI_HEAD + 2 n n + 5 m n doubles
 //   head | G [n][n] | G_i [n][n] (setup scratch) | B | X (buffer 0) | X (buffer 1) | M | V      (the last five [m][n])
@@ -36,52 +35,13 @@ struct wudi_off_t {
   __host__ __device__ size_t X(int buf) const { return X0 + (buf ? mn : 0); }  // (no indexed member: that would live in scratch)
 };
 
-struct wudi_in_tab_t {
-  const float* c[VLM_F64_MAX_BATCH];
-  const float* s[VLM_F64_MAX_BATCH];  // ONE source (prepare walks them) or unused
-};
-struct wudi_out_tab_t {
-  float* p[VLM_F64_MAX_BATCH];
-};
-
-// workgroups (= partials) of an elementwise pass over N elements
-static int wudi_elem_parts(size_t N) {
-  const size_t p = (N + WUDI_PER_BLOCK - 1) / WUDI_PER_BLOCK;
-  return p > WUDI_MAX_PARTS ? WUDI_MAX_PARTS : (int)(p ? p : 1);
-}
-static int wudi_sum_parts(int m, int n) { return wudi_elem_parts((size_t)n * (m > n ? m : n)); }  // the larger of [m][n] and [n][n]
+static int wudi_sum_parts(int m, int n) { return f64_elem_parts((size_t)n * (m > n ? m : n)); }  // the larger of [m][n] and [n][n]
 static int wudi_tiles(int m, int n) { return ((m + F64_TILE - 1) / F64_TILE) * ((n + F64_TILE - 1) / F64_TILE); }
 // per matrix: the partials of an elementwise sum, then two slots of per-tile loss shares (step 1; the latest later step)
 static int wudi_parts(int m, int n) { return wudi_sum_parts(m, n) + 2 * wudi_tiles(m, n); }
 
-// The workgroup's sum of `v` in a fixed order, valid in thread 0.
-__device__ __forceinline__ double wudi_block_sum(double v) {
-  __shared__ double wsum[4];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = __dadd_rn(v, __shfl_down(v, d));
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return __dadd_rn(__dadd_rn(wsum[0], wsum[1]), __dadd_rn(wsum[2], wsum[3]));
-}
-
-// One wave's sum of p[0 .. parts) in a fixed order, valid in lane 0.
-__device__ __forceinline__ double wudi_wave_fold(const double* __restrict__ p, int parts) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < parts; i += 64) v = __dadd_rn(v, p[i]);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = __dadd_rn(v, __shfl_down(v, d));
-  return v;
-}
-
-// head[slot] of matrix b = the sum of its `parts` partials: one wave per matrix.
-__global__ __launch_bounds__(64) void wudi_fold_kernel(const double* __restrict__ partials, int stride, int parts, const f64_tab_t W,
-                                                       int slot) {
-  const double v = wudi_wave_fold(partials + (size_t)blockIdx.x * stride, parts);
-  if (threadIdx.x == 0) W.p[blockIdx.x][slot] = v;
-}
-
 // Source k: tau = W_k - c in fp64 into V; X_0 = 0 + tau (k = 0) or X_0 + tau; the partial of sum tau^2.
-__global__ __launch_bounds__(256) void wudi_tau_kernel(const wudi_in_tab_t in, const f64_tab_t W, int k, int m, int n,
+__global__ __launch_bounds__(256) void wudi_tau_kernel(const f32_in_tab_t in, const f64_tab_t W, int k, int m, int n,
                                                        double* __restrict__ partials, int stride) {
   const int b = blockIdx.y;
   const wudi_off_t off(m, n);
@@ -97,7 +57,7 @@ __global__ __launch_bounds__(256) void wudi_tau_kernel(const wudi_in_tab_t in, c
     X0[e] = __dadd_rn(k ? X0[e] : 0.0, t);
     acc = __dadd_rn(acc, __dmul_rn(t, t));
   }
-  acc = wudi_block_sum(acc);
+  acc = f64_block_sum(acc);
   if (threadIdx.x == 0) partials[(size_t)b * stride + blockIdx.x] = acc;
 }
 
@@ -119,7 +79,7 @@ __global__ __launch_bounds__(256) void wudi_gacc_kernel(const f64_tab_t W, int k
     G[e] = __dadd_rn(k ? G[e] : 0.0, g);
     acc = __dadd_rn(acc, __dmul_rn(g, g));
   }
-  acc = wudi_block_sum(acc);
+  acc = f64_block_sum(acc);
   if (threadIdx.x == 0) partials[(size_t)b * stride + blockIdx.x] = acc;
 }
 
@@ -172,7 +132,7 @@ __global__ __launch_bounds__(256, 4) void wudi_step_kernel(const f64_tab_t W, co
     Xn[e] = __dsub_rn(x, __dmul_rn(p.step, __ddiv_rn(mo, denom)));
     share = __dadd_rn(share, __dmul_rn(x, __dsub_rn(xg, __dmul_rn(2.0, bv))));
   });
-  share = wudi_block_sum(share);
+  share = f64_block_sum(share);
   if (threadIdx.x == 0) {
     const int tiles = gridDim.x * gridDim.y;
     partials[(size_t)blockIdx.z * stride + sum_parts + (size_t)p.slot * tiles + blockIdx.y * gridDim.x + blockIdx.x] = share;
@@ -184,8 +144,8 @@ __global__ __launch_bounds__(256, 4) void wudi_step_kernel(const f64_tab_t W, co
 __global__ __launch_bounds__(64) void wudi_loss_kernel(const double* __restrict__ partials, int stride, int sum_parts, int tiles, int last,
                                                        int S, const f64_tab_t W) {
   const double* __restrict__ p = partials + (size_t)blockIdx.x * stride + sum_parts;
-  const double first = wudi_wave_fold(p, tiles);
-  const double later = wudi_wave_fold(p + (size_t)last * tiles, tiles);
+  const double first = f64_wave_fold(p, tiles);
+  const double later = f64_wave_fold(p + (size_t)last * tiles, tiles);
   if (threadIdx.x == 0) {
     double* __restrict__ head = W.p[blockIdx.x];
     double K = 0.0;
@@ -198,7 +158,7 @@ __global__ __launch_bounds__(64) void wudi_loss_kernel(const double* __restrict_
 
 // dst = fl32(c + lam * X_T): product, sum, ONE rounding to fp32.  A thread reads its elements of c before it writes them: dst may
 // be c, or a source (no source is read here).
-__global__ __launch_bounds__(256) void wudi_apply_kernel(const wudi_in_tab_t in, const wudi_out_tab_t dst, const f64_tab_t W, int m, int n,
+__global__ __launch_bounds__(256) void wudi_apply_kernel(const f32_in_tab_t in, const f32_out_tab_t dst, const f64_tab_t W, int m, int n,
                                                          int buf, double lam) {
   const int b = blockIdx.y;
   const wudi_off_t off(m, n);
@@ -209,37 +169,16 @@ __global__ __launch_bounds__(256) void wudi_apply_kernel(const wudi_in_tab_t in,
   for (size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; e < N; e += (size_t)gridDim.x * 1024) {
     const int cnt = N - e < 4 ? (int)(N - e) : 4;
     float cv[4], o[4];
-    if (cnt == 4) {
-      const float4 t = *reinterpret_cast<const float4*>(c + e);
-      cv[0] = t.x, cv[1] = t.y, cv[2] = t.z, cv[3] = t.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) cv[j] = j < cnt ? c[e + j] : 0.0f;
-    }
+    f32_load4(c, e, cnt, cv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = __double2float_rn(__dadd_rn((double)cv[j], __dmul_rn(lam, j < cnt ? X[e + j] : 0.0)));
-    if (cnt == 4) {
-      *reinterpret_cast<float4*>(out + e) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (j < cnt) out[e + j] = o[j];
-    }
+    f32_store4(out, e, cnt, o);
   }
 }
 
 static int wudi_shape(int m, int n, int count) {
-  if (m <= 0 || n <= 0 || count <= 0 || count > VLM_F64_MAX_BATCH) return VLM_ERR_ARG;
+  if (m <= 0 || n <= 0 || f64_count(count)) return VLM_ERR_ARG;
   return m > 65535 * F64_TILE ? VLM_ERR_ARG : VLM_OK;  // (the tile grid's y; element offsets are size_t throughout)
-}
-
-static int wudi_f32(const float* const* list, int count, const float** out) {
-  if (!list) return VLM_ERR_ARG;
-  for (int i = 0; i < count; ++i) {
-    if (!list[i] || ((uintptr_t)list[i] & 15)) return VLM_ERR_ARG;
-    out[i] = list[i];
-  }
-  return VLM_OK;
 }
 
 extern "C" int vlm_wudi_parts(int m, int n) { return m > 0 && n > 0 ? wudi_parts(m, n) : 0; }
@@ -255,15 +194,15 @@ extern "C" size_t vlm_wudi_state_offset(int m, int n, int iters) {
 extern "C" int vlm_wudi_prepare(const float* const* c_list, const float* const* src_list, int S, int m, int n, double* const* work_list,
                                 double* partials, int count, void* stream) {
   if (wudi_shape(m, n, count) || S < 1 || S > VLM_MERGE_MAX_SRC || !src_list || !partials) return VLM_ERR_ARG;
-  wudi_in_tab_t in;
+  f32_in_tab_t in;
   f64_tab_t W;
-  int rc = wudi_f32(c_list, count, in.c);
-  for (int k = 0; k < S && !rc; ++k) rc = wudi_f32(src_list + (size_t)k * count, count, in.s);  // (checked before anything is launched)
+  int rc = f32_ptrs(c_list, count, in.c);
+  for (int k = 0; k < S && !rc; ++k) rc = f32_ptrs(src_list + (size_t)k * count, count, in.s);  // (checked before anything is launched)
   if (!rc) rc = f64_tab(work_list, count, W);
   if (rc) return rc;
   const wudi_off_t off(m, n);
   const int stride = wudi_parts(m, n);
-  const int parts_mn = wudi_elem_parts((size_t)m * n), parts_nn = wudi_elem_parts((size_t)n * n);
+  const int parts_mn = f64_elem_parts((size_t)m * n), parts_nn = f64_elem_parts((size_t)n * n);
   const void* tau[VLM_F64_MAX_BATCH];
   const double* gi_in[VLM_F64_MAX_BATCH];
   double* gi[VLM_F64_MAX_BATCH];
@@ -276,18 +215,18 @@ extern "C" int vlm_wudi_prepare(const float* const* c_list, const float* const* 
   }
   hipStream_t s = (hipStream_t)stream;
   for (int k = 0; k < S; ++k) {
-    wudi_f32(src_list + (size_t)k * count, count, in.s);
+    f32_ptrs(src_list + (size_t)k * count, count, in.s);
     hipLaunchKernelGGL(wudi_tau_kernel, dim3(parts_mn, count), dim3(256), 0, s, in, W, k, m, n, partials, stride);
     VLM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(wudi_fold_kernel, dim3(count), dim3(64), 0, s, partials, stride, parts_mn, W, WUDI_SQ + k);
-    VLM_CHECK_LAUNCH();
+    rc = f64_fold(partials, stride, parts_mn, W, WUDI_SQ + k, count, s);
+    if (rc) return rc;
     // G_i = tau^T tau, scaled by w_i and added to G; then B (+)= tau G_i, G_i read through its transpose (it is symmetric)
     rc = vlm_gemm_f64_batched(1, 0, n, n, m, 1.0, tau, n, 0, reinterpret_cast<const double* const*>(tau), n, 0.0, gi, n, count, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(wudi_gacc_kernel, dim3(parts_nn, count), dim3(256), 0, s, W, k, m, n, partials, stride);
     VLM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(wudi_fold_kernel, dim3(count), dim3(64), 0, s, partials, stride, parts_nn, W, WUDI_GSQ + k);
-    VLM_CHECK_LAUNCH();
+    rc = f64_fold(partials, stride, parts_nn, W, WUDI_GSQ + k, count, s);
+    if (rc) return rc;
     rc = vlm_gemm_f64_batched(0, 1, m, n, n, 1.0, tau, n, 0, gi_in, n, k ? 1.0 : 0.0, bm, n, count, stream);
     if (rc) return rc;
   }
@@ -312,18 +251,18 @@ extern "C" int vlm_wudi_step(double* const* work_list, int m, int n, int t, doub
 extern "C" int vlm_wudi_finish(double* const* work_list, const float* const* c_list, float* const* dst_list, int S, int m, int n,
                                int iters, double lam, double* partials, int count, void* stream) {
   if (wudi_shape(m, n, count) || S < 1 || S > VLM_MERGE_MAX_SRC || iters < 1 || !dst_list || !partials) return VLM_ERR_ARG;
-  wudi_in_tab_t in;
-  wudi_out_tab_t dst;
+  f32_in_tab_t in;
+  f32_out_tab_t dst;
   f64_tab_t W;
-  int rc = wudi_f32(c_list, count, in.c);
-  if (!rc) rc = wudi_f32(dst_list, count, const_cast<const float**>(dst.p));
+  int rc = f32_ptrs(c_list, count, in.c);
+  if (!rc) rc = f32_ptrs(dst_list, count, dst.p);
   if (!rc) rc = f64_tab(work_list, count, W);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(wudi_loss_kernel, dim3(count), dim3(64), 0, s, partials, wudi_parts(m, n), wudi_sum_parts(m, n), wudi_tiles(m, n),
                      iters == 1 ? 0 : 1, S, W);
   VLM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(wudi_apply_kernel, dim3(wudi_elem_parts((size_t)m * n), count), dim3(256), 0, s, in, dst, W, m, n, iters & 1, lam);
+  hipLaunchKernelGGL(wudi_apply_kernel, dim3(f64_elem_parts((size_t)m * n), count), dim3(256), 0, s, in, dst, W, m, n, iters & 1, lam);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }

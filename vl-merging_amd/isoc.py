@@ -21,9 +21,8 @@ import warnings
 import torch
 
 from . import _lib as L
-from . import merge as M
 from . import ops
-from .regmean import _side_streams
+from .matrix_plan import MatrixPlan, batches, matrix_merge, run_groups, shape_groups
 
 EXTRA_ROUND = 4    # further steps per round for what the schedule left unconverged
 EXTRA_MAX = 32     # and at most this many
@@ -50,53 +49,28 @@ def iso_schedule(l0=1e-6, steps=8):
     return out
 
 
-class IsoPlan:
+class IsoPlan(MatrixPlan):
     """The matrices of an Iso-C merge: add() them, run() enqueues everything and reads the verdicts (the outputs' apply pass is
     enqueued behind that read: run() does not end synchronised).  Matrices are grouped by working shape [rows >= cols] (fc1 and
     the transposed fc2 are one group) and walk the iteration in lock step, every step of a group one launch over all of it (64 at
     a time); independent groups run side by side on side streams.  After run(): self.rows (report()), self.factor(i): the
     device's float64 X of matrix i in working orientation."""
 
+    NAME, KERNELS = "an Iso-C", "Iso-C"
+
     def __init__(self, device, l0=1e-6, steps=8):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.VlmError("the Iso-C kernels run on the GPU only (got device %s)" % (device,))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(device)
         if not 1 <= steps <= L.ISO_MAX_STEPS - EXTRA_MAX:
             raise ValueError("Iso-C takes 1 .. %d scheduled steps, got %r" % (L.ISO_MAX_STEPS - EXTRA_MAX, steps))
         self.schedule = iso_schedule(l0, steps)
-        self.jobs = []   # (name, central, sources, out, lam)
-        self.keep = []
-        self.rows = None
         self._where = {}
-
-    _dev = M._Plan._dev   # float32, on the device, contiguous, 16-byte aligned: staged and kept alive where it is not
-
-    def add(self, srcs, base, lam=1.0, out=None, name=None):
-        """One output matrix.  `out` may be `base` or one of `srcs` (they are read before it is written) or any tensor that meets
-        none of them."""
-        if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
-            raise L.VlmError("an Iso-C job takes 1 .. %d sources, got %d" % (L.MERGE_MAX_SRC, len(srcs)))
-        base = self._dev(base)
-        srcs = [self._dev(s) for s in srcs]
-        if base.dim() != 2 or base.numel() == 0 or any(s.shape != base.shape for s in srcs):
-            raise L.VlmError("an Iso-C job takes non-empty matrices of one shape, got %s" % ([tuple(t.shape) for t in [base] + srcs],))
-        if out is None:
-            out = torch.empty_like(base)
-        elif out.shape != base.shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() \
-                or (out.data_ptr() & 15):
-            raise L.VlmError("an Iso-C output must be a contiguous, 16-byte aligned float32 tensor of the sources' shape on %s" % self.device)
-        self.jobs.append((name, base, srcs, out, float(lam)))
-        return out
 
     # ------------------------------------------------------------------------------------------------ the device side
     def _step(self, g, idx, k, abc):
         """Step k with coefficients abc for the matrices idx of group g, 64 at a time."""
         a, b, c = abc
         rows, cols = g["shape"]
-        for i0 in range(0, len(idx), ops.F64_MAX_BATCH):
-            part = idx[i0:i0 + ops.F64_MAX_BATCH]
+        for _, part in batches(idx):
             work, zs = [g["work"][i] for i in part], [g["z"][i] for i in part]
             ys = [g["y"][i] for i in part]
             ops.iso_gram(work, rows, cols, zs, c, first=k == 0)
@@ -109,15 +83,12 @@ class IsoPlan:
     def _finish(self, g, idx, phases):
         """The phases of ops.iso_finish for the matrices idx of group g: one call per original shape (the two orientations of a
         group), lam and 64 matrices."""
-        by = {}
-        for i in idx:
+        def key(i):
             job = self.jobs[g["jobs"][i]]
-            by.setdefault((tuple(job[1].shape), job[4]), []).append(i)
-        for (shape, lam), ids in sorted(by.items()):
-            for i0 in range(0, len(ids), ops.F64_MAX_BATCH):
-                part = ids[i0:i0 + ops.F64_MAX_BATCH]
-                js = [self.jobs[g["jobs"][i]] for i in part]
-                ops.iso_finish([g["work"][i] for i in part], [j[1] for j in js], [j[3] for j in js], lam, g["partials"], phases)
+            return tuple(job[1].shape), job[4]
+        for (shape, lam), part in batches(idx, key):
+            js = [self.jobs[g["jobs"][i]] for i in part]
+            ops.iso_finish([g["work"][i] for i in part], [j[1] for j in js], [j[3] for j in js], lam, g["partials"], phases)
 
     def _allocate(self, g):
         """The group's buffers, on the CALLER's stream: the group's side stream works in them between its wait for the caller's
@@ -138,15 +109,12 @@ class IsoPlan:
 
     def _delta(self, g):
         """D of every matrix of the group: one call per original shape, source count and 64 matrices."""
-        by = {}
-        for i, j in enumerate(g["jobs"]):
-            _, base, srcs, _, _ = self.jobs[j]
-            by.setdefault((tuple(base.shape), len(srcs)), []).append(i)
-        for (shape, S), ids in sorted(by.items()):
-            for i0 in range(0, len(ids), ops.F64_MAX_BATCH):
-                part = ids[i0:i0 + ops.F64_MAX_BATCH]
-                js = [self.jobs[g["jobs"][i]] for i in part]
-                ops.iso_delta([j[1] for j in js], [[j[2][k] for j in js] for k in range(S)], [g["work"][i] for i in part], g["partials"])
+        def key(i):
+            job = self.jobs[g["jobs"][i]]
+            return tuple(job[1].shape), len(job[2])
+        for (shape, S), part in batches(range(len(g["jobs"])), key):
+            js = [self.jobs[g["jobs"][i]] for i in part]
+            ops.iso_delta([j[1] for j in js], [[j[2][k] for j in js] for k in range(S)], [g["work"][i] for i in part], g["partials"])
 
     def _heads(self, groups):
         """Every head and Cholesky verdict of the groups in ONE blocking copy: the merge's one synchronisation (and one more per
@@ -170,29 +138,20 @@ class IsoPlan:
         if not self.jobs:
             self.rows = []
             return self
-        groups = {}
-        for j, (_, base, _, _, _) in enumerate(self.jobs):
-            m, n = base.shape
-            groups.setdefault((max(m, n), min(m, n)), []).append(j)
-        groups = [dict(shape=key, jobs=js) for key, js in sorted(groups.items(), key=lambda kv: -kv[0][0] * kv[0][1] ** 2 * len(kv[1]))]
+        groups = shape_groups(len(self.jobs), lambda j: (max(self.jobs[j][1].shape), min(self.jobs[j][1].shape)),
+                              lambda shape: shape[0] * shape[1] ** 2)
         K = len(self.schedule)
-        main = torch.cuda.current_stream(self.device)
-        side = _side_streams(self.device, len(groups) - 1)
+
+        def scheduled(g):
+            self._delta(g)
+            every = list(range(len(g["jobs"])))
+            for k, abc in enumerate(self.schedule):
+                self._step(g, every, k, abc)
+            self._finish(g, every, L.ISO_PHASE_NUCLEAR)
         with torch.cuda.device(self.device):
             for g in groups:
                 self._allocate(g)
-            for n_, g in enumerate(groups):  # the largest group stays on the caller's stream
-                st = main if n_ == 0 else side[n_ - 1]
-                if st is not main:
-                    st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    self._delta(g)
-                    every = list(range(len(g["jobs"])))
-                    for k, abc in enumerate(self.schedule):
-                        self._step(g, every, k, abc)
-                    self._finish(g, every, L.ISO_PHASE_NUCLEAR)
-            for st in side[:len(groups) - 1]:
-                main.wait_stream(st)
+            run_groups(self.device, groups, scheduled)
             # A matrix's output is written ONCE, after its verdict: the apply pass reads the central tensor, which the output may be.
             # Before the read only <X, D> is made, so the common case is still one synchronisation, with the apply pass enqueued behind it.
             heads = self._heads(groups)
@@ -237,11 +196,6 @@ class IsoPlan:
     def _converged(head, k, r):
         return math.sqrt(head[1 + k]) <= STEP_TOL * math.sqrt(r)   # head[2 + (k - 1)]: the last step taken
 
-    def report(self):
-        if self.rows is None:
-            raise L.VlmError("IsoPlan.report() needs a plan that has run")
-        return [dict(r) for r in self.rows]
-
     def factor(self, j):
         """The device's float64 X of job j, [rows >= cols] (the transpose of the polar factor when the matrix is wide)."""
         g, i = self._where[j]
@@ -264,29 +218,8 @@ def isoc_merge(state_dict, config, central_weight=None, lam=None, device="cuda",
     has jobs; `report_out` receives one row per matrix (dst, n, shape, transposed, S, fro, nuclear, sigma_mean, steps, last_step,
     converged); `factors_out[dst]` the device's float64 X in working orientation.  A matrix that has not converged after the extra
     rounds is written as it stands, reported with converged = False, and warned about."""
-    if lam is None:
-        lam = config["sum_lambda"]
     iso = IsoPlan(device, l0=l0, steps=steps)
-    plan = M.MergePlan(iso.device)
-    out = M._passthrough(state_dict)
-    central = M._central(central_weight, config)
-    for dst, mods, srcs, through in M._walk(state_dict, config, central):
-        if srcs is None:
-            out[dst] = through
-        elif len(mods) == 1:
-            out[dst] = plan.add(L.MERGE_TASKVEC, M._tensors(srcs), [1], base=central[dst])
-        elif central[dst].dim() == 2:
-            out[dst] = iso.add(M._tensors(srcs), central[dst], lam=lam, name=dst)
-        else:
-            out[dst] = plan.add(L.MERGE_TASKVEC, M._tensors(srcs), [lam / len(srcs)] * len(srcs), base=central[dst])
-    if plan.jobs:
-        plan.run()   # (enqueued first: the streaming pass runs under the iteration's launch chain)
-    if iso.jobs:
-        iso.run()
-    if plan_out is not None:
-        plan_out.extend(p for p in (iso, plan) if p.jobs)
-    if report_out is not None:
-        report_out.extend(iso.report() if iso.jobs else [])
+    out = matrix_merge(iso, state_dict, config, central_weight, lam, plan_out, report_out)
     if factors_out is not None:
         for j, job in enumerate(iso.jobs):
             factors_out[job[0]] = iso.factor(j)

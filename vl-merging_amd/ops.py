@@ -846,19 +846,30 @@ def solve_spd_right_(rhs, chol):
     return rhs
 
 
-def _iso_work(work, m, n, who):
-    """The working sets of an Iso-C call (include/vlm_hip.h): contiguous float64 [ISO_HEAD + 3 m n] each, at most F64_MAX_BATCH."""
-    if not 1 <= len(work) <= F64_MAX_BATCH or m < 1 or n < 1:
-        raise L.VlmError("%s: 1 .. %d matrices of a positive shape" % (who, F64_MAX_BATCH))
+def _f64_work(work, m, n, size, who, shape_ok=True, shape="a positive shape", what=None):
+    """The working sets of a per-matrix float64 call (include/vlm_hip.h): at most F64_MAX_BATCH contiguous float64 [size] tensors,
+    one per [m, n] matrix."""
+    if not 1 <= len(work) <= F64_MAX_BATCH or m < 1 or n < 1 or not shape_ok:
+        raise L.VlmError("%s: 1 .. %d matrices of %s" % (who, F64_MAX_BATCH, shape))
     for w in work:
-        if w.dtype != F64 or w.dim() != 1 or w.numel() != L.ISO_HEAD + 3 * m * n or not w.is_contiguous():
-            raise L.VlmError("%s: a working set is a contiguous float64 [%d + 3 * %d * %d] tensor" % (who, L.ISO_HEAD, m, n))
+        if w.dtype != F64 or w.dim() != 1 or w.numel() != size or not w.is_contiguous():
+            raise L.VlmError("%s: a working set is a contiguous float64 %s" % (who, what or "[%d] tensor for a [%d, %d] matrix" % (size, m, n)))
 
 
-def _iso_f32(ts, m, n, who):
+def _iso_work(work, m, n, who):
+    _f64_work(work, m, n, L.ISO_HEAD + 3 * m * n, who, what="[%d + 3 * %d * %d] tensor" % (L.ISO_HEAD, m, n))
+
+
+def _f32_matrices(ts, m, n, who):
+    """fp32 matrices of one shape, contiguous and 16-byte aligned: what the float64 merge kernels read and write four at a time."""
     for t in ts:
         if t.dtype != F32 or tuple(t.shape) != (m, n) or not t.is_contiguous() or (t.data_ptr() & 15):
             raise L.VlmError("%s: contiguous, 16-byte aligned float32 [%d, %d] tensors" % (who, m, n))
+
+
+def _f64_partials(partials, need, who, made_by):
+    if partials.dtype != F64 or not partials.is_contiguous() or partials.numel() < need:
+        raise L.VlmError("%s: partials too small (%s)" % (who, made_by))
 
 
 def iso_partials(m, n, count, device):
@@ -867,8 +878,7 @@ def iso_partials(m, n, count, device):
 
 
 def _iso_scratch(partials, m, n, count, who):
-    if partials.dtype != F64 or not partials.is_contiguous() or partials.numel() < count * L.get_lib().vlm_iso_parts(m, n):
-        raise L.VlmError(who + ": partials too small (iso_partials)")
+    _f64_partials(partials, count * L.get_lib().vlm_iso_parts(m, n), who, "iso_partials")
 
 
 def iso_delta(base, srcs, work, partials):
@@ -879,7 +889,7 @@ def iso_delta(base, srcs, work, partials):
     _iso_work(work, m, n, "iso_delta")
     if not 1 <= len(srcs) <= L.MERGE_MAX_SRC or any(len(s) != len(base) for s in srcs) or len(work) != len(base):
         raise L.VlmError("iso_delta: 1 .. %d source lists as long as the list of central tensors" % L.MERGE_MAX_SRC)
-    _iso_f32(list(base) + [t for s in srcs for t in s], m, n, "iso_delta")
+    _f32_matrices(list(base) + [t for s in srcs for t in s], m, n, "iso_delta")
     _iso_scratch(partials, m, n, len(base), "iso_delta")
     L.check(L.get_lib().vlm_iso_delta(_ptr_list(base), _ptr_list([t for s in srcs for t in s]), len(srcs), m, n, _ptr_list(work),
                                       L.ptr(partials), len(base), L.stream_ptr()), "vlm_iso_delta")
@@ -921,7 +931,7 @@ def iso_finish(work, base, dst, lam, partials, phases=L.ISO_PHASE_NUCLEAR | L.IS
     _iso_work(work, m, n, "iso_finish")
     if len(base) != len(work) or len(dst) != len(work):
         raise L.VlmError("iso_finish: one central tensor and one output per working set")
-    _iso_f32(list(base) + list(dst), m, n, "iso_finish")
+    _f32_matrices(list(base) + list(dst), m, n, "iso_finish")
     _iso_scratch(partials, m, n, len(work), "iso_finish")
     L.check(L.get_lib().vlm_iso_finish(_ptr_list(work), _ptr_list(base), _ptr_list(dst), m, n, float(lam), L.ptr(partials), len(work),
                                        phases, L.stream_ptr()), "vlm_iso_finish")
@@ -945,14 +955,8 @@ def wudi_state(work, m, n, iters):
 
 
 def _wudi_work(work, m, n, partials, who):
-    if not 1 <= len(work) <= F64_MAX_BATCH or m < 1 or n < 1:
-        raise L.VlmError("%s: 1 .. %d matrices of a positive shape" % (who, F64_MAX_BATCH))
-    size = wudi_work_doubles(m, n)
-    for w in work:
-        if w.dtype != F64 or w.dim() != 1 or w.numel() != size or not w.is_contiguous():
-            raise L.VlmError("%s: a working set is a contiguous float64 [%d] tensor for a [%d, %d] matrix" % (who, size, m, n))
-    if partials.dtype != F64 or not partials.is_contiguous() or partials.numel() < len(work) * L.get_lib().vlm_wudi_parts(m, n):
-        raise L.VlmError(who + ": partials too small (wudi_partials)")
+    _f64_work(work, m, n, wudi_work_doubles(m, n), who)
+    _f64_partials(partials, len(work) * L.get_lib().vlm_wudi_parts(m, n), who, "wudi_partials")
 
 
 def wudi_prepare(base, srcs, work, partials):
@@ -963,7 +967,7 @@ def wudi_prepare(base, srcs, work, partials):
     _wudi_work(work, m, n, partials, "wudi_prepare")
     if not 1 <= len(srcs) <= L.MERGE_MAX_SRC or any(len(s) != len(base) for s in srcs) or len(work) != len(base):
         raise L.VlmError("wudi_prepare: 1 .. %d source lists as long as the list of central tensors" % L.MERGE_MAX_SRC)
-    _iso_f32(list(base) + [t for s in srcs for t in s], m, n, "wudi_prepare")
+    _f32_matrices(list(base) + [t for s in srcs for t in s], m, n, "wudi_prepare")
     L.check(L.get_lib().vlm_wudi_prepare(_ptr_list(base), _ptr_list([t for s in srcs for t in s]), len(srcs), m, n, _ptr_list(work),
                                          L.ptr(partials), len(base), L.stream_ptr()), "vlm_wudi_prepare")
     return work
@@ -989,7 +993,7 @@ def wudi_finish(work, base, dst, S, iters, lam, partials):
     _wudi_work(work, m, n, partials, "wudi_finish")
     if len(base) != len(work) or len(dst) != len(work) or not 1 <= S <= L.MERGE_MAX_SRC or iters < 1:
         raise L.VlmError("wudi_finish: one central tensor and one output per working set, 1 .. %d sources, iters >= 1" % L.MERGE_MAX_SRC)
-    _iso_f32(list(base) + list(dst), m, n, "wudi_finish")
+    _f32_matrices(list(base) + list(dst), m, n, "wudi_finish")
     L.check(L.get_lib().vlm_wudi_finish(_ptr_list(work), _ptr_list(base), _ptr_list(dst), S, m, n, iters, float(lam), L.ptr(partials),
                                         len(work), L.stream_ptr()), "vlm_wudi_finish")
     return dst
@@ -1009,14 +1013,9 @@ def svd_views(work, p, q):
 
 
 def _svd_work(work, p, q, who):
-    if not 1 <= len(work) <= F64_MAX_BATCH or p < 1 or q < p:
-        raise L.VlmError("%s: 1 .. %d matrices of a working shape [p <= q]" % (who, F64_MAX_BATCH))
+    _f64_work(work, p, q, svd_work_doubles(p, q), who, shape_ok=q >= p, shape="a working shape [p <= q]")
     if q > L.SVD_MAX_Q:
         raise L.VlmError("%s: a row of %d doubles does not fit a workgroup's registers (at most %d)" % (who, q, L.SVD_MAX_Q))
-    size = svd_work_doubles(p, q)
-    for w in work:
-        if w.dtype != F64 or w.dim() != 1 or w.numel() != size or not w.is_contiguous():
-            raise L.VlmError("%s: a working set is a contiguous float64 [%d] tensor for a [%d, %d] matrix" % (who, size, p, q))
 
 
 def svd_reset(work, p, q):
@@ -1057,7 +1056,7 @@ def tsv_delta(base, srcs, work):
     _svd_work(work, min(m, n), max(m, n), "tsv_delta")
     if len(srcs) != len(base) or len(work) != len(base):
         raise L.VlmError("tsv_delta: one source and one working set per central tensor")
-    _iso_f32(list(base) + list(srcs), m, n, "tsv_delta")
+    _f32_matrices(list(base) + list(srcs), m, n, "tsv_delta")
     L.check(L.get_lib().vlm_tsv_delta(_ptr_list(base), _ptr_list(srcs), m, n, _ptr_list(work), len(base), L.stream_ptr()), "vlm_tsv_delta")
     return work
 
@@ -1091,7 +1090,7 @@ def tsv_apply(pu, pv, scat, base, dst, t, kS, lam):
     L.require_cuda(*pu, *pv, *scat, *base, *dst, *t)
     if not 1 <= len(base) <= F64_MAX_BATCH or not (len(pu) == len(pv) == len(scat) == len(dst) == len(t) == len(base)) or not 0 <= kS <= p:
         raise L.VlmError("tsv_apply: 1 .. %d matrices, one entry per list and matrix, 0 <= kS <= min(m, n)" % F64_MAX_BATCH)
-    _iso_f32(list(base) + list(dst), m, n, "tsv_apply")
+    _f32_matrices(list(base) + list(dst), m, n, "tsv_apply")
     for a, b, s, x in zip(pu, pv, scat, t):
         if any(y.dtype != F64 or not y.is_contiguous() for y in (a, b, s, x)) or tuple(x.shape) != (p, q) \
                 or (kS and (tuple(a.shape) != (kS, p) or tuple(b.shape) != (kS, q) or s.numel() != kS)):

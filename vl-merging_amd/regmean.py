@@ -15,21 +15,12 @@ import torch
 from . import _lib as L
 from . import merge as M
 from . import ops
+from .matrix_plan import run_groups
 
 
 def scale_gram(G, alpha):
     """:388-392"""
     return alpha * G + (1 - alpha) * torch.diag_embed(torch.diag(G))
-
-
-_SIDE = {}
-
-
-def _side_streams(device, n):
-    pool = _SIDE.setdefault(torch.device(device).index, [])
-    while len(pool) < n:
-        pool.append(torch.cuda.Stream(device=device))
-    return pool
 
 
 class _Solves:
@@ -73,30 +64,21 @@ class _Solves:
         self.slot = {j: k for k, j in enumerate(order)}
         # One stream per shape group (round 5): a group's factorisation + solve is a chain of ~300 small dependent launches (a block
         # factor is ONE wave per matrix, a panel solve a few hundred workgroups), and the groups are independent -- side by side the
-        # 768-wide groups hide under the 3072-wide one.  The largest group stays on the caller's stream.
-        main = torch.cuda.current_stream(self.device)
+        # 768-wide groups hide under the 3072-wide one.  The largest group stays on the caller's stream (matrix_plan.run_groups).
         keys = sorted(groups, key=lambda k: -k[0] * k[0] * len(groups[k]))
         starts, k0 = {}, 0
         for key in sorted(groups):
             starts[key] = k0
             k0 += len(groups[key])
-        side = _side_streams(self.device, len(keys) - 1)
-        for n_, key in enumerate(keys):
+
+        def enqueue(key):
             idx = groups[key]
-            st = main if n_ == 0 else side[n_ - 1]
-            if st is not main:
-                if small_ready is not None and key[0] <= 1024:
-                    st.wait_event(small_ready)
-                else:
-                    st.wait_stream(main)
-            with torch.cuda.stream(st):
-                for i in idx:  # (on the group's own stream: before its in-place factorisation, after its products)
-                    self.jobs[i][3], self.jobs[i][4] = self.jobs[i][2].clone(), self.jobs[i][1].clone()
-                dens = [self.jobs[i][2] for i in idx]
-                ops.cholesky_batched_(dens, self.status[starts[key]:starts[key] + len(idx)])
-                ops.solve_spd_right_batched_([self.jobs[i][1] for i in idx], dens)
-        for st in side[:len(keys) - 1]:
-            main.wait_stream(st)
+            for i in idx:  # (on the group's own stream: before its in-place factorisation, after its products)
+                self.jobs[i][3], self.jobs[i][4] = self.jobs[i][2].clone(), self.jobs[i][1].clone()
+            dens = [self.jobs[i][2] for i in idx]
+            ops.cholesky_batched_(dens, self.status[starts[key]:starts[key] + len(idx)])
+            ops.solve_spd_right_batched_([self.jobs[i][1] for i in idx], dens)
+        run_groups(self.device, keys, enqueue, ready=lambda key: small_ready if key[0] <= 1024 else None)
 
     def collect(self, out):
         """Read the verdicts (ONE synchronisation for all solves) and replace what has no Cholesky factor."""

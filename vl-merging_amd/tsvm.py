@@ -22,9 +22,8 @@ import warnings
 import torch
 
 from . import _lib as L
-from . import merge as M
 from . import ops
-from .regmean import _side_streams
+from .matrix_plan import MatrixPlan, batches, cuda_device, matrix_merge, report, run_groups, shape_groups
 
 SWEEPS = 18        # scheduled: the base-size merge needs at most 16 (docs/experiments.md, "TSV-M"); the restated sweep 15 at 768 x 768
 EXTRA_ROUND = 2    # further sweeps per round for what the schedule left rotating
@@ -40,11 +39,7 @@ class SvdPlan:
     `transposed`)."""
 
     def __init__(self, device, sweeps=SWEEPS, floor_rel=0.0):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.VlmError("the SVD kernels run on the GPU only (got device %s)" % (device,))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = cuda_device(device, "SVD")
         if int(sweeps) != sweeps or not 1 <= sweeps <= L.SVD_MAX_SWEEPS:
             raise ValueError("an SVD plan schedules 1 .. %d sweeps, got %r" % (L.SVD_MAX_SWEEPS, sweeps))
         if not 0.0 <= floor_rel < 1.0:
@@ -73,8 +68,8 @@ class SvdPlan:
 
     def _sweep(self, g, idx, sweep):
         p, q = g["shape"]
-        for i0 in range(0, len(idx), ops.F64_MAX_BATCH):
-            ops.svd_sweep([self.sets[j][0] for j in idx[i0:i0 + ops.F64_MAX_BATCH]], p, q, sweep)
+        for _, part in batches(idx):
+            ops.svd_sweep([self.sets[j][0] for j in part], p, q, sweep)
             self.launches += L.get_lib().vlm_svd_steps(p)
 
     def _heads(self):
@@ -95,26 +90,17 @@ class SvdPlan:
         if not self.sets:
             self.rows = []
             return self
-        groups = {}
-        for j, (_, p, q, _) in enumerate(self.sets):
-            groups.setdefault((p, q), []).append(j)
-        groups = [dict(shape=key, jobs=js) for key, js in sorted(groups.items(), key=lambda kv: -kv[0][0] ** 2 * kv[0][1] * len(kv[1]))]
-        main = torch.cuda.current_stream(self.device)
-        side = _side_streams(self.device, len(groups) - 1)
+        groups = shape_groups(len(self.sets), lambda j: self.sets[j][1:3], lambda shape: shape[0] ** 2 * shape[1])
+
+        def scheduled(g):
+            p, q = g["shape"]
+            for _, part in batches(g["jobs"]):
+                ops.svd_reset([self.sets[j][0] for j in part], p, q)
+                self.launches += 1
+            for sweep in range(self.sweeps if p > 1 else 0):
+                self._sweep(g, g["jobs"], sweep)
         with torch.cuda.device(self.device):
-            for n_, g in enumerate(groups):  # the largest group stays on the caller's stream
-                st = main if n_ == 0 else side[n_ - 1]
-                if st is not main:
-                    st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    p, q = g["shape"]
-                    for i0 in range(0, len(g["jobs"]), ops.F64_MAX_BATCH):
-                        ops.svd_reset([self.sets[j][0] for j in g["jobs"][i0:i0 + ops.F64_MAX_BATCH]], p, q)
-                        self.launches += 1
-                    for sweep in range(self.sweeps if p > 1 else 0):
-                        self._sweep(g, g["jobs"], sweep)
-            for st in side[:len(groups) - 1]:
-                main.wait_stream(st)
+            run_groups(self.device, groups, scheduled)
             ran = self.sweeps
             heads = self._heads()   # the one synchronisation (and one more per extra round)
 
@@ -131,8 +117,8 @@ class SvdPlan:
                 todo = rotating()
             for g in groups:
                 p, q = g["shape"]
-                for i0 in range(0, len(g["jobs"]), ops.F64_MAX_BATCH):
-                    ops.svd_finish([self.sets[j][0] for j in g["jobs"][i0:i0 + ops.F64_MAX_BATCH]], p, q, self.floor_rel)
+                for _, part in batches(g["jobs"]):
+                    ops.svd_finish([self.sets[j][0] for j in part], p, q, self.floor_rel)
                     self.launches += 3
         rows = []
         for j, (_, p, q, transposed) in enumerate(self.sets):
@@ -146,10 +132,7 @@ class SvdPlan:
         self.groups = groups
         return self
 
-    def report(self):
-        if self.rows is None:
-            raise L.VlmError("SvdPlan.report() needs a plan that has run")
-        return [dict(r, rotations=list(r["rotations"]), off=list(r["off"])) for r in self.rows]
+    report = report
 
     def _view(self, j, which):
         work, p, q, _ = self.sets[j]
@@ -174,55 +157,23 @@ class SvdPlan:
         return self._view(j, 5)
 
 
-class TsvPlan:
+class TsvPlan(MatrixPlan):
     """The matrices of a TSV-M merge: add() them, run() takes the SVDs of every task vector in one SvdPlan, gathers Ucat^T and
     Vcat^T, takes their SVDs in a second SvdPlan, and enqueues the polar products and the outputs (run() does not end
     synchronised).  After run(): self.rows (report()), self.task_vector(j): the device's float64 merged task vector of matrix j in
     the tensor's own orientation."""
 
+    NAME, KERNELS = "a TSV-M", "SVD"
+
     def __init__(self, device, sweeps=SWEEPS):
-        self.svd = [SvdPlan(device, sweeps), SvdPlan(device, sweeps, floor_rel=POLAR_FLOOR)]
-        self.device = self.svd[0].device
-        self.jobs = []   # (name, central, sources, out, lam)
-        self.keep = []
-        self.rows = None
+        super().__init__(device)
+        self.svd = [SvdPlan(self.device, sweeps), SvdPlan(self.device, sweeps, floor_rel=POLAR_FLOOR)]
         self.launches = 0   # kernel launches run() issued through the library, the SVD plans' included
         self._t = {}
 
-    _dev = M._Plan._dev   # float32, on the device, contiguous, 16-byte aligned: staged and kept alive where it is not
-
-    def add(self, srcs, base, lam=1.0, out=None, name=None):
-        """One output matrix.  `out` may be `base` or one of `srcs` (they are read before it is written) or any tensor that meets
-        none of them."""
-        if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
-            raise L.VlmError("a TSV-M job takes 1 .. %d sources, got %d" % (L.MERGE_MAX_SRC, len(srcs)))
-        base = self._dev(base)
-        srcs = [self._dev(s) for s in srcs]
-        if base.dim() != 2 or base.numel() == 0 or any(s.shape != base.shape for s in srcs):
-            raise L.VlmError("a TSV-M job takes non-empty matrices of one shape, got %s" % ([tuple(t.shape) for t in [base] + srcs],))
-        if max(base.shape) > L.SVD_MAX_Q:
-            raise L.VlmError("the Jacobi SVD holds rows of at most %d doubles, got a %s matrix" % (L.SVD_MAX_Q, tuple(base.shape)))
-        if out is None:
-            out = torch.empty_like(base)
-        elif out.shape != base.shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() \
-                or (out.data_ptr() & 15):
-            raise L.VlmError("a TSV-M output must be a contiguous, 16-byte aligned float32 tensor of the sources' shape on %s" % self.device)
-        self.jobs.append((name, base, srcs, out, float(lam)))
-        return out
-
-    @staticmethod
-    def _chunks(ids):
-        for i0 in range(0, len(ids), ops.F64_MAX_BATCH):
-            yield ids[i0:i0 + ops.F64_MAX_BATCH]
-
-    def _by(self, key, ids=None):
-        """The jobs `ids` grouped by key(j), 64 at a time, in a fixed order."""
-        by = {}
-        for j in (range(len(self.jobs)) if ids is None else ids):
-            by.setdefault(key(j), []).append(j)
-        for k_, js in sorted(by.items()):
-            for part in self._chunks(js):
-                yield k_, part
+    def _check_shape(self, shape):
+        if max(shape) > L.SVD_MAX_Q:
+            raise L.VlmError("the Jacobi SVD holds rows of at most %d doubles, got a %s matrix" % (L.SVD_MAX_Q, tuple(shape)))
 
     def run(self):
         if not self.jobs:
@@ -243,7 +194,7 @@ class TsvPlan:
                     sets[j] = [buf[at + i] for i in range(dims[j]["S"])]
                     at += dims[j]["S"]
             for i in range(L.MERGE_MAX_SRC):
-                for _, part in self._by(lambda j: tuple(jobs[j][1].shape), [j for j in live if dims[j]["S"] > i]):
+                for _, part in batches([j for j in live if dims[j]["S"] > i], lambda j: tuple(jobs[j][1].shape)):
                     ops.tsv_delta([jobs[j][1] for j in part], [jobs[j][2][i] for j in part], [sets[j][i] for j in part])
                     self.launches += 1
             for j in live:
@@ -257,7 +208,7 @@ class TsvPlan:
                 sb = torch.empty(len(js), kS, **f64)
                 for i, j in enumerate(js):
                     cat[j], scat[j] = (ub[i], vb[i]), sb[i]
-            for (p, q, S, k), part in self._by(lambda j: (dims[j]["p"], dims[j]["q"], dims[j]["S"], dims[j]["k"]), live):
+            for (p, q, S, k), part in batches(live, lambda j: (dims[j]["p"], dims[j]["q"], dims[j]["S"], dims[j]["k"])):
                 src = [[sets[j][i] for j in part] for i in range(S)]
                 ops.tsv_gather(src, p, q, k, 0, [cat[j][0] for j in part])
                 ops.tsv_gather(src, p, q, k, 1, [cat[j][1] for j in part], [scat[j] for j in part])
@@ -271,14 +222,14 @@ class TsvPlan:
             # ---- the transposed polar factors R^T (unit rows), T = PU^T diag(scat) PV and the outputs
             pol = {}
             for side in (0, 1):
-                for (kS, ln), part in self._by(lambda j: (dims[j]["k"] * dims[j]["S"], dims[j]["q" if side else "p"]), live):
+                for (kS, ln), part in batches(live, lambda j: (dims[j]["k"] * dims[j]["S"], dims[j]["q" if side else "p"])):
                     outb = torch.empty(len(part), kS, ln, **f64)
                     for i, j in enumerate(part):
                         pol.setdefault(j, [None, None])[side] = outb[i]
                     ops.gemm_f64_batched([self.svd[1].rt(second[j][side]) for j in part], [self.svd[1].vt(second[j][side]) for j in part],
                                          [pol[j][side] for j in part], ta=True)
                     self.launches += 1
-            for (shape, kS, lam), part in self._by(lambda j: (tuple(jobs[j][1].shape), dims[j]["k"] * dims[j]["S"], jobs[j][4])):
+            for (shape, kS, lam), part in batches(range(len(jobs)), lambda j: (tuple(jobs[j][1].shape), dims[j]["k"] * dims[j]["S"], jobs[j][4])):
                 tb = torch.empty(len(part), min(shape), max(shape), **f64)
                 for i, j in enumerate(part):
                     self._t[j] = tb[i]
@@ -334,12 +285,6 @@ class TsvPlan:
         m, n = base.shape
         return dict(m=m, n=n, p=min(m, n), q=max(m, n), S=len(srcs), k=min(m, n) // len(srcs))
 
-    def report(self):
-        if self.rows is None:
-            raise L.VlmError("TsvPlan.report() needs a plan that has run")
-        import copy
-        return copy.deepcopy(self.rows)
-
     def task_vector(self, j):
         """The device's float64 merged task vector of job j, [m, n] as the tensor is stored (a transposed view when m > n)."""
         m, n = self.jobs[j][1].shape
@@ -354,27 +299,4 @@ def tsvm_merge(state_dict, config, central_weight=None, lam=None, device="cuda",
     V}: every SVD taken), s_max, s_kept_min, s_dropped_max (the gap at the cut) and energy_kept per source, dropped ({U, V}: polar
     directions below 2^-40 of the largest).  An SVD that still rotates after VLM_SVD_MAX_SWEEPS sweeps is used as it stands,
     reported with converged = False, and warned about."""
-    if lam is None:
-        lam = config["sum_lambda"]
-    tsv = TsvPlan(device)
-    plan = M.MergePlan(tsv.device)
-    out = M._passthrough(state_dict)
-    central = M._central(central_weight, config)
-    for dst, mods, srcs, through in M._walk(state_dict, config, central):
-        if srcs is None:
-            out[dst] = through
-        elif len(mods) == 1:
-            out[dst] = plan.add(L.MERGE_TASKVEC, M._tensors(srcs), [1], base=central[dst])
-        elif central[dst].dim() == 2:
-            out[dst] = tsv.add(M._tensors(srcs), central[dst], lam=lam, name=dst)
-        else:
-            out[dst] = plan.add(L.MERGE_TASKVEC, M._tensors(srcs), [lam / len(srcs)] * len(srcs), base=central[dst])
-    if plan.jobs:
-        plan.run()   # (enqueued first: the streaming pass runs under the sweeps' launch chain)
-    if tsv.jobs:
-        tsv.run()
-    if plan_out is not None:
-        plan_out.extend(p for p in (tsv, plan) if p.jobs)
-    if report_out is not None:
-        report_out.extend(tsv.report() if tsv.jobs else [])
-    return out
+    return matrix_merge(TsvPlan(device), state_dict, config, central_weight, lam, plan_out, report_out)

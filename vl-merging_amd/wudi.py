@@ -20,9 +20,8 @@ import math
 import torch
 
 from . import _lib as L
-from . import merge as M
 from . import ops
-from .regmean import _side_streams
+from .matrix_plan import MatrixPlan, matrix_merge, run_groups, shape_groups
 
 BETA1, BETA2, EPS = 0.9, 0.999, 1e-8   # torch.optim.Adam's defaults, as the paper's code runs it
 
@@ -32,47 +31,23 @@ def adam_scalars(t, lr, beta1=BETA1, beta2=BETA2):
     return lr / (1.0 - beta1 ** t), math.sqrt(1.0 - beta2 ** t)
 
 
-class WudiPlan:
+class WudiPlan(MatrixPlan):
     """The matrices of a WUDI merge: add() them, run() enqueues everything -- the setup, `iters` step launches per lock-step group,
     the outputs -- and synchronises ONCE at its end, reading the heads for report().  Matrices are grouped by their exact shape
     [m, n] (G is [n, n]: orientation matters) and walk the steps in lock step, a step of a group one launch over all of it (64 at
     a time); independent groups run side by side on side streams.  After run(): self.rows (report()), self.state(j): the device's
     float64 X_T of matrix j."""
 
+    NAME, KERNELS = "a WUDI", "WUDI"
+
     def __init__(self, device, iters=300, lr=1e-5):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.VlmError("the WUDI kernels run on the GPU only (got device %s)" % (device,))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(device)
         if int(iters) != iters or iters < 1:
             raise ValueError("WUDI takes iters >= 1 Adam steps, got %r" % (iters,))
         if not (lr > 0.0 and math.isfinite(lr)):
             raise ValueError("WUDI takes a finite lr > 0, got %r" % (lr,))
         self.iters, self.lr = int(iters), float(lr)
-        self.jobs = []   # (name, central, sources, out, lam)
-        self.keep = []
-        self.rows = None
         self._where = {}
-
-    _dev = M._Plan._dev   # float32, on the device, contiguous, 16-byte aligned: staged and kept alive where it is not
-
-    def add(self, srcs, base, lam=1.0, out=None, name=None):
-        """One output matrix.  `out` may be `base` or one of `srcs` (they are read before it is written) or any tensor that meets
-        none of them."""
-        if not 1 <= len(srcs) <= L.MERGE_MAX_SRC:
-            raise L.VlmError("a WUDI job takes 1 .. %d sources, got %d" % (L.MERGE_MAX_SRC, len(srcs)))
-        base = self._dev(base)
-        srcs = [self._dev(s) for s in srcs]
-        if base.dim() != 2 or base.numel() == 0 or any(s.shape != base.shape for s in srcs):
-            raise L.VlmError("a WUDI job takes non-empty matrices of one shape, got %s" % ([tuple(t.shape) for t in [base] + srcs],))
-        if out is None:
-            out = torch.empty_like(base)
-        elif out.shape != base.shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() \
-                or (out.data_ptr() & 15):
-            raise L.VlmError("a WUDI output must be a contiguous, 16-byte aligned float32 tensor of the sources' shape on %s" % self.device)
-        self.jobs.append((name, base, srcs, out, float(lam)))
-        return out
 
     def _chunks(self, g):
         """The calls of a group.  A step does not look at a matrix's source count or lam: it runs the group 64 matrices at a time,
@@ -118,26 +93,14 @@ class WudiPlan:
         if not self.jobs:
             self.rows = []
             return self
-        groups = {}
-        for j, (_, base, _, _, _) in enumerate(self.jobs):
-            groups.setdefault(tuple(base.shape), []).append(j)
-        groups = [dict(shape=key, jobs=js) for key, js in sorted(groups.items(), key=lambda kv: -kv[0][0] * kv[0][1] ** 2 * len(kv[1]))]
-        main = torch.cuda.current_stream(self.device)
-        side = _side_streams(self.device, len(groups) - 1)
+        groups = shape_groups(len(self.jobs), lambda j: tuple(self.jobs[j][1].shape), lambda shape: shape[0] * shape[1] ** 2)
         with torch.cuda.device(self.device):
             for g in groups:   # buffers on the CALLER's stream, whose allocator pool they belong to (state() outlives the run)
                 m, n = g["shape"]
                 g["buf"] = torch.empty(len(g["jobs"]), ops.wudi_work_doubles(m, n), dtype=torch.float64, device=self.device)
                 g["work"] = [g["buf"][i] for i in range(len(g["jobs"]))]
                 g["chunks"] = list(self._chunks(g))
-            for n_, g in enumerate(groups):  # the largest group stays on the caller's stream
-                st = main if n_ == 0 else side[n_ - 1]
-                if st is not main:
-                    st.wait_stream(main)
-                with torch.cuda.stream(st):
-                    self._enqueue(g)
-            for st in side[:len(groups) - 1]:
-                main.wait_stream(st)
+            run_groups(self.device, groups, self._enqueue)
             heads = torch.cat([g["buf"][:, :L.WUDI_HEAD].reshape(-1) for g in groups]).cpu().tolist()   # the one synchronisation
         rows, k0 = [None] * len(self.jobs), 0
         for g in groups:
@@ -153,11 +116,6 @@ class WudiPlan:
         self.groups = groups
         return self
 
-    def report(self):
-        if self.rows is None:
-            raise L.VlmError("WudiPlan.report() needs a plan that has run")
-        return [dict(r, sq=list(r["sq"])) for r in self.rows]
-
     def state(self, j):
         """The device's float64 X_T of job j, [m, n] as the tensor is stored."""
         g, i = self._where[j]
@@ -171,29 +129,8 @@ def wudi_merge(state_dict, config, central_weight=None, lam=None, device="cuda",
     only.  `plan_out` receives the WudiPlan FIRST whenever a matrix has several sources, then the MergePlan of everything else if it
     has jobs; `report_out` receives one row per matrix (dst, n, shape, S, iters, lr, sq per source, loss_first = L(X_0), loss_last =
     L(X_{iters-1})); `states_out[dst]` the device's float64 X_iters."""
-    if lam is None:
-        lam = config["sum_lambda"]
     wudi = WudiPlan(device, iters=iters, lr=lr)
-    plan = M.MergePlan(wudi.device)
-    out = M._passthrough(state_dict)
-    central = M._central(central_weight, config)
-    for dst, mods, srcs, through in M._walk(state_dict, config, central):
-        if srcs is None:
-            out[dst] = through
-        elif len(mods) == 1:
-            out[dst] = plan.add(L.MERGE_TASKVEC, M._tensors(srcs), [1], base=central[dst])
-        elif central[dst].dim() == 2:
-            out[dst] = wudi.add(M._tensors(srcs), central[dst], lam=lam, name=dst)
-        else:
-            out[dst] = plan.add(L.MERGE_TASKVEC, M._tensors(srcs), [lam / len(srcs)] * len(srcs), base=central[dst])
-    if plan.jobs:
-        plan.run()   # (enqueued first: the streaming pass runs under the iteration)
-    if wudi.jobs:
-        wudi.run()
-    if plan_out is not None:
-        plan_out.extend(p for p in (wudi, plan) if p.jobs)
-    if report_out is not None:
-        report_out.extend(wudi.report() if wudi.jobs else [])
+    out = matrix_merge(wudi, state_dict, config, central_weight, lam, plan_out, report_out)
     if states_out is not None:
         for j, job in enumerate(wudi.jobs):
             states_out[job[0]] = wudi.state(j)

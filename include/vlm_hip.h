@@ -1433,7 +1433,20 @@ typedef struct {
   const uint8_t* keep1;
   int32_t B, n0, n1, base0, base1, pos1;
   float scale;
-  int32_t reserved;
+  /* Kept query rows (the two ints this struct held in reserve; the second one sits behind dense_tiles): the outputs of the
+   * first q_keep0 text and the first q_keep1 image QUERY positions of every sample are wanted, nothing else.  0 in both = all
+   * (a limit past its segment is the whole segment; (k, 0) keeps no image query, (0, k) no text query).  Keys are never limited.
+   *   vlm_attention_fwd launches only the 128-position query tiles that hold a kept position; a launched tile writes all its
+   *     rows, the rows of out and lse in other tiles are NOT written and nobody may read them.
+   *   vlm_attention_bwd / _live: the caller promises -- as for row_live -- that the dO rows outside the prefixes count as
+   *     zero; they, and the out / lse rows there, are NOT read.  dQ of a kept row is what the unlimited call gives, the dQ third
+   *     of every other row is written as zeros (the qkv dgrad and wgrad read every row), dK / dV / the column sums / the
+   *     bias-table gradient take the kept queries only, delta is written for kept rows only.
+   * The limit is honoured where vlm_attention_qkeep_served() says so: by every forward kernel, every dQ kernel and the fused
+   * dK / dV / bias-gradient kernel.  A backward whose plan has the separate dK / dV kernel (no bias-table gradient asked for,
+   * or a panel that does not fit) IGNORES the limit: it reads every row of dO, out and lse, so its forward must have run
+   * without the limit and the dO rows outside the prefixes must hold zeros. */
+  int32_t q_keep0;
   /* Dense bias (vlm_bias_dense), REQUIRED when bias_t is set: fp16 log2(e) * bias_t[c][rel_index[q][k]/4] (the
    * kernels' score accumulators are base-2 exponents) for every (layer, head) column c, stored as 4-KiB tiles in MFMA operand order (one tile
    * per 32 stationary x 64 streamed positions, vlm_bias_dense_bytes() per column); positions that are not valid
@@ -1445,8 +1458,12 @@ typedef struct {
   const void* bias_dense;
   const void* bias_dense_t;
   int32_t dense_tiles; /* vlm_bias_dense_bytes(n0, n1, pos1, mode) / 4096 */
-  int32_t reserved2;
+  int32_t q_keep1;
 } vlm_attn_desc_t;
+
+/* 1: a vlm_attention_bwd / _live of this descriptor (with a bias-table gradient when with_dbias != 0) honours q_keep0 / q_keep1;
+ * 0: it ignores them (see above), or the descriptor is invalid.  The forward always honours them. */
+int vlm_attention_qkeep_served(const vlm_attn_desc_t* d, int with_dbias);
 
 /* Dense relative-position bias for all heads and layers at once (the reference's get_rel_pos_bias,
  * modules/vilt_module.py:1061-1064): out = n_cols columns of vlm_bias_dense_bytes() each.  index: int16 [pos1 + n1,

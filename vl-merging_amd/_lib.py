@@ -387,8 +387,8 @@ class AttnDesc(ctypes.Structure):
         ("index_t_rows", ctypes.c_int32), ("head_row0", ctypes.c_int32), ("mode", ctypes.c_int32),
         ("keep0", c_void_p), ("keep1", c_void_p),
         ("B", ctypes.c_int32), ("n0", ctypes.c_int32), ("n1", ctypes.c_int32), ("base0", ctypes.c_int32),
-        ("base1", ctypes.c_int32), ("pos1", ctypes.c_int32), ("scale", c_float), ("reserved", ctypes.c_int32),
-        ("bias_dense", c_void_p), ("bias_dense_t", c_void_p), ("dense_tiles", ctypes.c_int32), ("reserved2", ctypes.c_int32),
+        ("base1", ctypes.c_int32), ("pos1", ctypes.c_int32), ("scale", c_float), ("q_keep0", ctypes.c_int32),
+        ("bias_dense", c_void_p), ("bias_dense_t", c_void_p), ("dense_tiles", ctypes.c_int32), ("q_keep1", ctypes.c_int32),
     ]
 
 
@@ -459,6 +459,7 @@ SIGNATURES = {
     "vlm_gemm_wgrad_batch": (c_int, [c_int, ctypes.POINTER(WgradProblem), c_int, c_void_p, c_u64, c_void_p]),
     "vlm_attention_fwd": (c_int, [ctypes.POINTER(AttnDesc), c_void_p, c_int, c_void_p, c_void_p]),
     "vlm_attention_bwd_ws_floats": (c_size_t, [ctypes.POINTER(AttnDesc), c_int]),
+    "vlm_attention_qkeep_served": (c_int, [ctypes.POINTER(AttnDesc), c_int]),
     "vlm_attention_bwd": (c_int, [ctypes.POINTER(AttnDesc), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vlm_attention_bwd_live": (c_int, [ctypes.POINTER(AttnDesc), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,

@@ -72,8 +72,24 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq_kernel(const attn_
   const int D = p.H * 64;
   const int qp = sp.p0 + wave * 32 + r;
   const int qrow_raw = qp < sp.s_hi ? att_row_of(ps, b, qp) : -1;
-  const bool qvalid = qrow_raw >= 0;
-  const size_t qrow = qvalid ? (size_t)qrow_raw : (size_t)att_row_of(ps, b, sp.s_lo);
+  // Kept query rows (attention_keep.h): a tile without a kept query stores zeros into the dQ third of its rows (the qkv dgrad and
+  // wgrad read every row) and reads nothing; an unkept lane of a kept tile reads a kept row (the anchor) and is switched off
+  // like a gap position -- its dO row may not exist -- and stores zeros as well.
+  const att_keep_t kq = att_keep_limits(ps.n0, ps.n1, ps.pos1, p.qk0, p.qk1);
+  const bool qstore = qrow_raw >= 0;
+  if (!att_keep_has(p.ktiles, wtile)) {  // (workgroup-uniform)
+    if (qstore) {
+      bf16_t* op = bp.dqkv + (size_t)qrow_raw * bp.ld_dqkv + h * 64 + 4 * hh;
+      const bf16x4 z = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) *reinterpret_cast<bf16x4*>(op + db * 32 + 8 * g4) = z;
+    }
+    return;
+  }
+  const bool qvalid = qstore && att_keep_pos(kq, ps.pos1, qp);
+  const size_t qrow = qvalid ? (size_t)qrow_raw : (size_t)att_row_of(ps, b, att_keep_anchor(kq, ps.pos1, sp.s_lo, sp.s_hi));
   const int ntiles = (sp.s_hi - sp.s_lo + ATT_BK - 1) / ATT_BK;
   const float c1 = p.scale * ATT_LOG2E;
 
@@ -252,15 +268,15 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq_kernel(const attn_
     o[0][i] *= p.scale;
     o[1][i] *= p.scale;
   }
-  if (qvalid) {
-    bf16_t* op = bp.dqkv + qrow * bp.ld_dqkv + h * 64 + 4 * hh;
+  if (qstore) {
+    bf16_t* op = bp.dqkv + (size_t)qrow_raw * bp.ld_dqkv + h * 64 + 4 * hh;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         bf16x4 v;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (bf16_t)o[db][4 * g4 + i];
+        for (int i = 0; i < 4; ++i) v[i] = (bf16_t)(qvalid ? o[db][4 * g4 + i] : 0.f);
         *reinterpret_cast<bf16x4*>(op + db * 32 + 8 * g4) = v;
       }
   }
@@ -849,6 +865,12 @@ extern "C" size_t vlm_attention_bwd_ws_floats(const vlm_attn_desc_t* d, int with
   return att_bwd_plan(p, p.bias_t != nullptr).ws_floats;
 }
 
+extern "C" int vlm_attention_qkeep_served(const vlm_attn_desc_t* d, int with_dbias) {
+  attn_params_t p;
+  if (att_fill_params(d, p) != VLM_OK) return 0;
+  return att_bwd_plan(p, p.bias_t != nullptr && with_dbias != 0).W != 0 ? 1 : 0;
+}
+
 template <int W>
 static void dkvb_launch(const attn_bwd_params_t& bp, const att_bwd_plan_t& pl, hipStream_t s) {
   // dynamic LDS beyond 64 KB has to be asked for once per kernel
@@ -893,6 +915,9 @@ static int attention_bwd(const vlm_attn_desc_t* d, const void* out, int ld_out, 
   // ... and takes its C operands (nstat) from the dQ launch
   const att_bwd_plan_t pl = att_bwd_plan(p, p.bias_t && dbias_t);
   if (ws_floats < pl.ws_floats) return VLM_ERR_WORKSPACE;  // vlm_attention_bwd_ws_floats says so
+  // kept query rows: the dQ kernels (all tiles are launched: an unkept one stores zeros) and the fused dK / dV / bias-gradient
+  // kernel take the limit; a plan with the separate dK / dV kernel ignores it as a whole (vlm_attention_qkeep_served)
+  if (!pl.W) att_set_keep(p, 0, 0);
   bp.nstat = pl.nstat_off ? delta_ws + pl.nstat_off : nullptr;
   bp.o = reinterpret_cast<const bf16_t*>(out);
   bp.ld_o = ld_out;

@@ -83,8 +83,30 @@ __global__ __launch_bounds__(W * 64, 1) void attn_bwd_dkvb_kernel(const attn_bwd
   if (p.mode == VLM_ATTN_SEPARATE) { s_lo = part ? ps.pos1 : 0; s_hi = part ? ps.NP : ps.n0; }
   else { s_lo = 0; s_hi = ps.NP; }
   const int kp0 = s_lo + sb * ATT_KB;
-  const int nblk = (s_hi - s_lo + ATT_KB - 1) / ATT_KB;
+  // Kept query rows (attention_keep.h): the streamed range is cut to the blocks that hold a kept query.  From here on a block
+  // index is COMPACT (the panel, the skew, the barriers count kept blocks only); att_keep_unit() gives the block's place in
+  // the part where positions, rows or the bias table are addressed.  No limit: every block, in place.
+  const att_keep_t kq = att_keep_limits(ps.n0, ps.n1, ps.pos1, p.qk0, p.qk1);
+  const att_keep_run_t kr = att_keep_run(ps.n0, ps.n1, ps.pos1, p.qk0, p.qk1, p.mode != VLM_ATTN_SEPARATE, part, ATT_KB,
+                                         (s_hi - s_lo + ATT_KB - 1) / ATT_KB);
+  const int nblk = kr.n;
+  const int q_hi = s_hi < kq.qe ? s_hi : kq.qe;          // one past the last kept image position of the part
+  const int q_anchor = att_keep_anchor(kq, ps.pos1, s_lo, s_hi);  // what a lane of an unkept / absent query position reads
   const int b_lo = (int)((long)ps.B * grp / n_groups), b_hi = (int)((long)ps.B * (grp + 1) / n_groups);
+  if (nblk == 0) {  // (workgroup-uniform) no kept query sees these keys: zero dK / dV rows, nothing for the panel or the column sums
+    for (int b = b_lo + wave; b < b_hi; b += W) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int kpi = kp0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const int row = kpi < s_hi ? att_row_of(ps, b, kpi) : -1;
+        if (row >= 0) {
+          bf16_t* dst = bp.dqkv + (size_t)row * bp.ld_dqkv + D + h * 64 + r;
+          dst[0] = dst[32] = dst[D] = dst[D + 32] = (bf16_t)0.f;
+        }
+      }
+    }
+    return;
+  }
   const int wact = nblk < W ? nblk : W;  // waves that take samples (a short query range cannot keep W skewed waves apart)
   const int S = nblk / wact;             // >= 1
   const float c1 = p.scale * ATT_LOG2E;
@@ -173,15 +195,19 @@ __global__ __launch_bounds__(W * 64, 1) void attn_bwd_dkvb_kernel(const attn_bwd
     // finite Q / dO values arrive there are multiplied by P = 0.  (A per-lane `ok ? offset : out-of-range` made hipcc put every
     // load under an exec-mask branch of its own: ~120 scalar instructions per block and no counted vmcnt.)
     const uint32_t row_txt = (uint32_t)(ps.base0 + b * ps.n0), row_img = (uint32_t)(ps.base1 + b * ps.n1 - ps.pos1);
+    // (an unkept query's dO row may not exist: it reads the anchor, a kept position, as the gap and the ragged end do.  Without a
+    // limit the anchor is the part's FIRST position where these lanes used to read its last one: other addresses, the same
+    // results, since P = 0 for such a lane whatever finite values arrive)
     auto row_of = [&](int qp) -> uint32_t {
-      qp = qp < s_hi - 1 ? qp : s_hi - 1;
+      qp = (qp < q_hi && att_keep_pos(kq, ps.pos1, qp)) ? qp : q_anchor;
       return (uint32_t)qp + (qp < ps.n0 ? row_txt : row_img);
     };
-    auto request = [&](int j) {
+    auto request = [&](int jc) {
+      const int j = att_keep_unit(kr, jc);
       const int q0 = s_lo + j * ATT_KB;
       // 17 of the 20 blocks of a 384^2 pass are 32 consecutive image rows: their addresses are a scalar base + per-lane
       // constants (no vector arithmetic at all); both paths issue the same loads in the same order
-      if (q0 >= ps.pos1 && q0 + ATT_KB <= s_hi) {  // (wave-uniform)
+      if (q0 >= ps.pos1 && q0 + ATT_KB <= q_hi) {  // (wave-uniform)
         const uint32_t row0 = row_img + (uint32_t)q0;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -242,8 +268,8 @@ __global__ __launch_bounds__(W * 64, 1) void attn_bwd_dkvb_kernel(const attn_bwd
       // ---- query side of the statistics k-step: (-lse, -delta) of row q0 + r as three bf16 terms each ------------------------
       bf16x8 astat_e, astat_d;
       {
-        const int qp = s_lo + j * ATT_KB + r;
-        const bool qok = qp < s_hi && (qp < ps.n0 || qp >= ps.pos1);
+        const int qp = s_lo + att_keep_unit(kr, j) * ATT_KB + r;
+        const bool qok = qp < q_hi && att_keep_pos(kq, ps.pos1, qp);
         const float ve = qok ? -nlse : ATT_NEG_BIG, vd = qok ? -ndel : 0.f;
         // two bf16 terms each: 16 significant bits -- an error of 2^-17 |lse| < 2e-4 in the exponent, 1e-4 relative in P,
         // against the 2^-9 of P's own rounding to bf16
@@ -369,7 +395,7 @@ __global__ __launch_bounds__(W * 64, 1) void attn_bwd_dkvb_kernel(const attn_bwd
     for (int n = wave; n < nblk * 4; n += W) {  // one (block, g4) group of 64 lanes x 4 queries per trip
       const int j = n >> 2, g4 = n & 3;
       const f32x4 v = *reinterpret_cast<const f32x4*>(panel + (size_t)j * 1024 + g4 * 256 + lane * 4);
-      const int qq0 = s_lo + j * ATT_KB + 8 * g4 + 4 * hh;
+      const int qq0 = s_lo + att_keep_unit(kr, j) * ATT_KB + 8 * g4 + 4 * hh;
       uint32_t ids[4];
       bool same = true;
 #pragma unroll

@@ -58,7 +58,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq2_kernel(const attn
   // vlm_attention_bwd_live: a workgroup belongs to ONE sample, so a dead sample is a whole-workgroup skip in front of the
   // stream: zero dQ rows, and what the kernels after this one read from the prologue for these rows -- delta = rowsum(dO O) = 0
   // (dO is zero there) and the bias-gradient kernel's C operands.  Nothing is added to the q_bias column sums.
-  if (att_bwd_dead(bp, ps, sp.part, b)) {  // (workgroup-uniform)
+  // Kept query rows (attention_keep.h): a tile without a kept query takes the same path -- the dQ third of its rows is zeros, the
+  // qkv dgrad and wgrad read every row -- and never looks at dO, O or lse; delta of its rows is not needed by anybody.
+  const att_keep_t kq = att_keep_limits(ps.n0, ps.n1, ps.pos1, p.qk0, p.qk1);
+  if (!att_keep_has(p.ktiles, wtile) || att_bwd_dead(bp, ps, sp.part, b)) {  // (workgroup-uniform)
     const int qpd = sp.p0 + wave * 32 + r;
     const int rowd = qpd < sp.s_hi ? att_row_of(ps, b, qpd) : -1;
     if (rowd >= 0) {
@@ -100,8 +103,9 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq2_kernel(const attn
   b1w[1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rbias, bvoff + 3072, 0, 0));
   const int qp = sp.p0 + wave * 32 + r;
   const int qrow_raw = qp < sp.s_hi ? att_row_of(ps, b, qp) : -1;
-  const bool qvalid = qrow_raw >= 0;
-  const size_t qrow = qvalid ? (size_t)qrow_raw : (size_t)att_row_of(ps, b, sp.s_lo);
+  // a lane whose query is not kept reads a kept row (the anchor) and is switched off like a gap position: its dO row may not exist
+  const bool qvalid = qrow_raw >= 0 && att_keep_pos(kq, ps.pos1, qp);
+  const size_t qrow = qvalid ? (size_t)qrow_raw : (size_t)att_row_of(ps, b, att_keep_anchor(kq, ps.pos1, sp.s_lo, sp.s_hi));
   bf16x8 rawq[4], dof[4], rawo[4];
   {
     const bf16_t* qptr = p.qkv + qrow * p.ld_qkv + h * 64 + 8 * hh;
@@ -259,10 +263,11 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq2_kernel(const attn
   const int lane2 = tid2 & 63, wave2 = __builtin_amdgcn_readfirstlane(tid2 >> 6), r2 = lane2 & 31, hh2 = lane2 >> 5;
   const int qp2 = sp.p0 + wave2 * 32 + r2;
   const int raw2 = qp2 < sp.s_hi ? att_row_of(ps, b, qp2) : -1;
+  const bool kept2 = att_keep_pos(kq, ps.pos1, qp2);  // an unkept row of a kept tile: P = 0 all along, its dQ row is stored as zeros
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    o0[i] *= p.scale;
-    o1[i] *= p.scale;
+    o0[i] = kept2 ? o0[i] * p.scale : 0.f;
+    o1[i] = kept2 ? o1[i] * p.scale : 0.f;
   }
   if (raw2 >= 0) {
     bf16_t* op = bp.dqkv + (size_t)raw2 * bp.ld_dqkv + h * 64 + 4 * hh2;

@@ -1,6 +1,7 @@
 // Shared pieces of the fused attention kernels (forward, backward dK/dV/dBias, backward dQ).
 #pragma once
 #include "vlm_common.h"
+#include "attention_keep.h"
 
 #define ATT_BQ 128
 #define ATT_BK 64
@@ -87,7 +88,15 @@ struct attn_params_t {
   attn_seq_t seq;
   int mode;
   float scale;
+  int qk0, qk1;           // kept query prefix of the text / image segment (attention_keep.h); 0, 0 = every query
+  att_keep_run_t ktiles;  // the 128-position tiles that hold a kept query
 };
+
+static inline void att_set_keep(attn_params_t& p, int k0, int k1) {
+  p.qk0 = att_keep_all(k0, k1) ? 0 : k0;
+  p.qk1 = att_keep_all(k0, k1) ? 0 : k1;
+  p.ktiles = att_keep_tiles(p.seq.n0, p.seq.n1, p.seq.pos1, p.qk0, p.qk1, p.mode == VLM_ATTN_SEPARATE);
+}
 
 static inline int att_fill_params(const vlm_attn_desc_t* d, attn_params_t& p) {
   if (!d || !d->qkv || d->H <= 0 || d->B < 0 || d->n0 < 0 || d->n1 < 0) return VLM_ERR_ARG;
@@ -97,6 +106,7 @@ static inline int att_fill_params(const vlm_attn_desc_t* d, attn_params_t& p) {
   if ((d->pos1 & 7) || d->pos1 < d->n0) return VLM_ERR_ARG;  // image positions start at a multiple of 8 (16-B bias rows)
   if (d->mode != VLM_ATTN_JOINT && d->mode != VLM_ATTN_SEPARATE) return VLM_ERR_ARG;
   if (d->R > 8191) return VLM_ERR_UNSUPPORTED;  // int16 byte offsets (4*index), LDS-resident bias column
+  if (d->q_keep0 < 0 || d->q_keep1 < 0) return VLM_ERR_ARG;
   p.qkv = reinterpret_cast<const bf16_t*>(d->qkv);
   p.ld_qkv = d->ld_qkv;
   p.H = d->H;
@@ -122,6 +132,7 @@ static inline int att_fill_params(const vlm_attn_desc_t* d, attn_params_t& p) {
   p.seq = (attn_seq_t){d->B, d->n0, d->n1, d->base0, d->base1, d->pos1};
   p.mode = d->mode;
   p.scale = d->scale;
+  att_set_keep(p, d->q_keep0, d->q_keep1);
   return VLM_OK;
 }
 

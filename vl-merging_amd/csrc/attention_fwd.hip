@@ -40,8 +40,8 @@ __global__ __launch_bounds__(ATT_THREADS, 3) void attn_fwd_kernel(const attn_par
   const int r = lane & 31, hh = lane >> 5;
   const att_pos_t ps = att_pos(p.seq);
   int wtile, b, h;
-  if (!att_work_item(att_num_tiles(ps.n0, ps.n1, ps.pos1, p.mode), ps.B, p.H, wtile, b, h)) return;
-  const att_span_t sp = att_span(ps, p.mode, wtile);
+  if (!att_work_item(p.ktiles.n, ps.B, p.H, wtile, b, h)) return;  // only the tiles that hold a kept query are launched
+  const att_span_t sp = att_span(ps, p.mode, att_keep_unit(p.ktiles, wtile));
   const int D = p.H * 64;
 
   const int qp = sp.p0 + wave * 32 + r;                 // this lane's query position
@@ -248,10 +248,10 @@ extern "C" int vlm_attention_fwd(const vlm_attn_desc_t* d, void* out, int ld_out
   p.ld_out = ld_out;
   p.lse = lse;
   const int nt = att_num_tiles(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode);
-  if (nt == 0 || p.seq.B == 0) return VLM_OK;
+  if (nt == 0 || p.seq.B == 0 || p.ktiles.n == 0) return VLM_OK;
   if (p.dense && p.dense_tiles != att_dense_layout(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode).tiles) return VLM_ERR_ARG;
   const size_t smem = 0;
-  dim3 grid(att_grid_size(nt, p.seq.B, p.H)), block(ATT_THREADS);
+  dim3 grid(att_grid_size(p.ktiles.n, p.seq.B, p.H)), block(ATT_THREADS);
   hipStream_t s = (hipStream_t)stream;
   if (p.bias_t) {  // the hand-placed stream (attention_fwd2.hip) takes the calls it covers
     const int r2 = att_fwd2_launch(p, s);

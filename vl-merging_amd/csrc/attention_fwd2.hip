@@ -51,8 +51,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd2_kernel(const attn_pa
   const att_pos_t ps = att_pos(p.seq);
   const int npairs = (ps.B + 1) >> 1;
   int wtile, bp, h;
-  if (!att_work_item(att_num_tiles(ps.n0, ps.n1, ps.pos1, p.mode), npairs, p.H, wtile, bp, h)) return;
-  const att_span_t sp = att_span(ps, p.mode, wtile);
+  if (!att_work_item(p.ktiles.n, npairs, p.H, wtile, bp, h)) return;  // only the tiles that hold a kept query are launched
+  const att_span_t sp = att_span(ps, p.mode, att_keep_unit(p.ktiles, wtile));
   ATT_STAMP(0);
   const int D = p.H * 64;
   const int bs[2] = {2 * bp, 2 * bp + 1 < ps.B ? 2 * bp + 1 : 2 * bp};  // an odd batch's last pair computes sample 0 twice
@@ -245,8 +245,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd2_kernel(const attn_pa
 // returns 1 when it has launched the call, 0 when the call is not for this kernel, < 0 on error
 int att_fwd2_launch(const attn_params_t& p, hipStream_t s) {
   if (!att_handplaced_covers(p)) return 0;
-  const int nt = att_num_tiles(p.seq.n0, p.seq.n1, p.seq.pos1, p.mode);
-  dim3 grid(att_grid_size(nt, (p.seq.B + 1) / 2, p.H)), block(ATT_THREADS);
+  dim3 grid(att_grid_size(p.ktiles.n, (p.seq.B + 1) / 2, p.H)), block(ATT_THREADS);
   hipLaunchKernelGGL(attn_fwd2_kernel, grid, block, 0, s, p);
   if (hipGetLastError() != hipSuccess) return VLM_ERR_LAUNCH;
   return 1;

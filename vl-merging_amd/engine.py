@@ -313,6 +313,102 @@ def wT16(p):
 _ROWSKIP = {"enabled": True}
 
 
+# Kept rows ("Kept rows"): the LAST block of a pass whose heads read a per-segment prefix of the rows only (the text rows
+# of the fused MLM + ITM pass, the cls rows of the fused unimodal pass) runs norm1 and the qkv projection on every row -- keys and
+# values need them -- and everything behind the attention on the kept rows alone, forward and backward; the attention kernels take
+# the prefixes as q_keep.  False: such a block computes every row and hands out the kept ones (tests run both ways in one process).
+_TAILROWS = {"enabled": True}
+
+
+class KeepRows:
+    """The rows of a segment-major pass that the per-segment query prefixes keep = (k0, k1) keep: one contiguous row range (a
+    whole segment and nothing of the other: views, no copy) or the first row of every sample of a segment (gathered once).
+    of(): None for any other prefix -- the block then computes every row."""
+
+    def __init__(self, seq, q, span, parts):
+        self.seq, self.q, self.span, self.parts = seq, q, span, parts
+        self.count = sum(c for _, _, c in parts)
+
+    @staticmethod
+    def of(seq, keep):
+        k0, k1 = min(int(keep[0]), seq.n0), min(int(keep[1]), seq.n1)
+        if k0 <= 0 and k1 <= 0:
+            return None
+        B = seq.B
+        if k1 <= 0 and k0 == seq.n0:
+            return KeepRows(seq, (k0, 0), (seq.base0, seq.base0 + B * k0), [(seq.base0, 1, B * k0)])
+        if k0 <= 0 and k1 == seq.n1:
+            return KeepRows(seq, (0, k1), (seq.base1, seq.base1 + B * k1), [(seq.base1, 1, B * k1)])
+        if k0 <= 1 and k1 <= 1:
+            parts = ([(seq.base0, seq.n0, B)] if k0 else []) + ([(seq.base1, seq.n1, B)] if k1 else [])
+            return KeepRows(seq, (max(k0, 0), max(k1, 0)), None, parts)
+        return None
+
+    def take(self, t):
+        """The kept rows of t [rows, ...]: a view of a contiguous range, else one gather copy."""
+        if t is None:
+            return None
+        if self.span is not None:
+            return t[self.span[0]:self.span[1]]
+        return torch.cat([t[first::step][:count] for first, step, count in self.parts])
+
+    def put(self, g, rows, dtype):
+        """[rows, D] of dtype: g's rows at their places, zeros elsewhere (one launch)."""
+        src, at = [], 0
+        for first, step, count in self.parts:
+            src.append((g[at:at + count], first, step))
+            at += count
+        return ops.scatter_rows(rows, g.shape[1], dtype, src, g.device)
+
+    def ranges(self, ranges):
+        """The plan's expert row ranges in kept-row coordinates."""
+        out, at = [], 0
+        for first, step, count in self.parts:
+            last = first + (count - 1) * step
+            for r0, r1, e in ranges:
+                lo, hi = max(first, r0), min(last + 1, r1)
+                if lo >= hi:
+                    continue
+                if step != 1 and not (r0 <= first and last < r1):
+                    return None  # a strided part that straddles two experts: nobody builds that
+                a = at + (lo - first if step == 1 else 0)
+                b = at + (hi - first if step == 1 else count)
+                if out and out[-1][1] == a and out[-1][2] is e:
+                    out[-1] = (out[-1][0], b, e)  # the same expert's next rows: one range
+                else:
+                    out.append((a, b, e))
+            at += count
+        return out
+
+    def pieces(self, r0, r1):
+        """[r0, r1) cut at the contiguous kept range: (a, b, first kept-row index or None) pieces in row order."""
+        k0, k1 = self.span
+        cuts = sorted({r0, r1, min(max(k0, r0), r1), min(max(k1, r0), r1)})
+        return [(a, b, a - k0 if k0 <= a and b <= k1 else None) for a, b in zip(cuts, cuts[1:]) if a < b]
+
+
+def _keep_rows(keep, plan, pc, rp, qkv, backward_follows):
+    """The KeepRows a block evaluation may use, or None: the switch, a prefix form KeepRows serves, no Gram capture (it reads
+    every row), and -- where a backward follows -- an attention backward plan that honours the limit (ops.attention_qkeep_served;
+    asked once per pass and mode).  The forward kernels always honour it: an evaluation nobody differentiates (torch.no_grad)
+    needs no more."""
+    if keep is None or not _TAILROWS["enabled"] or pc.gram is not None:
+        return None
+    kr = KeepRows.of(pc.seq, keep)
+    rg = kr.ranges(plan.ranges) if kr is not None else None
+    if rg is None or (kr.span is None and len(rg) > 1):
+        return None  # (gathered first rows of two experts would be two groups of B rows each: such a block computes every row)
+    if not backward_follows:
+        return kr
+    served = pc.__dict__.setdefault("_qkeep_served", {})
+    key = (plan.mode, rp is not None and rp.holder.get("dbias_t") is not None)
+    if key not in served:
+        served[key] = rp is not None and ops.attention_qkeep_served(
+            qkv, pc.seq, pc.H, bias_t=rp.bias_t.detach(), head_row0=plan.layer * pc.H, rel_index=rp.index, rel_index_t=rp.index_t,
+            keep0=pc.keep0, keep1=pc.keep1, mode=plan.mode, bias_dense=rp.dense_for(pc.seq, plan.mode), with_dbias=key[1])
+    return kr if served[key] else None
+
+
 def _live(rs, plan, pc):
     """The row vector a site's GEMMs and attention backward may skip by: the site's DropPath factors, unless the Gram cache is
     being recorded (it reads the activations of every row) or joint attention mixes two draws (a live segment would then read the
@@ -702,7 +798,7 @@ class _BlockFn(torch.autograd.Function):
     Reference: Block.plain_forward / separate_plain_forward / moe_forward, vision_transformer.py:525-681."""
 
     @staticmethod
-    def forward(ctx, x, bias_t, plan: BlockPlan, pc: PassCtx, training: bool, hook):
+    def forward(ctx, x, bias_t, plan: BlockPlan, pc: PassCtx, training: bool, hook, keep=None, recorded=True):
         M, D = x.shape
         dev = x.device
         H = pc.H
@@ -722,10 +818,19 @@ class _BlockFn(torch.autograd.Function):
         o = torch.empty(M, D, device=dev, dtype=BF16)
         lse = torch.empty(H, M, device=dev, dtype=F32)
         rp = pc.relpos
+        # kept rows: behind the attention the block works on the rows its caller reads alone (kr.take: views of a contiguous
+        # range, one gather otherwise) -- M, rg, x, o and the DropPath factors stand for the kept rows from there on
+        # (recorded: autograd keeps this evaluation, a backward may read its buffers -- run_block says so)
+        kr = _keep_rows(keep, plan, pc, rp, qkv, recorded) if bias_t is not None else None
         ops.attention_fwd(qkv, o, lse, pc.seq, H, bias_t=bias_t, head_row0=plan.layer * H,
                           rel_index=rp.index if rp is not None else None,
                           rel_index_t=rp.index_t if rp is not None else None, keep0=pc.keep0, keep1=pc.keep1,
-                          mode=plan.mode, bias_dense=rp.dense_for(pc.seq, plan.mode) if rp is not None else None)
+                          mode=plan.mode, bias_dense=rp.dense_for(pc.seq, plan.mode) if rp is not None else None,
+                          q_keep=kr.q if kr is not None else None)
+        M_all, x_all, o_all, rs1_all, rs2_all = M, x, o, rs1, rs2
+        if kr is not None:
+            M, rg = kr.count, kr.ranges(rg)
+            x, o, rs1, rs2, live1, live2 = (kr.take(t) for t in (x, o, rs1, rs2, live1, live2))
         x1 = torch.empty(M, D, device=dev, dtype=F32)
         folded = _folded(plan.ranges)
         # folded: W' = diag(gamma) W and b' = gamma * b are the GEMM operands -- no column scale, no saved branch output
@@ -769,24 +874,43 @@ class _BlockFn(torch.autograd.Function):
         ctx.plan, ctx.pc, ctx.hook = plan, pc, hook
         ctx.has_bias = bias_t is not None
         ctx.folded = folded
-        ctx.save_for_backward(x, st1, ln1, qkv, o, lse, y1 if y1 is not None else x.new_empty(0), x1, st2, ln2, h, a,
+        ctx.kr = kr
+        if kr is None and keep is not None and KeepRows.of(pc.seq, keep) is not None:
+            # the limit is not served here (switch off, Gram capture, a backward plan that ignores it): every row was computed,
+            # the caller still gets the kept rows
+            ctx.kr_out = KeepRows.of(pc.seq, keep)
+            x2_out = ctx.kr_out.take(x2)
+        else:
+            ctx.kr_out, x2_out = None, x2
+        # (kept rows: x and o are saved whole -- norm1's backward and the attention backward read them by row -- and ok, the
+        # compact operand of the proj wgrad, beside o when it is a gathered copy)
+        ctx.save_for_backward(x_all, st1, ln1, qkv, o_all, lse, y1 if y1 is not None else x.new_empty(0), x1, st2, ln2, h, a,
                               y2 if y2 is not None else x.new_empty(0),
-                              rs1 if rs1 is not None else x.new_empty(0), rs2 if rs2 is not None else x.new_empty(0),
-                              bias_t if bias_t is not None else x.new_empty(0))
-        return x2
+                              rs1_all if rs1_all is not None else x.new_empty(0),
+                              rs2_all if rs2_all is not None else x.new_empty(0),
+                              bias_t if bias_t is not None else x.new_empty(0),
+                              o if (kr is not None and kr.span is None) else x.new_empty(0))
+        return x2_out
 
     @staticmethod
     def backward(ctx, dx2):
         plan, pc = ctx.plan, ctx.pc
-        x, st1, ln1, qkv, o, lse, y1, x1, st2, ln2, h, a, y2, rs1, rs2, bias_t = ctx.saved_tensors
+        x, st1, ln1, qkv, o, lse, y1, x1, st2, ln2, h, a, y2, rs1, rs2, bias_t, ok = ctx.saved_tensors
+        kr = ctx.kr
         rs1 = rs1 if rs1.numel() else None
         rs2 = rs2 if rs2.numel() else None
+        live_all = _live(rs1, plan, pc)  # the attention backward reads the whole vector, the GEMMs the kept rows' factors
+        if kr is not None:
+            rs1, rs2 = kr.take(rs1), kr.take(rs2)
         live1, live2 = _live(rs1, plan, pc), _live(rs2, plan, pc)
         bias_t = bias_t if ctx.has_bias else None
-        M, D = x.shape
+        M_all, D = x.shape
+        M = x1.shape[0]
         dev = x.device
         H = pc.H
         Fdim = h.shape[1]
+        if ctx.kr_out is not None:  # every row was computed and the kept ones handed out: the other rows' gradient is zero
+            dx2 = ctx.kr_out.put(dx2.contiguous(), M_all, F32)
         dx2 = dx2.contiguous()
         g1, g2 = plan.gamma1, plan.gamma2
         folded = ctx.folded
@@ -809,8 +933,20 @@ class _BlockFn(torch.autograd.Function):
         fold = ops.FoldBatch(dev, D)
         # ---- FFN branch, then the attention branch up to the attention core.  Row kernels run per expert row range (their
         # parameters and gradient targets differ), every GEMM covers all ranges (_gemm_rows / _wgrad_rows) ----
-        rg = plan.ranges
-        do = torch.empty(M, D, device=dev, dtype=BF16)
+        # Kept rows: M, rg, ok and the DropPath factors are the kept rows' up to the proj dgrad; the attention backward, the qkv
+        # dgrad / wgrad and norm1's backward see all M_all rows (rg_all), with dO and dres present on the kept rows only
+        rg_all = plan.ranges
+        rg = kr.ranges(rg_all) if kr is not None else rg_all
+        # ok: the attention output of the rows the tail works on (the proj wgrad's operand); do: where the proj dgrad writes dO;
+        # do_all: dO as the attention backward addresses it, by row of the pass
+        if kr is None:
+            ok, do_all = o, torch.empty(M_all, D, device=dev, dtype=BF16)
+            do = do_all
+        elif kr.span is not None:  # a contiguous range: views
+            ok, do_all = kr.take(o), torch.empty(M_all, D, device=dev, dtype=BF16)
+            do = kr.take(do_all)
+        else:                      # gathered rows: ok is the forward's copy, dO is scattered to its rows behind the proj dgrad
+            do_all, do = None, torch.empty(M, D, device=dev, dtype=BF16)
         for r0, r1, e in rg:
             rr = slice(r0, r1)
             if folded:
@@ -823,8 +959,11 @@ class _BlockFn(torch.autograd.Function):
         _gemm_rows(dy2, [(r0, r1, wT16(e.fc2w), None, e.fc1b.grad) for r0, r1, e in rg], dh, act=L.ACT_MUL_AUX, aux=h,
                    col_sum_fold=fold, row_live=live2)
         # side stream, one row range: the block's four weight gradients leave as ONE batched launch after the attention backward
+        # (kept rows: the three tail weights reduce over the kept rows, qkv over all of them -- a batch has ONE reduction length,
+        # so the tail's three leave as one batch and qkv's goes alone)
+        tail3 = [(D, Fdim), (Fdim, D), (D, D)]
         batch = wgrad_stream() is not None and len(rg) == 1 and ops.wgrad_batch_serves(
-            rg[0][1] - rg[0][0], [(D, Fdim), (Fdim, D), (D, D), (3 * D, D)])
+            rg[0][1] - rg[0][0], tail3 + ([(3 * D, D)] if kr is None else []))
         if not batch:
             with _Side(dy2, a, dh, ln2):
                 _wgrad_rows(dy2, a, [(r0, r1, wg(e.fc2w)) for r0, r1, e in rg])
@@ -836,39 +975,56 @@ class _BlockFn(torch.autograd.Function):
                             rs1[rr] if rs1 is not None else None, dy1[rr], fold)
         _gemm_rows(dy1, [(r0, r1, wT16(e.projw), None, None) for r0, r1, e in rg], do, row_live=live1)
         if not batch:
-            with _Side(dy1, o):
-                _wgrad_rows(dy1, o, [(r0, r1, wg(e.projw)) for r0, r1, e in rg])
-        dqkv = torch.empty(M, 3 * D, device=dev, dtype=BF16)
-        dln1 = torch.empty(M, D, device=dev, dtype=BF16)
+            with _Side(dy1, ok):
+                _wgrad_rows(dy1, ok, [(r0, r1, wg(e.projw)) for r0, r1, e in rg])
+        if do_all is None:
+            do_all = kr.put(do, M_all, BF16)  # gathered rows: dO at its rows (the attention backward reads the kept ones only)
+        dqkv = torch.empty(M_all, 3 * D, device=dev, dtype=BF16)
+        dln1 = torch.empty(M_all, D, device=dev, dtype=BF16)
         rp = pc.relpos
         # q_bias / v_bias gradients: column sums of dQ / dV per segment, taken inside the attention backward when every
         # segment lies inside ONE expert's row range (always true for the layouts Block.plan() builds)
-        qb_grads, vb_grads, fused_qv = _segment_bias_grads(rg, pc.seq)
-        ops.attention_bwd(qkv, o, do, lse, dqkv, pc.seq, H, bias_t=bias_t, head_row0=plan.layer * H,
+        qb_grads, vb_grads, fused_qv = _segment_bias_grads(rg_all, pc.seq)
+        dbias_acc = rp.holder.get("dbias_t") if rp is not None else None
+        if kr is not None and dbias_acc is None:
+            # The forward ran with the limit because THIS call's plan honours it: the plan with the table gradient.  Its accumulator
+            # is gone (a second backward over a retained graph: _TableT.backward has taken it) -- the plan must stay, or the separate
+            # dK / dV kernel would read the rows of out, lse and dO that were never written.  The table gradient goes to a scratch.
+            dbias_acc = torch.zeros_like(bias_t)
+        ops.attention_bwd(qkv, o, do_all, lse, dqkv, pc.seq, H, bias_t=bias_t, head_row0=plan.layer * H,
                           rel_index=rp.index if rp is not None else None,
                           rel_index_t=rp.index_t if rp is not None else None, keep0=pc.keep0, keep1=pc.keep1,
-                          mode=plan.mode, dbias_t=rp.holder.get("dbias_t") if rp is not None else None,
+                          mode=plan.mode, dbias_t=dbias_acc,
                           dq_colsum=qb_grads, dv_colsum=vb_grads,
-                          bias_dense=rp.dense_for(pc.seq, plan.mode) if rp is not None else None, row_live=live1)
-        dx = torch.empty(M, D, device=dev, dtype=F32)
-        for r0, r1, e in rg:
+                          bias_dense=rp.dense_for(pc.seq, plan.mode) if rp is not None else None, row_live=live_all,
+                          q_keep=kr.q if kr is not None else None)
+        dx = torch.empty(M_all, D, device=dev, dtype=F32)
+        for r0, r1, e in rg_all:
             if e.qb is not None and not fused_qv:
                 ops.colsum(dqkv[r0:r1, :D], e.qb.grad)
                 ops.colsum(dqkv[r0:r1, 2 * D:], e.vb.grad)
         if batch:
             (r0, r1, e), = rg
             rr = slice(r0, r1)
-            with _Side(dy2, a, dh, ln2, dy1, o, dqkv, ln1):
-                ops.gemm_wgrad_batch([(dy2[rr], a[rr], wg(e.fc2w)), (dh[rr], ln2[rr], e.fc1w.grad),
-                                      (dy1[rr], o[rr], wg(e.projw)), (dqkv[rr], ln1[rr], e.qkvw.grad)])
+            with _Side(dy2, a, dh, ln2, dy1, ok, dqkv, ln1):
+                tail = [(dy2[rr], a[rr], wg(e.fc2w)), (dh[rr], ln2[rr], e.fc1w.grad), (dy1[rr], ok[rr], wg(e.projw))]
+                if kr is None:
+                    ops.gemm_wgrad_batch(tail + [(dqkv[rr], ln1[rr], e.qkvw.grad)])
+                else:
+                    ops.gemm_wgrad_batch(tail)
+                    _wgrad_rows(dqkv, ln1, [(q0, q1, eq.qkvw.grad) for q0, q1, eq in rg_all])
         else:
             with _Side(dqkv, ln1):
-                _wgrad_rows(dqkv, ln1, [(r0, r1, e.qkvw.grad) for r0, r1, e in rg])
-        _gemm_rows(dqkv, [(r0, r1, wT16(e.qkvw), None, None) for r0, r1, e in rg], dln1, row_live=live1)
-        for r0, r1, e in rg:
-            rr = slice(r0, r1)
-            ops.layernorm_bwd(dln1[rr], x[rr], st1[rr], e.n1w, dx[rr], dres=dx1[rr], dgamma=e.n1w.grad, dbeta=e.n1b.grad,
-                              fold=fold)
+                _wgrad_rows(dqkv, ln1, [(r0, r1, e.qkvw.grad) for r0, r1, e in rg_all])
+        _gemm_rows(dqkv, [(r0, r1, wT16(e.qkvw), None, None) for r0, r1, e in rg_all], dln1, row_live=live_all)
+        if kr is not None and kr.span is None:
+            dx1 = kr.put(dx1, M_all, F32)  # gathered rows: the residual-stream gradient at its rows, zeros elsewhere
+        for r0, r1, e in rg_all:
+            # (a contiguous kept range: the rows outside it have no residual-stream gradient -- norm1's backward runs per piece)
+            for p0, p1, at in ([(r0, r1, r0)] if kr is None or kr.span is None else kr.pieces(r0, r1)):
+                rr = slice(p0, p1)
+                ops.layernorm_bwd(dln1[rr], x[rr], st1[rr], e.n1w, dx[rr], dres=dx1[at:at + p1 - p0] if at is not None else None,
+                                  dgamma=e.n1w.grad, dbeta=e.n1b.grad, fold=fold)
         fold.flush()
         if folded:
             flat.ls_pending.add(plan.layer)
@@ -880,12 +1036,18 @@ class _BlockFn(torch.autograd.Function):
             # reach _TableT.backward (a zero from every block evaluation cost 22 [144, R] additions per step)
             rp.holder["routed"] = True
             dbias = _zero_scalar(dev).expand_as(bias_t)
-        return dx, dbias, None, None, None, None
+        return dx, dbias, None, None, None, None, None, None
 
 
-def run_block(x, plan: BlockPlan, pc: PassCtx, training: bool, hook=None):
+def run_block(x, plan: BlockPlan, pc: PassCtx, training: bool, hook=None, keep=None):
+    """keep: per-segment prefixes (k0, k1) of the rows the caller reads -- the block then RETURNS those rows only (KeepRows: a
+    whole segment as a contiguous range, or the first row of every sample of the named segments, text rows first) and takes
+    their gradient; None: every row."""
     bias_t = pc.relpos.bias_t if pc.relpos is not None else None
-    return _BlockFn.apply(x, bias_t, plan, pc, training, hook)
+    if keep is not None and KeepRows.of(pc.seq, keep) is None:
+        raise L.VlmError("run_block: keep must name whole segments or first rows, got %r" % (keep,))
+    recorded = torch.is_grad_enabled() and (x.requires_grad or (bias_t is not None and bias_t.requires_grad))
+    return _BlockFn.apply(x, bias_t, plan, pc, training, hook, keep, recorded)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -1237,7 +1399,7 @@ def feature_views(x, B, T, I):
     if _kernel_rows(x) and x.is_contiguous() and D % 4 == 0 and torch.is_grad_enabled() and x.requires_grad:
         return _FeatureViewsFn.apply(x, B, T, I)
     text, image = x[:nt].view(B, T, D), x[nt:].view(B, I, D)
-    return text, image, text[:, 0], image[:, 0]
+    return text, image, (text[:, 0] if T else x[:0]), (image[:, 0] if I else x[:0])  # (an empty segment has no cls rows)
 
 
 class _RowRangeFn(torch.autograd.Function):

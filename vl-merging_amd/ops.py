@@ -1126,7 +1126,7 @@ class Seq:
         return self.B * (self.n0 + self.n1)
 
 
-def _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, keep1, mode, scale, bias_dense=None):
+def _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, keep1, mode, scale, bias_dense=None, q_keep=None):
     L.require_cuda(qkv, bias_t, rel_index, rel_index_t, keep0, keep1)
     if qkv.dtype != BF16:
         raise L.VlmError("attention expects bf16 qkv")
@@ -1160,6 +1160,8 @@ def _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, ke
     d.keep1 = keep1.data_ptr() if keep1 is not None else 0
     d.B, d.n0, d.n1, d.base0, d.base1, d.pos1 = seq.B, seq.n0, seq.n1, seq.base0, seq.base1, seq.pos1
     d.scale = scale
+    if q_keep is not None:  # kept query prefixes (text, image) of include/vlm_hip.h; None or (0, 0): every query
+        d.q_keep0, d.q_keep1 = int(q_keep[0]), int(q_keep[1])
     if bias_t is not None:
         if bias_dense is None:
             if rel_index is None:
@@ -1208,12 +1210,22 @@ def bias_dense(bias_t, index16, seq, mode):
 
 
 def attention_fwd(qkv, out, lse, seq, H, *, bias_t=None, head_row0=0, rel_index=None, rel_index_t=None, keep0=None,
-                  keep1=None, mode=L.ATTN_JOINT, scale=0.125, bias_dense=None):
-    d = _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, keep1, mode, scale, bias_dense)
+                  keep1=None, mode=L.ATTN_JOINT, scale=0.125, bias_dense=None, q_keep=None):
+    """q_keep: (text, image) query prefixes whose rows of out / lse are wanted; the other query tiles are not launched and their
+    rows are not written."""
+    d = _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, keep1, mode, scale, bias_dense, q_keep)
     L.require_cuda(out, lse)
     rc = L.get_lib().vlm_attention_fwd(ctypes.byref(d), L.ptr(out), _ld(out), L.ptr(lse), L.stream_ptr())
     L.check(rc, "vlm_attention_fwd")
     return out
+
+
+def attention_qkeep_served(qkv, seq, H, *, bias_t=None, head_row0=0, rel_index=None, rel_index_t=None, keep0=None, keep1=None,
+                           mode=L.ATTN_JOINT, scale=0.125, bias_dense=None, with_dbias=True):
+    """Does attention_bwd of this call honour a q_keep limit (vlm_attention_qkeep_served)?  Where it does not, run forward and
+    backward without one."""
+    d = _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, keep1, mode, scale, bias_dense)
+    return bool(L.get_lib().vlm_attention_qkeep_served(ctypes.byref(d), 1 if with_dbias else 0))
 
 
 _ATTN_WS = {}
@@ -1221,13 +1233,15 @@ _ATTN_WS = {}
 
 def attention_bwd(qkv, out, dout, lse, dqkv, seq, H, *, bias_t=None, head_row0=0, rel_index=None, rel_index_t=None,
                   keep0=None, keep1=None, mode=L.ATTN_JOINT, scale=0.125, dbias_t=None, delta_ws=None,
-                  dq_colsum=None, dv_colsum=None, bias_dense=None, row_live=None):
+                  dq_colsum=None, dv_colsum=None, bias_dense=None, row_live=None, q_keep=None):
     """dqkv <- d(loss)/d(qkv) (bf16, same layout as qkv); dbias_t += d(loss)/d(bias_t).  dq_colsum / dv_colsum:
     optional pairs (text-segment target, image-segment target) of f32 [H*64] vectors (None entries allowed) that
     receive += column sums of dQ / dV over that segment's rows (the q_bias / v_bias gradients).
     row_live: f32 [rows] DropPath factors; a (sample, segment) whose first row is 0 has zero dout rows and gets zero dqkv rows
-    without being recomputed (vlm_attention_bwd_live)."""
-    d = _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, keep1, mode, scale, bias_dense)
+    without being recomputed (vlm_attention_bwd_live).
+    q_keep: (text, image) query prefixes; dout / out / lse rows outside them are not read and count as zero, the dQ third of those
+    rows is written as zeros.  Honoured where attention_qkeep_served() says so, ignored otherwise (include/vlm_hip.h)."""
+    d = _attn_desc(qkv, seq, H, bias_t, head_row0, rel_index, rel_index_t, keep0, keep1, mode, scale, bias_dense, q_keep)
     L.require_cuda(out, dout, lse, dqkv, dbias_t, delta_ws)
     cs = None
     if dq_colsum is not None or dv_colsum is not None:

@@ -86,7 +86,7 @@ def _labels_arange(n, device):
 
 def compute_ifm(pl_module, batch, aggregate=True):
     if getattr(pl_module, "fuse_unimodal_passes", False):
-        infer_imag, infer_text = pl_module.infer_unimodal_pair(batch, with_vlffn=True)
+        infer_imag, infer_text = pl_module.infer_unimodal_pair(batch, with_vlffn=True, reads="cls")
     else:
         infer_imag = pl_module.infer_image(batch, mask_image=False)
         infer_text = pl_module.infer_text(batch, mask_text=False)
@@ -100,7 +100,7 @@ def compute_ifm(pl_module, batch, aggregate=True):
 
 def compute_irtr(pl_module, batch, aggregate=True):
     if getattr(pl_module, "fuse_unimodal_passes", False):
-        infer_imag, infer_text = pl_module.infer_unimodal_pair(batch, with_vlffn=False)
+        infer_imag, infer_text = pl_module.infer_unimodal_pair(batch, with_vlffn=False, reads="cls")
     else:
         infer_imag = pl_module.infer_image_ft(batch, mask_image=False)
         infer_text = pl_module.infer_text_ft(batch, mask_text=False)
@@ -213,7 +213,8 @@ def compute_mlm_itm_fused(pl_module, batch, sim_i2t, sim_t2i):
         "text_labels": torch.cat([batch["text_labels_mlm"]] + [batch["text_labels"]] * 3),
         "image": [torch.cat([img, img, images_neg, img])],
     }
-    infer = pl_module.infer(big, mask_text=False, mask_image=False)
+    # the heads below read text rows only (text_feats of the masked copies, the cls rows of the other three)
+    infer = pl_module.infer(big, mask_text=False, mask_image=False, reads="text")
     mlm_logits = pl_module.mlm_score(engine.row_range(infer["text_feats"], 0, bsz))
     mlm_labels = batch["text_labels_mlm"]
     mlm_loss = engine.cross_entropy(mlm_logits.view(-1, pl_module.hparams.config["vocab_size"]), mlm_labels.view(-1), ignore_index=-100)

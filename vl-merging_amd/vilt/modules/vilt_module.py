@@ -505,9 +505,18 @@ class ViLTransformerSS(nn.Module):
         return sites
 
     # ---- passes ----------------------------------------------------------------------------------------------------------
+    def _reads(self, reads, allowed):
+        """The row set a pass's caller reads: "all", or a restriction the last block and the final norm then honour (kept rows,
+        engine.run_block).  Recording the Gram cache reads every row."""
+        if reads not in ("all",) + allowed:
+            raise ValueError("reads must be one of %r" % (("all",) + allowed,))
+        return "all" if getattr(self, "_gram", None) is not None else reads
+
     def infer(self, batch, mask_text=False, mask_image=False, bool_masked_pos=None, image_token_type_idx=1,
-              image_embeds=None, image_masks=None):
-        """Joint text+image pass, reference :1071-1156."""
+              image_embeds=None, image_masks=None, reads="all"):
+        """Joint text+image pass, reference :1071-1156.  reads="text": the caller reads text_feats (and the cls rows in them)
+        only -- the last block and the final norm run on the text rows, image_feats is None."""
+        reads = self._reads(reads, ("text",))
         self._ensure_engine()
         imgkey = f"image_{image_token_type_idx - 1}" if f"image_{image_token_type_idx - 1}" in batch else "image"
         do_mlm = "_mlm" if mask_text else ""
@@ -543,10 +552,15 @@ class ViLTransformerSS(nn.Module):
         pc = self._pass_ctx(ops.Seq(B, T, I), self.hparams.config["num_heads"], self.get_rel_pos_bias(index, T),
                             keep0=text_masks.to(torch.uint8).contiguous(), keep1=keep1)
         pc.plan_drop_path(self._drop_sites(False))
-        for blk in self.transformer.blocks:
-            x = blk.run(x, pc, 2, self._hook())
+        last = len(self.transformer.blocks) - 1
+        for i, blk in enumerate(self.transformer.blocks):
+            x = blk.run(x, pc, 2, self._hook(), keep=(T, 0) if (reads == "text" and i == last) else None)
         x = self._final_norm(x)
-        text_feats, image_feats, text_cls, _ = engine.feature_views(x, B, T, I)
+        if reads == "text":  # x holds the B * T text rows
+            text_feats, _, text_cls, _ = engine.feature_views(x, B, T, 0)
+            image_feats = None
+        else:
+            text_feats, image_feats, text_cls, _ = engine.feature_views(x, B, T, I)
         cls_feats = self.pooler(text_feats, cls_rows=text_cls)
         return {"text_feats": text_feats, "image_feats": image_feats, "cls_feats": cls_feats,
                 "raw_cls_feats": text_cls, "image_labels": None, "image_masks": image_masks, "image": img,
@@ -590,12 +604,16 @@ class ViLTransformerSS(nn.Module):
                                  text_masks)
 
     def infer_unimodal_pair(self, batch, with_vlffn=True, mask_text=False, mask_image=False, image_token_type_idx=1,
-                            bool_masked_pos=None):
+                            bool_masked_pos=None, reads="all"):
         """(infer_image*, infer_text*) of one batch as ONE pass: text rows and image rows share every launch, block-
         diagonal attention (SEPARATE mode on the joint index, whose diagonal blocks ARE the unimodal indices) keeps
         them apart.  Each row computes exactly what its own unimodal pass computes (reference :1159-1464), the 880-row
-        text pass no longer costs ~150 tiny launches per step.  Returns (image result dict, text result dict)."""
+        text pass no longer costs ~150 tiny launches per step.  Returns (image result dict, text result dict).
+        reads="cls": the caller reads the cls features only -- the last block of each path and the final norm run on the 2B
+        cls rows (text rows first), text_feats and image_feats are None."""
         self._ensure_engine()
+        reads = self._reads(reads, ("cls",))
+        cls_only = (1, 1) if reads == "cls" else None
         do_mlm = "_mlm" if mask_text else ""
         text_ids, text_labels, text_masks = batch[f"text_ids{do_mlm}"], batch[f"text_labels{do_mlm}"], batch["text_masks"]
         imgkey = f"image_{image_token_type_idx - 1}" if f"image_{image_token_type_idx - 1}" in batch else "image"
@@ -618,40 +636,49 @@ class ViLTransformerSS(nn.Module):
         pc.plan_drop_path(self._drop_sites(with_vlffn))
         hs = None
         for i, blk in enumerate(self.transformer.blocks):
-            x = blk.run(x, pc, 3, self._hook())
+            x = blk.run(x, pc, 3, self._hook(), keep=cls_only if i == self.num_layers - 1 else None)
             if i == self.vlffn_start_layer_index - 1:
                 hs = x
         v = None
         if with_vlffn:
             v = hs
             for i in range(self.vlffn_start_layer_index, self.num_layers):
-                v = self.transformer.blocks[i].run(v, pc, 4, self._hook())
+                v = self.transformer.blocks[i].run(v, pc, 4, self._hook(), keep=cls_only if i == self.num_layers - 1 else None)
             v = self._final_norm(v)
         x = self._final_norm(x)
         # the views the two result dicts expose, one autograd node per feature matrix (engine.feature_views)
+        if cls_only is not None:  # x and v hold the B text cls rows, then the B image cls rows
+            lt = li = vt = vi = None
+            lt_cls, li_cls = engine.row_range(x, 0, B), engine.row_range(x, B, None)
+            vt_cls, vi_cls = (engine.row_range(v, 0, B), engine.row_range(v, B, None)) if v is not None else (None, None)
+            text = self._text_result(lt, vt, text_labels, text_ids, text_masks, lt_cls, vt_cls, has_v=v is not None)
+            image = self._image_result(li, vi, image_masks, text_masks, li_cls, vi_cls, has_v=v is not None)
+            return image, text
         lt, li, lt_cls, li_cls = engine.feature_views(x, B, T, I)
         vt, vi, vt_cls, vi_cls = engine.feature_views(v, B, T, I) if v is not None else (None, None, None, None)
         text = self._text_result(lt, vt, text_labels, text_ids, text_masks, lt_cls, vt_cls)
         image = self._image_result(li, vi, image_masks, text_masks, li_cls, vi_cls)
         return image, text
 
-    def _text_result(self, l, v, text_labels, text_ids, text_masks, l_cls=None, v_cls=None):
+    def _text_result(self, l, v, text_labels, text_ids, text_masks, l_cls=None, v_cls=None, has_v=None):
+        has_v = (v is not None) if has_v is None else has_v  # (a cls-only pass hands in the cls rows and no feature matrix)
         l_cls = l[:, 0] if l_cls is None else l_cls
-        v_cls = (v[:, 0] if v_cls is None else v_cls) if v is not None else None
+        v_cls = (v[:, 0] if v_cls is None else v_cls) if has_v else None
         cls = self._l2(self.ifm_text_proj(l_cls)) if getattr(self, "ifm_text_proj", None) is not None else None
-        cls_v = self._l2(self.ifm_vl_text_proj(v_cls)) if v is not None else None
+        cls_v = self._l2(self.ifm_vl_text_proj(v_cls)) if has_v else None
         return {"text_feats": l, "image_feats": None, "cls_feats": cls, "cls_vlffn_feats": cls_v,
                 "raw_cls_feats": l_cls, "image_labels": None, "image_masks": None, "text_labels": text_labels,
                 "text_ids": text_ids, "text_masks": text_masks, "patch_index": None}
 
-    def _image_result(self, vf, v, image_masks, text_masks, vf_cls=None, v_cls=None):
+    def _image_result(self, vf, v, image_masks, text_masks, vf_cls=None, v_cls=None, has_v=None):
+        has_v = (v is not None) if has_v is None else has_v
         vf_cls = vf[:, 0] if vf_cls is None else vf_cls
-        v_cls = (v[:, 0] if v_cls is None else v_cls) if v is not None else None
+        v_cls = (v[:, 0] if v_cls is None else v_cls) if has_v else None
         if getattr(self, "ifm_image_proj", None) is not None:
             cls = self._l2(self.ifm_image_proj(vf_cls))
         else:
             cls = self.pooler(vf, cls_rows=vf_cls)
-        cls_v = self._l2(self.ifm_vl_image_proj(v_cls)) if v is not None else None
+        cls_v = self._l2(self.ifm_vl_image_proj(v_cls)) if has_v else None
         return {"text_feats": None, "image_feats": vf, "cls_feats": cls, "cls_vlffn_feats": cls_v,
                 "raw_cls_feats": vf_cls, "image_labels": None, "image_masks": image_masks, "text_labels": None,
                 "text_ids": None, "text_masks": text_masks, "patch_index": None}

@@ -183,9 +183,10 @@ class Block(nn.Module):
         self._plans[k] = p
         return p
 
-    def run(self, x, pc, type_id, hook=None):
-        """x: fp32 [rows, D] (segment-major) -> fp32 [rows, D]."""
-        return engine.run_block(x, self.plan(type_id, pc.seq), pc, self.training, hook)
+    def run(self, x, pc, type_id, hook=None, keep=None):
+        """x: fp32 [rows, D] (segment-major) -> fp32 [rows, D]; keep = (k0, k1): only the rows of these per-segment prefixes
+        come back (engine.run_block: the last block of a pass whose heads read nothing else)."""
+        return engine.run_block(x, self.plan(type_id, pc.seq), pc, self.training, hook, keep)
 
     def forward(self, x, mask=None, type_id=None, relative_position_bias=None):
         """Reference-shaped entry (Block.forward(x[B,N,D], mask[B,N], type_id, relative_position_bias)) -> (x, None).
